@@ -7,6 +7,7 @@ One "step" = student quantized fwd + float-teacher fwd + SDR-weighted KD loss (P
 phase is passed in an untimed calibration before the warm-up).  Inputs are resident in HBM.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                  (also writes what the last timed step returned: DIR/<name>.npy)
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
 HIP-event timed live) and `cpu_baseline` (oracle/ = CPU port of the reference path, rank 0, N=1).
@@ -55,7 +56,98 @@ def parse():
     ap.add_argument("--other-warmup", type=int, default=5, help="warm-up replays of each `other_workloads` leg")
     ap.add_argument("--hd-batch", type=int, default=4, help="cfg5: samples per GPU (htdemucs.yaml: 32 over 8 GPUs)")
     ap.add_argument("--hd-seconds", type=float, default=10.0, help="cfg5: segment length in seconds (htdemucs.yaml: 10)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (rank 0; float32 / float64, "
+                         "64 MB at most: a larger array is replaced by a fixed seeded sample of its elements).  cfg2: the last timed step "
+                         "starts from a training state that is the same bit for bit in every run (see reproducible_state)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.workload not in ("cfg2", "infer"):
+        ap.error("--dump-outputs: the cfg2 (default) and infer workloads")
+    return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of `arrays` (name -> tensor / number; None entries are left out), float64 kept,
+    everything else as float32.  The budget of DUMP_BYTES is split evenly over the arrays; an array above its share is written as the
+    elements at a fixed, seeded (numpy PCG64, seed 0), sorted set of flat indices -- the same indices for the same shape in every run --
+    so that two builds can be compared output for output"""
+    import numpy as np
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = DUMP_BYTES // max(1, len(arrays)) - 4096          # (4 KiB for each file's .npy header)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        t = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        x = t.numpy()
+        if x.nbytes > share:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
+def _arena_slots(step):
+    """id(parameter) -> its offset in the step's ParamArena"""
+    return {id(p): o for p, o in zip(step.arena.params, step.arena.offsets)}
+
+
+def reproducible_state(dev, x, tgt):
+    """--dump-outputs, cfg 2: a training state that is the same bit for bit in every run, for the last timed step to start from.  The
+    timed steps sum their gradients with fp32 atomics, and Adam turns the rounding differences of that order into different weights
+    within a few steps, so the state the timed loop reaches differs from run to run.  This builds the same model (same seed) and runs
+    the same untimed calibration as main() -- observer step, 49 observer forwards, first quantizing step -- with FQSS_DETERMINISTIC=1
+    (integer gradient atomics, kernels.DetMode), and returns that model's parameters, Adam moments and clocks and its buffers, by name"""
+    import gc
+    from fqss_amd import kernels as K
+    from fqss_amd.runtime import KDTrainStep
+    from fqss_amd.smoke import build_pair
+    prev = os.environ.get("FQSS_DETERMINISTIC")
+    os.environ["FQSS_DETERMINISTIC"] = "1"
+    try:
+        model, fmodel = build_pair(dev, 0, n_spks=2, kernel_size=16, stride=8)
+        step = KDTrainStep(model, fmodel, kd_lambda=0.1, lr=1e-3, clip=5.0)
+        assert step.det is not None
+        step(x, tgt)
+        with torch.no_grad():
+            for _ in range(49):
+                model(x)
+        step(x, tgt)
+        torch.cuda.synchronize()
+        ar, slot = step.arena, _arena_slots(step)
+        state = {"params": {}, "buffers": {k: b.detach().clone() for k, b in model.named_buffers()},
+                 "step_t": ar.step_t.clone(), "host_step": ar._host_step}
+        for name, p in model.named_parameters():
+            if id(p) in slot:
+                o, n = slot[id(p)], p.numel()
+                state["params"][name] = tuple(t[o:o + n].clone() for t in (ar.flat_p, ar.exp_avg, ar.exp_avg_sq, ar.t0))
+        return state
+    finally:
+        K.DetMode.off()
+        if prev is None:
+            os.environ.pop("FQSS_DETERMINISTIC", None)
+        else:
+            os.environ["FQSS_DETERMINISTIC"] = prev
+        gc.collect()
+        torch.cuda.empty_cache()
+
+
+def load_state(model, step, state):
+    """copies reproducible_state() into the timed step's model and ParamArena in place (the captured graphs keep their addresses)"""
+    ar, slot = step.arena, _arena_slots(step)
+    named = dict(model.named_parameters())
+    assert set(named) == set(state["params"]), "reproducible_state: a different model"
+    with torch.no_grad():
+        for name, vals in state["params"].items():
+            o, n = slot[id(named[name])], named[name].numel()
+            for t, v in zip((ar.flat_p, ar.exp_avg, ar.exp_avg_sq, ar.t0), vals):
+                t[o:o + n].copy_(v)
+        for k, b in model.named_buffers():
+            b.copy_(state["buffers"][k])
+        ar.step_t.copy_(state["step_t"])
+    ar._host_step = state["host_step"]
 
 
 def dominant_kernel_roofline(dev, ms_step):
@@ -541,6 +633,8 @@ def main_infer(a):
         y = run(x)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"est": y})
     ms = dt / a.steps * 1e3
     fwd_bytes = 74.8e9 / 4.0                                  # one forward = a quarter of the step's algorithmic bytes
     print(json.dumps({"metric": "quantized inference samples/sec, ConvTasNet 2spk 8kHz W8A8", "value": round(8 * a.steps / dt, 2), "unit": "samples/s",
@@ -657,8 +751,9 @@ def main():
     torch.cuda.set_device(ldev)
     dev = torch.device("cuda", ldev)
 
-    model, fmodel = build_pair(dev, 0, n_spks=2, kernel_size=16, stride=8)   # same init on every rank
     x, tgt = synth_batch(B_PER_GPU, T_SAMPLES, seed=100 + comm.rank, device=dev)   # per-rank shard (weak scaling)
+    state = reproducible_state(dev, x, tgt) if a.dump_outputs else None
+    model, fmodel = build_pair(dev, 0, n_spks=2, kernel_size=16, stride=8)   # same init on every rank
     # a second, different batch: the timed loop alternates the two, so the teacher's look-ahead (its forward of batch n+1 runs on the
     # teacher stream beside the whole of step n) works on a mixture that is NOT the one the step is training on
     x2, tgt2 = synth_batch(B_PER_GPU, T_SAMPLES, seed=200 + comm.rank, device=dev)
@@ -694,14 +789,28 @@ def main():
     comm.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(a.steps - (state is not None)):
         r = step(X[it & 1], TG[it & 1], x_next=X[(it + 1) & 1])      # one student fwd + bwd + update AND one teacher forward per step
         it += 1
     torch.cuda.synchronize()
     comm.barrier()
-    dt = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
+    dt = time.perf_counter() - t0
+    if state is not None:
+        # --dump-outputs: the last timed step starts from the reproducible state, loaded outside the timed window
+        load_state(model, step, state)
+        torch.cuda.synchronize()
+        comm.barrier()
+        t0 = time.perf_counter()
+        r = step(X[it & 1], TG[it & 1], x_next=X[(it + 1) & 1])
+        it += 1
+        torch.cuda.synchronize()
+        comm.barrier()
+        dt += time.perf_counter() - t0
+    dt = torch.tensor([dt], device=dev, dtype=torch.float64)
     comm.all_reduce_max(dt)
     dt = dt.item()
+    if a.dump_outputs and comm.rank == 0:
+        dump_outputs(a.dump_outputs, r)          # before exchange_report's replays overwrite the graphs' static outputs
     sisdr = r["sisdr"].mean().reshape(1).double()
     comm.all_reduce_sum(sisdr)
     dist_info = exchange_report(step, comm, ldev, lambda i: step(X[i & 1], TG[i & 1], x_next=X[(i + 1) & 1]), it)
