@@ -544,7 +544,7 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_mfma(const float* __re
 //   * the lane's own row (q; k / v in the dk/dv pass; dO) is the B operand, split once into registers;
 //   * the B operand of the second product (V, K, dO, Q as [row = k][d = n]) comes out of the same planes through the transposing
 //     LDS read ds_read_tr16_b64 (the idiom of csrc/qgemm.hip).
-// Needs 16-B aligned rows (float4 global loads); the fp32-MFMA kernels above remain for everything else (FQSS_ATTN_MFMA=f32 forces them).
+// Needs 16-B aligned rows (float4 global loads); the fp32-MFMA kernels above remain for everything else.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -1448,16 +1448,6 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_c(const unsigned char*
     }
 }
 
-// 0: vector ALU, 1: fp32 MFMA, 2: split-bf16 MFMA (default where head_dim and alignment allow)
-static int attn_mfma_mode() {
-    static const int mode = [] {
-        const char* e = getenv("FQSS_ATTN_MFMA");
-        if (e && e[0] == '0') return 0;
-        if (e && (e[0] == 'f' || e[0] == '1')) return 1;
-        return 2;
-    }();
-    return mode;
-}
 static bool rows_aligned16(const void* const* ptrs, int np, const int64_t* st, int ns) {
     for (int t = 0; t < np; ++t) if (!aligned16(ptrs[t])) return false;
     for (int t = 0; t < ns; ++t) if (st[t] % 4 != 0) return false;
@@ -1493,9 +1483,8 @@ extern "C" int fqss_attn_long_fwd(const float* q, const float* k, const float* v
     FQSS_REQUIRE((obs_attn == nullptr) == (obs_soft == nullptr), "observer workspaces come in pairs");
     if (int rc = check_attn(Lq, Lk, B, nh, hd, strides, 4)) return rc;
     AttnGeom g{Lq, Lk, B, nh, {strides[0], strides[1]}, {strides[2], strides[3]}, {strides[4], strides[5]}, {strides[6], strides[7]}, {}, {}, {}, {}};
-    const int mode = attn_mfma_mode();
-    const bool use_mfma = mode != 0;
-    if (mode == 2 && (hd == 16 || hd == 32 || hd == 64)) {
+    // split-bf16 MFMA where head_dim and alignment allow, else fp32 MFMA (head_dim 32 / 64), else the vector ALU
+    if (hd == 16 || hd == 32 || hd == 64) {
         const void* ptrs[3] = {q, k, v};
         if (rows_aligned16(ptrs, 3, strides, 6)) {
             dim3 gm((unsigned)cdiv(Lq, 128), (unsigned)(B * nh));
@@ -1508,7 +1497,7 @@ extern "C" int fqss_attn_long_fwd(const float* q, const float* k, const float* v
             return launch_status("fqss_attn_long_fwd");
         }
     }
-    if (use_mfma && (hd == 32 || hd == 64)) {
+    if (hd == 32 || hd == 64) {
         dim3 gm((unsigned)cdiv(Lq, 128), (unsigned)(B * nh));
         if (hd == 32) hipLaunchKernelGGL((k_attn_long_fwd_mfma<32>), gm, dim3(256), 0, (hipStream_t)stream, q, k, v, o, stats, g, obs_attn, obs_soft);
         else hipLaunchKernelGGL((k_attn_long_fwd_mfma<64>), gm, dim3(256), 0, (hipStream_t)stream, q, k, v, o, stats, g, obs_attn, obs_soft);
@@ -1529,9 +1518,8 @@ extern "C" int fqss_attn_long_bwd(const float* q, const float* k, const float* v
     if (int rc = check_attn(Lq, Lk, B, nh, hd, strides, 8)) return rc;
     const int64_t* s = strides;
     AttnGeom g{Lq, Lk, B, nh, {s[0], s[1]}, {s[2], s[3]}, {s[4], s[5]}, {s[6], s[7]}, {s[8], s[9]}, {s[10], s[11]}, {s[12], s[13]}, {s[14], s[15]}};
-    const int mode = attn_mfma_mode();
-    const bool use_mfma = mode != 0;
-    if (mode == 2 && (hd == 16 || hd == 32 || hd == 64)) {
+    // split-bf16 MFMA where head_dim and alignment allow, else fp32 MFMA (head_dim 32 / 64), else the vector ALU
+    if (hd == 16 || hd == 32 || hd == 64) {
         const void* ptrs[5] = {q, k, v, o, go};
         if (rows_aligned16(ptrs, 5, strides, 10)) {
             dim3 gq_((unsigned)cdiv(Lq, 128), (unsigned)(B * nh)), gk_((unsigned)cdiv(Lk, 128), (unsigned)(B * nh));
@@ -1549,7 +1537,7 @@ extern "C" int fqss_attn_long_bwd(const float* q, const float* k, const float* v
             return launch_status("fqss_attn_long_bwd");
         }
     }
-    if (use_mfma && (hd == 32 || hd == 64)) {
+    if (hd == 32 || hd == 64) {
         dim3 gq_((unsigned)cdiv(Lq, 128), (unsigned)(B * nh)), gk_((unsigned)cdiv(Lk, 128), (unsigned)(B * nh));
         hipStream_t st = (hipStream_t)stream;
         if (hd == 32) {

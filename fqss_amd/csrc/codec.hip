@@ -455,9 +455,6 @@ static int frames_conv_impl(const char* who, const float* x, const float* w, flo
     if (N == 0 || M == 0) return FQSS_OK;
     hipStream_t s = (hipStream_t)stream;
     {   // four frames per lane: vector-aligned rows with readable / writable padding, dense 16-B aligned signals
-        // A/B switch, bit (Ci - 1)
-        static const int wide_ci = [] { const char* e = getenv("FQSS_FRAMES_WIDE"); return e ? atoi(e) : 3; }();
-        const bool wide_on = Ci <= 2 && ((wide_ci >> (Ci - 1)) & 1);
         const int64_t m4 = (M + 3) & ~(int64_t)3;
         const bool k16 = K == 16 && stride == 8, k32 = K == 32 && stride == 16;
         int co_tile = (int)((48 * 1024) / ((size_t)Ci * K * sizeof(float))) & ~3;      // output channels whose taps fit 48 KB of LDS
@@ -465,7 +462,7 @@ static int frames_conv_impl(const char* who, const float* x, const float* w, flo
         size_t lds = (size_t)co_tile * Ci * K * sizeof(float);
         static const int taps_lds = [] { const char* e = getenv("FQSS_TAPS_LDS"); return e ? atoi(e) : 1; }();   // A/B switch
         if (!taps_lds) { co_tile = -1; lds = 0; }       // taps by wave-uniform loads from memory
-        if (wide_on && (k16 || k32) && (Ci == 1 || Ci == 2) && aligned16(x) && T % 4 == 0 && T >= 4 && aligned16(z) && ld_z % 4 == 0 &&
+        if ((k16 || k32) && (Ci == 1 || Ci == 2) && aligned16(x) && T % 4 == 0 && T >= 4 && aligned16(z) && ld_z % 4 == 0 &&
             ld_z >= m4 && (!add || (aligned16(add) && ld_add % 4 == 0 && ld_add >= m4))) {
             // slices of the output channels in grid.z until ~512 workgroups are in flight (>= 32 channels per slice)
             int64_t zs = cdiv(512, cdiv(M, 256) * (int64_t)N);
@@ -523,9 +520,8 @@ static int ola_convtr_impl(const char* who, int mode, const void* x, const float
     hipStream_t s = (hipStream_t)stream;
     if (NS < 1) NS = 1;
     {   // (16, 8) window on vector-aligned rows: the matrix-core form
-        static const bool mfma_on = [] { const char* e = getenv("FQSS_OLA_MFMA"); return !(e && e[0] == '0'); }();   // A/B switch
         const int64_t m4 = (M + 3) & ~(int64_t)3;
-        bool ok = mfma_on && K == 16 && stride == 8 && ld_x >= m4 && aligned16(x) && (mode == 1 ? ld_x % 16 == 0 : ld_x % 4 == 0);
+        bool ok = K == 16 && stride == 8 && ld_x >= m4 && aligned16(x) && (mode == 1 ? ld_x % 16 == 0 : ld_x % 4 == 0);
         if (mode == 2) ok = ok && aligned16(feat) && ld_f % 4 == 0 && ld_f >= m4;
         if (ok) {
             dim3 gridm((unsigned)cdiv((int64_t)M + 1, 60), (unsigned)N);

@@ -393,8 +393,7 @@ extern "C" int fqss_frames_gather(const float* x, float* frames, FQSS_GEOM_ARGS,
     FQSS_GEOM_INIT;
     if (int rc = check_geom(g)) return rc;
     FQSS_REQUIRE(Ho * Wo < (1ll << 24) && H * W < (1ll << 31), "frame plane too large (positions are split by a float reciprocal: < 2^24)");
-    static const bool one = getenv("FQSS_GATHER_V1") != nullptr;       // (A/B knob: the one-element kernel)
-    if (!one && ld % 4 == 0 && aligned16(frames))
+    if (ld % 4 == 0 && aligned16(frames))
         hipLaunchKernelGGL(k_frames_gather4, plane_grid(Ho * Wo, B * C * kh * kw), dim3(256), 0, (hipStream_t)stream, x, frames, g);
     else
         hipLaunchKernelGGL(k_frames_gather, plane_grid(Ho * Wo, B * C * kh * kw), dim3(256), 0, (hipStream_t)stream, x, frames, g);
@@ -415,8 +414,7 @@ extern "C" int fqss_frames_ola(const float* frames, const float* bias, float* y,
         else hipLaunchKernelGGL(k_frames_ola_rows<0>, grid, dim3(256), 0, (hipStream_t)stream, frames, bias, y, g);
         return launch_status("fqss_frames_ola");
     }
-    static const bool one = getenv("FQSS_OLA_V1") != nullptr;       // (A/B knob: the one-element kernel)
-    if (!one && kw == 1 && st_w == 1 && pw == 0 && W >= 8)
+    if (kw == 1 && st_w == 1 && pw == 0 && W >= 8)
         hipLaunchKernelGGL(k_frames_ola_col4, plane_grid(H * W, B * C), dim3(256), 0, (hipStream_t)stream, frames, bias, y, g);
     else
         hipLaunchKernelGGL(k_frames_ola, plane_grid(H * W, B * C), dim3(256), 0, (hipStream_t)stream, frames, bias, y, g);
@@ -612,8 +610,7 @@ extern "C" int fqss_phase_unpack(const float* gy, float* gx, int64_t B, int64_t 
     FQSS_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (axis == 0 || (axis == 1 && H == 1)) && s >= 1 && p >= 0 && off >= 0, "bad shape");
     FQSS_REQUIRE(Wp % 4 == 0 && (axis == 0 ? plane >= Hy * Wp : (Hy <= Wp && plane >= Wp)) && H * W < (1ll << 24), "packed planes");
     FQSS_REQUIRE(sh >= W && sc >= sh * (H - 1) + W && (B == 1 || sb >= sc * (C - 1) + W), "bad strides");
-    static const bool one = getenv("FQSS_UNPACK_V1") != nullptr;       // (A/B knob: the one-element kernel)
-    if (!one && W >= 8)
+    if (W >= 8)
         hipLaunchKernelGGL(k_phase_unpack4, plane_grid(H * ((W + 3) / 4) * 4, B * C), dim3(256), 0, (hipStream_t)stream, gy, gx, B * C, (int)C, (int)H, (int)W,
                            sb, sc, sh, axis, s, p, (int)Hy, (int)Wp, plane, off, bias);
     else

@@ -731,10 +731,7 @@ extern "C" int fqss_actq_fwd(const float* z, float* out, uint8_t* idx, int64_t r
     // element by element (store_group4: the output may be a column block of a wider matrix).  Round 6; before, "fewer than 4 floats of
     // row padding" was required and every activation padded to 64 B by more -- [B, C, 110250] -> 110256 -- took the one-element path.
     // (The packed codes of a partial group go out as one word: code rows are padded by their owner, kernels.empty_codes.)
-    bool vec = aligned16(z) && (!out || aligned16(out)) && (ld_z % 4 == 0) && (ld_out % 4 == 0);
-#ifdef FQSS_OLD_TAIL_RULE      // (A/B builds only: `make variant SRC=fq NAME=oldtail DEFS=-DFQSS_OLD_TAIL_RULE`)
-    vec = vec && ((cols % 4 == 0) || (out == nullptr) || (ld_out - cols < 4));
-#endif
+    const bool vec = aligned16(z) && (!out || aligned16(out)) && (ld_z % 4 == 0) && (ld_out % 4 == 0);
     hipStream_t s = (hipStream_t)stream;
     if (vec && act < FQSS_ACT_GELU && qmode == FQSS_Q_QUANT && cols % 4 == 0 && cols <= 512 && rows >= 1024 &&
         (!idx || ((ld_idx & 3) == 0 && (reinterpret_cast<uintptr_t>(idx) & 3u) == 0))) {
@@ -826,10 +823,7 @@ extern "C" int fqss_actq_bwd(const float* z, const float* g, float* gz, int64_t 
     // (16-B groups whenever the rows are 16-B aligned: the loads of a row's last group stay inside its stride, the store of a partial
     // group writes its live elements only -- round 6; the rule before, "fewer than 4 floats of padding", sent every activation whose
     // rows are padded to 64 B by more than that -- [B, C, 110250] -> 110256 -- down the one-element path)
-    bool vec = aligned16(z) && aligned16(g) && aligned16(gz) && (ld_z % 4 == 0) && (ld_g % 4 == 0) && (ld_gz % 4 == 0);
-#ifdef FQSS_OLD_TAIL_RULE
-    vec = vec && ((cols % 4 == 0) || (ld_gz - cols < 4));
-#endif
+    const bool vec = aligned16(z) && aligned16(g) && aligned16(gz) && (ld_z % 4 == 0) && (ld_g % 4 == 0) && (ld_gz % 4 == 0);
     hipStream_t s = (hipStream_t)stream;
     const int v = vec ? 4 : 1;
     int64_t gx = cdiv(cols, 256 * (int64_t)v);

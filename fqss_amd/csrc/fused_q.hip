@@ -603,227 +603,6 @@ __global__ __launch_bounds__(256) void k_dwq_fwd(const uint8_t* __restrict__ xc,
     }
 }
 
-#ifdef FQSS_EXPERIMENTS   // round-4 experiment, measured slower: built by `make experiments` only (declared in include/fqss_experiments.h)
-// gLN + fake-quant FOLLOWED BY depthwise conv + PReLU + fake-quant, both on codes, as ONE launch (round 4; the teacher's k_tdw does the
-// same in float): a workgroup takes `rpw` consecutive rows; per row it normalises + re-quantises the 16 input codes of every thread
-// (k_gnq_apply's arithmetic, codes written to HBM -- the backward of both layers reads them -- AND to an LDS row), then runs the
-// 3-tap FIR + PReLU + quantizer of k_dwq_fwd<3> out of that LDS row.  One launch and one 4-KB re-read per row less; every value is
-// computed by the op sequences of the two kernels it replaces (gate: tests/test_gpu_kernels.py::test_gn_dw_fused_bit_identical).
-// Rows of at most 4096 positions (256 threads x 16), K = 3, statistics of the INPUT codes supplied by their producer.
-__global__ __launch_bounds__(256) void k_gndwq_fwd(const uint8_t* __restrict__ xc, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    uint8_t* __restrict__ y1, float* __restrict__ mean_rstd, const long long* __restrict__ ws,
-                                                    int nslots, float eps, int B, int C, int M, int64_t ld_xc, int64_t ld_y1,
-                                                    const float* qmin_x, const float* qmax_x, const float* qmin1, const float* qmax1,
-                                                    const float* __restrict__ w, const float* __restrict__ bias, int dil, int pad, int act,
-                                                    const float* slope_p, uint8_t* __restrict__ y2, int64_t ld_y2, const float* qmin2,
-                                                    const float* qmax2, long long* stats2, int rpw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rowbuf[];      // [padl + 4096 + pad + 16]
-    __shared__ long long red[2 * 4];
-    __shared__ float mr[2];
-    __shared__ unsigned int sred[2 * 4];
-    const QRange rx = load_qrange(qmin_x, qmax_x), r1 = load_qrange(qmin1, qmax1), r2 = load_qrange(qmin2, qmax2);
-    const float slope = (act == FQSS_ACT_PRELU) ? *slope_p : 0.0f;
-    const int rows = B * C, padl = (pad + 15) & ~15;
-    const int m0 = threadIdx.x * 16;
-    int b_have = -1;
-    for (int r0 = blockIdx.x * rpw; r0 < rows; r0 += gridDim.x * rpw)
-    for (int row = r0; row < min(rows, r0 + rpw); ++row) {
-        const int b = row / C, c = row - b * C;
-        uint4 v0 = make_uint4(0, 0, 0, 0);
-        if (m0 < M) v0 = *reinterpret_cast<const uint4*>(xc + (int64_t)row * ld_xc + m0);
-        if (b != b_have) {    // block-uniform
-            gnq_sample_stats(ws, nslots, b, (int64_t)C * M, eps, rx, red, mr);
-            b_have = b;
-            if (c == 0 && threadIdx.x == 0) {   // saved for the GroupNorm's backward
-                mean_rstd[2 * b] = mr[0];
-                mean_rstd[2 * b + 1] = mr[1];
-            }
-        }
-        const float scale = mr[1] * gamma[c];
-        const float shift = fmaf(-scale, mr[0], beta[c]);
-        if (m0 < M) {        // ---- GroupNorm + quantizer: k_gnq_apply's arithmetic
-            const unsigned int wv[4] = {v0.x, v0.y, v0.z, v0.w};
-            unsigned int o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float xv[4];
-                dec4(wv[q], rx, xv);
-                unsigned int pk = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pk = pack_code(fq_code(fmaf(xv[e], scale, shift), r1), e, pk);
-                o[q] = pk;
-            }
-            const uint4 ov = make_uint4(o[0], o[1], o[2], o[3]);
-            *reinterpret_cast<uint4*>(y1 + (int64_t)row * ld_y1 + m0) = ov;
-            *reinterpret_cast<uint4*>(rowbuf + padl + m0) = ov;
-        }
-        __syncthreads();
-        // ---- depthwise 3-tap FIR + PReLU + quantizer: k_dwq_fwd<3>'s arithmetic, taps from the LDS row
-        float wk[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) wk[k] = w[c * 3 + k];
-        const float bv = bias ? bias[c] : 0.0f;
-        unsigned int st_s = 0, st_ss = 0;
-        if (m0 < M) {
-            const bool inner = (m0 - pad >= 0) && (m0 + 15 + pad < M);
-            unsigned int o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = m0 + 4 * q;
-                float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const int s0 = m + k * dil - pad;
-                    float v[4];
-                    if (inner) {
-                        const int a = padl + s0;                               // >= 0: inner
-                        const unsigned int lo = *reinterpret_cast<const unsigned int*>(rowbuf + (a & ~3));
-                        const unsigned int hi = *reinterpret_cast<const unsigned int*>(rowbuf + (a & ~3) + 4);
-                        dec4(__builtin_amdgcn_alignbyte(hi, lo, (unsigned)(a & 3)), r1, v);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = (s0 + j >= 0 && s0 + j < M) ? dec((unsigned int)rowbuf[padl + s0 + j], r1) : 0.0f;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = fmaf(wk[k], v[j], acc[j]);
-                }
-                unsigned int pk = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pk = pack_code(fq_code(act_apply(acc[j] + bv, act, slope), r2), j, pk);
-                o[q] = pk;
-                const unsigned int live = (m + 3 < M) ? 0xFFFFFFFFu : ((m < M) ? (0xFFFFFFFFu >> (8 * (4 - (M - m)))) : 0u);
-                code_stats4(pk & live, st_s, st_ss);
-            }
-            *reinterpret_cast<uint4*>(y2 + (int64_t)row * ld_y2 + m0) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-        if (stats2 != nullptr) {   // one slot per row; block_sum's barriers also protect the LDS row against the next row's stores
-            unsigned int v[2] = {st_s, st_ss};
-            block_sum<unsigned int, 2>(v, sred);
-            if (threadIdx.x == 0) {
-                stats2[2 * (int64_t)row] = (long long)v[0];
-                stats2[2 * (int64_t)row + 1] = (long long)v[1];
-            }
-        } else {
-            __syncthreads();
-        }
-    }
-}
-#endif  // FQSS_EXPERIMENTS
-
-#ifdef FQSS_EXPERIMENTS   // round-5 experiment (the table form of the fused forward): bit-identical, STILL slower than the two launches (39.6 vs 33.5 us)
-// gLN + fake-quant FOLLOWED BY the 3-tap depthwise conv + PReLU + fake-quant, codes -> codes -> codes, as ONE launch -- round 5, on
-// code tables (the round-4 form above computed both layers per element and lost to the two launches: both halves were bound by vector
-// issue).  Per (b, c) row the GroupNorm's output code is a function T of the input code (k_gnq_apply_t), and what the FIR needs of it
-// -- its de-quantised value -- is another: V[c] = delta1 * T[c] + min1.  A workgroup takes RPW consecutive rows of one sample; per row
-// thread t evaluates T[t] and V[t] once (256-B + 1-KB LDS tables), the row's INPUT codes go to an LDS row, and then
-//   y1[m] = T[x[m]]                                   (one byte lookup per element, stored for the backward of both layers)
-//   z[m]  = fma(w2, V[x[m + d]], fma(w1, V[x[m]], w0 * V[x[m - d]])) + b     (three float lookups instead of three decodes)
-//   y2[m] = fq(PReLU(z[m]))                           (k_dwq_fwd<3>'s arithmetic), + the integer statistics of y2 for the next gLN.
-// Every value is what fqss_gnq_fwd + fqss_dwq_fwd compute (tests/test_gpu_kernels.py::test_gn_dw_fused_bit_identical); ~20 vector
-// instructions per element instead of 3 + 27, one launch and one 16-MB re-read less.  Rows of at most 4096 positions, K = 3.
-__global__ __launch_bounds__(256) void k_gndwq_fwd_t(const uint8_t* __restrict__ xc, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      uint8_t* __restrict__ y1, float* __restrict__ mean_rstd, const long long* __restrict__ ws,
-                                                      int nslots, float eps, int B, int C, int M, int64_t ld_xc, int64_t ld_y1,
-                                                      const float* qmin_x, const float* qmax_x, const float* qmin1, const float* qmax1,
-                                                      const float* __restrict__ w, const float* __restrict__ bias, int dil, int pad, int act,
-                                                      const float* slope_p, uint8_t* __restrict__ y2, int64_t ld_y2, const float* qmin2,
-                                                      const float* qmax2, long long* stats2, int rpw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rowbuf[];      // [padl + 4096 + pad + 16]: the row's INPUT codes
-    __shared__ long long red[2 * 4];
-    __shared__ float mr[2];
-    __shared__ unsigned int sred[2 * 4];
-    __shared__ __attribute__((aligned(16))) uint8_t tabC[256];
-    __shared__ __attribute__((aligned(16))) float tabV[256];
-    const QRange rx = load_qrange(qmin_x, qmax_x), r1 = load_qrange(qmin1, qmax1), r2 = load_qrange(qmin2, qmax2);
-    const float slope = (act == FQSS_ACT_PRELU) ? *slope_p : 0.0f;
-    const int rows = B * C, padl = (pad + 15) & ~15;
-    const int m0 = threadIdx.x * 16;
-    const float xt = dec(threadIdx.x, rx);
-    int b_have = -1;
-    for (int r0 = blockIdx.x * rpw; r0 < rows; r0 += gridDim.x * rpw)
-    for (int row = r0; row < min(rows, r0 + rpw); ++row) {
-        const int b = row / C, c = row - b * C;
-        uint4 v0 = make_uint4(0, 0, 0, 0);
-        if (m0 < M) v0 = *reinterpret_cast<const uint4*>(xc + (int64_t)row * ld_xc + m0);
-        if (b != b_have) {    // block-uniform
-            gnq_sample_stats(ws, nslots, b, (int64_t)C * M, eps, rx, red, mr);
-            b_have = b;
-            if (c == 0 && threadIdx.x == 0) {   // saved for the GroupNorm's backward
-                mean_rstd[2 * b] = mr[0];
-                mean_rstd[2 * b + 1] = mr[1];
-            }
-        }
-        const float scale = mr[1] * gamma[c];
-        const float shift = fmaf(-scale, mr[0], beta[c]);
-        {
-            const float c1 = fq_code(fmaf(xt, scale, shift), r1);      // k_gnq_apply's arithmetic, once per code
-            tabC[threadIdx.x] = (uint8_t)c1;
-            tabV[threadIdx.x] = r1.delta * c1 + r1.lo;                   // dec() of that code, as k_dwq_fwd reads it
-        }
-        if (m0 < M) *reinterpret_cast<uint4*>(rowbuf + padl + m0) = v0;
-        __syncthreads();
-        float wk[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) wk[k] = w[c * 3 + k];
-        const float bv = bias ? bias[c] : 0.0f;
-        unsigned int st_s = 0, st_ss = 0;
-        if (m0 < M) {
-            {   // ---- the GroupNorm's output codes (for the backward of both layers)
-                const unsigned int wv[4] = {v0.x, v0.y, v0.z, v0.w};
-                unsigned int o[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    o[q] = (unsigned int)tabC[wv[q] & 255u] | ((unsigned int)tabC[(wv[q] >> 8) & 255u] << 8) |
-                           ((unsigned int)tabC[(wv[q] >> 16) & 255u] << 16) | ((unsigned int)tabC[wv[q] >> 24] << 24);
-                *reinterpret_cast<uint4*>(y1 + (int64_t)row * ld_y1 + m0) = make_uint4(o[0], o[1], o[2], o[3]);
-            }
-            const bool inner = (m0 - pad >= 0) && (m0 + 15 + pad < M);
-            unsigned int o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = m0 + 4 * q;
-                float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const int s0 = m + k * dil - pad;
-                    float v[4];
-                    if (inner) {
-                        const int a = padl + s0;                               // >= 0: inner
-                        const unsigned int lo = *reinterpret_cast<const unsigned int*>(rowbuf + (a & ~3));
-                        const unsigned int hi = *reinterpret_cast<const unsigned int*>(rowbuf + (a & ~3) + 4);
-                        const unsigned int cw = __builtin_amdgcn_alignbyte(hi, lo, (unsigned)(a & 3));
-                        v[0] = tabV[cw & 255u]; v[1] = tabV[(cw >> 8) & 255u]; v[2] = tabV[(cw >> 16) & 255u]; v[3] = tabV[cw >> 24];
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = (s0 + j >= 0 && s0 + j < M) ? tabV[rowbuf[padl + s0 + j]] : 0.0f;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = fmaf(wk[k], v[j], acc[j]);
-                }
-                unsigned int pk = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pk = pack_code(fq_code(act_apply(acc[j] + bv, act, slope), r2), j, pk);
-                o[q] = pk;
-                const unsigned int live = (m + 3 < M) ? 0xFFFFFFFFu : ((m < M) ? (0xFFFFFFFFu >> (8 * (4 - (M - m)))) : 0u);
-                code_stats4(pk & live, st_s, st_ss);
-            }
-            *reinterpret_cast<uint4*>(y2 + (int64_t)row * ld_y2 + m0) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-        if (stats2 != nullptr) {   // one slot per row; block_sum's barriers also protect the LDS row and tables against the next row's stores
-            unsigned int v[2] = {st_s, st_ss};
-            block_sum<unsigned int, 2>(v, sred);
-            if (threadIdx.x == 0) {
-                stats2[2 * (int64_t)row] = (long long)v[0];
-                stats2[2 * (int64_t)row + 1] = (long long)v[1];
-            }
-        } else {
-            __syncthreads();
-        }
-    }
-}
-
-#endif  // FQSS_EXPERIMENTS
-
 // backward: recompute z, STE + PReLU -> gz (fp32), bias row-sums, range/slope partials (gacc slots)
 template <int NQ>   // float4 groups per thread and pass: a workgroup covers NQ * 1024 consecutive positions
 __global__ __launch_bounds__(256) void k_dwq_bwd_z(const uint8_t* __restrict__ xc, const float* __restrict__ w,
@@ -930,19 +709,6 @@ struct DwGnBefore {
     double* gacc;                            // partial slots of its output quantizer (= this layer's input range)
 };
 
-#ifndef FQSS_DWB_ABL
-#define FQSS_DWB_ABL 0      // timing ablations (tools only): 1 no coefficient sums in the GA prologue, 2 no phase 2, 4 no final reductions, 8 no phase-1 arithmetic
-#endif
-// FQSS_DWB_STAMPS (tools/dwb_stamps.py only): wave 0 of every workgroup records s_memtime at its phase boundaries; the eight deltas
-// (16 shader cycles per unit) replace the row's two doubles in GBd.ws
-#ifdef FQSS_DWB_STAMPS
-#define DWB_STAMP(k) do { if (threadIdx.x == 0) stamp_[k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define DWB_STAMP(k) do { } while (0)
-#endif
-#ifndef FQSS_DWB_GPP
-#define FQSS_DWB_GPP 2      // float4 groups per thread and pass (a pass = 1024 x GPP positions; the thread -> element order does not depend on it)
-#endif
 template <int KT, bool GA = false, bool GB = false, int ACTC = -1>   // KT: taps known at compile time (3 on the training path) or 0: runtime K <= kTaps;
                                                                        // ACTC >= 0: the activation known at compile time (PReLU in the TCN blocks)
 __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc, const float* __restrict__ w,
@@ -961,10 +727,6 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
     // entries made every lookup a 2- / 4-bank access: LDS conflict rate 1.59, profiles/r05_sq_counters.txt)
     __shared__ float tabA0[GA ? 256 : 1], tabA1[GA ? 256 : 1];            // GA: fma(x, c2, c3) | in-range, per code of THIS layer's output
     __shared__ float tabB0[GB ? 256 : 1], tabB1[GB ? 256 : 1], tabB2[GB ? 256 : 1];   // GB: x | c - u or c | in-range, per code of the GroupNorm's input
-#ifdef FQSS_DWB_STAMPS
-    unsigned long long stamp_[9];
-#endif
-    DWB_STAMP(0);
     const bool det_on = det_preload();
     const QRange rx = load_qrange(qmin_x, qmax_x), ry = load_qrange(qmin, qmax);
     const float slope = (act == FQSS_ACT_PRELU) ? *slope_p : 0.0f;
@@ -973,7 +735,7 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
     // (the straight loop exposed one HBM round trip per group: PMC showed the waves parked 46 % of the time)
     const uint8_t* xr = xc + (int64_t)row * ld_xc;
     const float* gr = g + (int64_t)row * ld_g;
-    constexpr int GPP = FQSS_DWB_GPP;
+    constexpr int GPP = 2;      // float4 groups per thread and pass (a pass = 1024 x GPP positions; the thread -> element order does not depend on it)
     float4 gq[GPP];
     unsigned int cw[GPP][NT];
     bool inner[GPP];
@@ -1018,7 +780,7 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
         float c2v, c3v;
         {
             double sv[2] = {0.0, 0.0};
-            for (int cc = threadIdx.x; cc < ((FQSS_DWB_ABL & 1) ? 0 : C); cc += 256) {
+            for (int cc = threadIdx.x; cc < C; cc += 256) {
                 const double gmm = (double)GAd.gamma[cc];
                 sv[0] += gmm * GAd.ws[2 * ((int64_t)b * C + cc)];
                 sv[1] += gmm * GAd.ws[2 * ((int64_t)b * C + cc) + 1];
@@ -1059,7 +821,6 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
         tabB2[threadIdx.x] = in1 ? 1.0f : 0.0f;
     }
     if constexpr (GA || GB) __syncthreads();
-    DWB_STAMP(1);      // prologue done
     float wk[NT], pw[NT];
 #pragma unroll
     for (int k = 0; k < NT; ++k) {
@@ -1084,13 +845,6 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
         for (int i = 0; i < GPP; ++i) {
             const int m = m0 + 1024 * i;
             if (m >= M) break;
-            if constexpr (FQSS_DWB_ABL & 8) {
-                float4 t = gq[i];
-#pragma unroll
-                for (int k = 0; k < NT; ++k) t.x += __uint_as_float(cw[i][k]);
-                *reinterpret_cast<float4*>(&sgz[m]) = t;
-                continue;
-            }
             float v[NT][4], acc[4] = {0.f, 0.f, 0.f, 0.f};
             if (inner[i]) {   // no padding masks, one unaligned dword per tap
 #pragma unroll
@@ -1154,12 +908,10 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
             *reinterpret_cast<float4*>(&sgz[m]) = make_float4(o[0], o[1], o[2], o[3]);
         }
     }
-    DWB_STAMP(2);      // phase 1 done (loads + arithmetic)
     __syncthreads();
-    DWB_STAMP(3);      // barrier passed
 
     float q_ds = 0.f, q_db = 0.f, q_du = 0.f, q_out = 0.f;      // GB: the producing GroupNormQ's row sums / range partials
-    if (want_gx && !(FQSS_DWB_ABL & 2)) {
+    if (want_gx) {
         float* xo = gx + (int64_t)row * ld_gx;
         const bool aligned = ((dil & 3) == 0) && ((pad & 3) == 0);
         const uint8_t* x0r = GB ? GBd.xc0 + (int64_t)row * GBd.ld_xc0 : nullptr;
@@ -1208,11 +960,6 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
             }
         }
     }
-    DWB_STAMP(4);      // phase 2 done
-    if constexpr (FQSS_DWB_ABL & 4) {
-        if (p_du + p_out + p_slope + p_bias + pw[0] + q_ds + q_db + q_du + q_out == 1.2345f) gacc[0] = 1.0;
-        return;
-    }
     // ONE block reduction for the layer's own partials and (GB) the producing GroupNormQ's: one barrier pair and one serial section of
     // thread 0 instead of two (each value keeps its own summation tree: same bits as two reductions)
     constexpr int NQ = GB ? 4 : 0;
@@ -1226,7 +973,6 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
         else pf[4 + NT] = 0.f;
         block_sum_f32w<4 + NT + (GB ? 4 : 1)>(pf, redf, v);
     }
-    DWB_STAMP(5);
     if (threadIdx.x == 0) {
         if constexpr (GB) {
             const double* qv = v + 4 + NT;
@@ -1247,22 +993,6 @@ __global__ __launch_bounds__(256) void k_dwq_bwd(const uint8_t* __restrict__ xc,
             for (int k = 0; k < K; ++k) grad_add(&gw[c * K + k], (float)v[4 + k], det_on);
     }
     (void)NQ;
-#ifdef FQSS_DWB_STAMPS
-    DWB_STAMP(6);
-    if constexpr (GB) {
-        if (threadIdx.x == 0) {
-            unsigned long long w0_ = 0, w1_ = 0;
-            for (int k = 0; k < 6; ++k) {
-                unsigned long long d = (stamp_[k + 1] - stamp_[k]) >> 4;
-                d = d > 65535 ? 65535 : d;
-                if (k < 4) w0_ |= d << (16 * k); else w1_ |= d << (16 * (k - 4));
-            }
-            w1_ |= ((stamp_[0] >> 8) & 0xffffffffull) << 32;        // start time in units of 256 cycles (relative order of the workgroups)
-            reinterpret_cast<unsigned long long*>(GBd.ws)[2 * (int64_t)row] = w0_;
-            reinterpret_cast<unsigned long long*>(GBd.ws)[2 * (int64_t)row + 1] = w1_;
-        }
-    }
-#endif
 }
 
 // gw[c][k] += sum_{b,m} gz[b][c][m] * decode(x[b][c][m + k*dil - pad])   ; grid (C, B), 4 m per thread
@@ -1396,12 +1126,10 @@ __device__ __forceinline__ float ew_producer_bwd(const EwProducer& P, const QRan
     }
 }
 
-#ifndef FQSS_EWQ_NR
-#define FQSS_EWQ_NR 2        // rows of loads in flight per thread (x FQSS_EWQ_WAVES waves per SIMD; 8 x 2 first: 196 VGPRs; round 5, the fused
+constexpr int EWQ_NR = 2;    // rows of loads in flight per thread (x FQSS_EWQ_WAVES waves per SIMD; 8 x 2 first: 196 VGPRs; round 5, the fused
                              // residual-add launch alone, us: 8 x 2 24.4, 8 x 3 32.0, 4 x 3 24.9, 3 x 3 23.6, 2 x 3 22.0, 2 x 4 22.3, 1 x 3 21.4, 1 x 4 21.2 --
                              // the step within +-0.03 ms for every row but 8 x 3 (+0.4); same per-thread summation order whatever NR)
 #define FQSS_EWQ_WAVES 3
-#endif
 template <bool PLAIN>
 __global__ __launch_bounds__(256, FQSS_EWQ_WAVES) void k_ewq_bwd(const uint8_t* __restrict__ ac, const uint8_t* __restrict__ bc,
                                                   const float* __restrict__ bf, float sb, const float* __restrict__ g,
@@ -1486,7 +1214,7 @@ __global__ __launch_bounds__(256, FQSS_EWQ_WAVES) void k_ewq_bwd(const uint8_t* 
         // consumed, UNCONDITIONALLY (row / column clamped into the tensor, the results of clamped groups dropped): a branch around a
         // load makes the compiler retire the loads in flight first, and the kernel is latency-bound (2 waves per SIMD, PMC: 64 % of
         // the wave time waiting on memory)
-        constexpr int NR = FQSS_EWQ_NR;
+        constexpr int NR = EWQ_NR;
         const bool active = c_first < cols;
         const int c_ld = active ? c_first : 0;
         const int rstep = gridDim.y;
@@ -2014,60 +1742,6 @@ extern "C" int fqss_gnq_bwd_apply(const uint8_t* xc, const float* qmin_x, const 
                         qmin, qmax, nullptr, const_cast<double*>(ws), P, stream, 2);
 }
 
-#ifdef FQSS_EXPERIMENTS
-/* GroupNormQ followed by a 3-tap depthwise Conv1dNlQ, both in their quantizing phase, codes -> codes -> codes in ONE launch on code tables
- * (k_gndwq_fwd_t, round 5): y1 = the GroupNorm's output codes (range 1), y2 = the depthwise layer's (range 2); stats = the producer's
- * statistics of xc ([B][nslots][2]), stats2 (nullable) = [B][C][2] statistics of y2 for a GroupNormQ behind it.  M <= 4096, K = 3;
- * bit-identical to fqss_gnq_fwd + fqss_dwq_fwd. */
-extern "C" int fqss_gndwq_fwd(const uint8_t* xc, const float* qmin_x, const float* qmax_x, const float* gamma, const float* beta, float eps,
-                              const int64_t* stats, int nslots, float* mean_rstd, uint8_t* y1, const float* qmin1, const float* qmax1,
-                              const float* w, const float* bias, int dil, int pad, int act, const float* slope, uint8_t* y2,
-                              const float* qmin2, const float* qmax2, int64_t* stats2, int B, int C, int M, int64_t ld_xc, int64_t ld_y1,
-                              int64_t ld_y2, fqss_stream_t stream) {
-    if (B == 0 || M == 0) return FQSS_OK;
-    FQSS_REQUIRE(xc && qmin_x && qmax_x && gamma && beta && stats && mean_rstd && y1 && qmin1 && qmax1 && w && y2 && qmin2 && qmax2, "null pointer");
-    FQSS_REQUIRE(B > 0 && C > 0 && M > 0 && M <= 4096 && dil > 0 && pad == dil && pad <= 2048, "rows of at most 4096 positions, 3 taps");
-    FQSS_REQUIRE(nslots > 0 && nslots <= 1024, "supplied statistics: 1 .. 1024 partial-sum slots per sample");
-    FQSS_REQUIRE(ld_xc >= M && ld_y1 >= M && ld_y2 >= M && codes_ok(xc, ld_xc) && codes_ok(y1, ld_y1) && codes_ok(y2, ld_y2), "code rows must be 16-B aligned");
-    FQSS_REQUIRE(act != FQSS_ACT_PRELU || slope, "PReLU needs a slope");
-    const int64_t rows = (int64_t)B * C;
-    FQSS_REQUIRE(rows < (1ll << 30), "tensor too large");
-    const int rpw = (rows >= 2048 && C % 4 == 0) ? 4 : ((rows >= 1024 && C % 2 == 0) ? 2 : 1);     // rows of ONE sample per workgroup
-    const size_t smem = (size_t)(((pad + 15) & ~15) + 4096 + pad + 16);
-    hipLaunchKernelGGL(k_gndwq_fwd_t, dim3((unsigned)cdiv(rows, rpw)), dim3(256), smem, (hipStream_t)stream, xc, gamma, beta, y1, mean_rstd,
-                       (const long long*)stats, nslots, eps, B, C, M, ld_xc, ld_y1, qmin_x, qmax_x, qmin1, qmax1, w, bias, dil, pad, act, slope, y2,
-                       ld_y2, qmin2, qmax2, (long long*)stats2, rpw);
-    return launch_status("fqss_gndwq_fwd");
-}
-
-#endif  // FQSS_EXPERIMENTS
-
-#ifdef FQSS_EXPERIMENTS
-/* GroupNormQ followed by a depthwise Conv1dNlQ, both in their quantizing phase, codes -> codes -> codes in one launch (k_gndwq_fwd):
- * y1 = the GroupNorm's output codes (range 1), y2 = the depthwise layer's (range 2); stats = the producer's statistics of xc ([B][nslots][2]),
- * stats2 (nullable) = [B][C][2] statistics of y2 for a GroupNormQ behind it.  M <= 4096, K = 3; bit-identical to fqss_gnq_fwd + fqss_dwq_fwd. */
-extern "C" int fqss_gndwq_fwd_v1(const uint8_t* xc, const float* qmin_x, const float* qmax_x, const float* gamma, const float* beta, float eps,
-                              const int64_t* stats, int nslots, float* mean_rstd, uint8_t* y1, const float* qmin1, const float* qmax1,
-                              const float* w, const float* bias, int dil, int pad, int act, const float* slope, uint8_t* y2,
-                              const float* qmin2, const float* qmax2, int64_t* stats2, int B, int C, int M, int64_t ld_xc, int64_t ld_y1,
-                              int64_t ld_y2, fqss_stream_t stream) {
-    if (B == 0 || M == 0) return FQSS_OK;
-    FQSS_REQUIRE(xc && qmin_x && qmax_x && gamma && beta && stats && mean_rstd && y1 && qmin1 && qmax1 && w && y2 && qmin2 && qmax2, "null pointer");
-    FQSS_REQUIRE(B > 0 && C > 0 && M > 0 && M <= 4096 && dil > 0 && pad == dil && pad <= 2048, "rows of at most 4096 positions, 3 taps");
-    FQSS_REQUIRE(nslots > 0 && nslots <= 1024, "supplied statistics: 1 .. 1024 partial-sum slots per sample");
-    FQSS_REQUIRE(ld_xc >= M && ld_y1 >= M && ld_y2 >= M && codes_ok(xc, ld_xc) && codes_ok(y1, ld_y1) && codes_ok(y2, ld_y2), "code rows must be 16-B aligned");
-    FQSS_REQUIRE(act != FQSS_ACT_PRELU || slope, "PReLU needs a slope");
-    const int64_t rows = (int64_t)B * C;
-    FQSS_REQUIRE(rows < (1ll << 30), "tensor too large");
-    const int rpw = rows >= 2048 ? 4 : 1;
-    const size_t smem = (size_t)(((pad + 15) & ~15) + 4096 + pad + 16);
-    hipLaunchKernelGGL(k_gndwq_fwd, dim3((unsigned)cdiv(rows, rpw)), dim3(256), smem, (hipStream_t)stream, xc, gamma, beta, y1, mean_rstd,
-                       (const long long*)stats, nslots, eps, B, C, M, ld_xc, ld_y1, qmin_x, qmax_x, qmin1, qmax1, w, bias, dil, pad, act, slope, y2,
-                       ld_y2, qmin2, qmax2, (long long*)stats2, rpw);
-    return launch_status("fqss_gndwq_fwd_v1");
-}
-#endif  // FQSS_EXPERIMENTS
-
 extern "C" int fqss_dwq_fwd(const uint8_t* xc, const float* qmin_x, const float* qmax_x, const float* w, const float* bias,
                             uint8_t* yc, float* yout, int B, int C, int M, int K, int dil, int pad, int64_t ld_xc,
                             int64_t ld_yc, int64_t ld_out, int act, const float* slope, const float* qmin, const float* qmax,
@@ -2087,8 +1761,6 @@ extern "C" int fqss_dwq_fwd(const uint8_t* xc, const float* qmin_x, const float*
         grid = dim3((unsigned)cdiv(M, 4096), (unsigned)rows, 1);
         FQSS_REQUIRE(rows <= 65535 * 16, "output statistics: too many rows");
         if (rows > 65535) grid.y = 65535;   // (rows strided over y keep their own slots: indexed by row)
-        static const int rpw = getenv("FQSS_DWF_RPW") ? atoi(getenv("FQSS_DWF_RPW")) : 1;       // A/B knob: rows per workgroup
-        if (rpw > 1) grid.y = (unsigned)cdiv(rows, rpw);
     }
     if (K == 3)
         hipLaunchKernelGGL(k_dwq_fwd<3>, grid, dim3(256), 0, (hipStream_t)stream, xc, w, bias, yc, yout, (int)rows, C, M, K, dil,

@@ -363,7 +363,7 @@ extern "C" int fqss_frames_wgrad(const float* a, const float* x, float* gw, int 
 }
 
 // split-bf16 variant (csrc/gemm_x3.hip): same problem description, 2-3x the fp32-MFMA throughput; `used` = false when its
-// 16-B vector loads do not apply (the caller then runs k_gemm_f32).  FQSS_ROWGEMM_X3=0 in the environment forces the fallback.
+// 16-B vector loads do not apply (the caller then runs k_gemm_f32).
 namespace fqss {
 struct GemmArgs3 {          // keep in sync with csrc/gemm_x3.hip
     const float* A;
@@ -397,19 +397,10 @@ int launch_gemm_x3q(const GemmArgs3& g, int bq, hipStream_t s, const char* what)
 // workgroups a row-major weight gradient aims for: every k-slice ADDS its whole Co x Ci tile with float atomics, so the slice count
 // is a trade between atomic traffic (measured: half of the kernel at 125 slices for a 256 x 256 gradient) and occupancy -- 512, and
 // 256 for outputs of at most four 128 x 128 tiles (tools/kprobe.py sweep: 256 x 256 coded 43 -> 32 us)
-static int rowgrad_wgs(int tiles) {
-    static const int n = [] { const char* e = getenv("FQSS_WGRAD_WGS"); const int v = e ? atoi(e) : 0; return v; }();
-    return n > 0 ? n : (tiles <= 4 ? 256 : 512);
-}
-
-static bool x3_enabled() {
-    static const bool on = [] { const char* e = getenv("FQSS_ROWGEMM_X3"); return !(e && e[0] == '0'); }();
-    return on;
-}
+static int rowgrad_wgs(int tiles) { return tiles <= 4 ? 256 : 512; }
 
 static int try_x3(const GemmArgs& g, bool a_kc, bool b_kc, bool atomic, hipStream_t s, const char* what, bool* used, int batch) {
     *used = false;
-    if (!x3_enabled()) return FQSS_OK;
     if (batch > 1 && (g.sAb % 4 != 0 || g.sBb % 4 != 0)) return FQSS_OK;      // every batch's operand 16-B aligned
     GemmArgs3 h{g.A, g.B, g.C, g.bias, g.bias_col, g.M, g.N, g.K, g.sAi, g.sAk, g.sBk, g.sBj, g.sCi, g.ksplit, g.kchunk, nullptr, nullptr, nullptr, nullptr,
                 batch, g.sAb, g.sBb, g.sCb, 0, 0, 0, 0, 0, 0, nullptr, 0, 0};

@@ -61,9 +61,6 @@ struct GemmArgs3 {
     float* rowsum_out;       // BQ = 1, optional: sum_k A(i, k) is ADDED here ([M]: the bias gradient of the linear whose weight gradient this is)
 };
 
-#ifndef FQSS_X3_PF
-#define FQSS_X3_PF 1     // operand tiles in flight per workgroup (register images)
-#endif
 // LDS rows are 32 bf16 = 64 B with NO padding; the four 16-B chunks of a row are stored XOR-swizzled by (row >> 2) & 3, so that the
 // sixteen rows a quarter-wave reads with one ds_read_b128 -- same logical chunk -- fall on sixteen different 16-B bank groups (rows r and
 // r + 4 are 256 B apart: the swizzle separates them; rows r .. r + 3 are 64 B apart).  The padded layout of rounds 1-3 (80-B rows) cost
@@ -319,7 +316,7 @@ __device__ __forceinline__ void x3_body(GemmArgs3 g, const int bx, const int by,
     // PF register images of the operands in flight: the tile of step kt + PF is requested while step kt computes.  One image (rounds 1-3)
     // gave a load one k-tile's time to arrive; the short-K row GEMMs with one workgroup per CU (266 workgroups of 4 waves: one wave per
     // SIMD, nothing to switch to) then waited out most of an HBM round trip per k-tile.
-    constexpr int PF = FQSS_X3_PF;
+    constexpr int PF = 1;    // operand tiles in flight per workgroup (register images)
     using TileA = TileIO<BMt, A_KC>;
     static_assert(!BPL || (BQ == 0 && !IMP && B_KC && !ATOMIC), "pre-split B: the forward form");
     using TileB = std::conditional_t<BPL, TileIOP<BNt>,
@@ -559,19 +556,6 @@ static bool x3_ok(const GemmArgs3& g, bool a_kc, bool b_kc, bool atomic) {
     return ok;
 }
 
-// A/B switches of the tile rules (tools/kprobe.py): FQSS_X3_LDS_PAD = bytes of unused dynamic LDS per workgroup (caps the workgroups per
-// CU; -1: every form padded to 61,440 B, the size before the planes were sized by the tile), FQSS_X3_MI = 1 / 2 forces the 64- / 128-row tile where both exist
-static unsigned x3_lds_pad(int mi, int ni, bool coded) {
-    static const int v = [] { const char* e = getenv("FQSS_X3_LDS_PAD"); return e ? atoi(e) : 0; }();
-    if (v >= 0) return (unsigned)v;
-    const int used = max(3 * 64 * mi * XLDK * 2 + (coded ? 1 : 3) * 64 * ni * XLDK * 2, 4 * 32 * 36 * 4);     // < 0: pad every form to the 61,440 B of rounds 1-3
-    return used < 61440 ? (unsigned)(61440 - used) : 0u;
-}
-static int x3_force_mi() {
-    static const int v = [] { const char* e = getenv("FQSS_X3_MI"); return e ? atoi(e) : 0; }();
-    return v;
-}
-
 static int x3_scalar_stores() {
     static const int v = [] { const char* e = getenv("FQSS_X3_STAGED"); return (e && e[0] == '0') ? 1 : 0; }();
     return v;
@@ -599,20 +583,18 @@ int launch_gemm_x3(const GemmArgs3& g_in, bool a_kc, bool b_kc, bool atomic, hip
         const int64_t t2 = cdiv(g.M, 128) * cdiv(g.N, 128) * zdim;
         mi = (a_kc && !b_kc) ? (t2 < 256 ? 1 : 2) : (t2 < 320 ? 1 : 2);
     }
-    if (x3_force_mi() && ni == 2 && g.M > 64) mi = x3_force_mi() == 2 ? 2 : 1;
-    if (x3_force_mi() == 3 && ni == 2 && g.M > 64 && !(a_kc && b_kc && g.Bp != nullptr)) ni = 1;      // 64 x 64 tiles (sweeps)
     dim3 grid((unsigned)cdiv(g.N, 64 * ni), (unsigned)cdiv(g.M, 64 * mi), (unsigned)zdim), block(256);
 #define FQSS_X3(AK, BKc, AT)                                                                                  \
     do {                                                                                                      \
-        if (mi == 1 && ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 1, 1>), grid, block, x3_lds_pad(1, 1, false), s, g);    \
-        else if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 2, 2>), grid, block, x3_lds_pad(2, 2, false), s, g);    \
-        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 2, 1>), grid, block, x3_lds_pad(2, 1, false), s, g);          \
-        else hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 1, 2>), grid, block, x3_lds_pad(1, 2, false), s, g);                       \
+        if (mi == 1 && ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 1, 1>), grid, block, 0, s, g);    \
+        else if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 2, 2>), grid, block, 0, s, g);    \
+        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 2, 1>), grid, block, 0, s, g);          \
+        else hipLaunchKernelGGL((k_gemm_x3<AK, BKc, AT, 1, 2>), grid, block, 0, s, g);                       \
     } while (0)
     if (!atomic && a_kc && b_kc && g.Bp != nullptr) {                  // fwd on the weight's pre-split planes
-        if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<true, true, false, 2, 2, 0, false, true>), grid, block, x3_lds_pad(2, 2, false), s, g);
-        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<true, true, false, 2, 1, 0, false, true>), grid, block, x3_lds_pad(2, 1, false), s, g);
-        else hipLaunchKernelGGL((k_gemm_x3<true, true, false, 1, 2, 0, false, true>), grid, block, x3_lds_pad(1, 2, false), s, g);
+        if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<true, true, false, 2, 2, 0, false, true>), grid, block, 0, s, g);
+        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<true, true, false, 2, 1, 0, false, true>), grid, block, 0, s, g);
+        else hipLaunchKernelGGL((k_gemm_x3<true, true, false, 1, 2, 0, false, true>), grid, block, 0, s, g);
     } else if (!atomic && a_kc && b_kc) FQSS_X3(true, true, false);   // fwd:   x [R][Ci], w [Co][Ci]
     else if (!atomic && a_kc && !b_kc) FQSS_X3(true, false, false);   // dgrad: gz [R][Co], w [Co][Ci] (j contiguous)
     else if (atomic && !a_kc && !b_kc) FQSS_X3(false, false, true);   // wgrad: gz^T, x (both row-index contiguous)
@@ -637,14 +619,14 @@ int launch_gemm_x3_imp(const GemmArgs3& g_in, bool wgrad, hipStream_t s, const c
     else if (g.M <= 64) mi = 1;
     // narrow outputs (the DConv convolutions, C / 8 channels): 64 x 128 tiles of one batch leave half the chip without a workgroup
     // (4 x 1 x 32 = 128 of them at [B F][C][431]) -- 64 x 64 tiles there
-    if (!wgrad && mi == 1 && ni == 2 && cdiv(g.N, 128) * cdiv(g.M, 64) * zdim < 256 && x3_force_mi() != 1) ni = 1;
+    if (!wgrad && mi == 1 && ni == 2 && cdiv(g.N, 128) * cdiv(g.M, 64) * zdim < 256) ni = 1;
     dim3 grid((unsigned)cdiv(g.N, 64 * ni), (unsigned)cdiv(g.M, 64 * mi), (unsigned)zdim), block(256);
 #define FQSS_X3I(BKc, AT)                                                                                              \
     do {                                                                                                               \
-        if (mi == 1 && ni == 1) hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 1, 1, 0, true>), grid, block, x3_lds_pad(1, 1, false), s, g);  \
-        else if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 2, 2, 0, true>), grid, block, x3_lds_pad(2, 2, false), s, g);  \
-        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 2, 1, 0, true>), grid, block, x3_lds_pad(2, 1, false), s, g);        \
-        else hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 1, 2, 0, true>), grid, block, x3_lds_pad(1, 2, false), s, g);                     \
+        if (mi == 1 && ni == 1) hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 1, 1, 0, true>), grid, block, 0, s, g);  \
+        else if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 2, 2, 0, true>), grid, block, 0, s, g);  \
+        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 2, 1, 0, true>), grid, block, 0, s, g);        \
+        else hipLaunchKernelGGL((k_gemm_x3<true, BKc, AT, 1, 2, 0, true>), grid, block, 0, s, g);                     \
     } while (0)
     if (wgrad) FQSS_X3I(true, true); else FQSS_X3I(false, false);
 #undef FQSS_X3I
@@ -668,15 +650,13 @@ int launch_gemm_x3q(const GemmArgs3& g_in, int bq, hipStream_t s, const char* wh
     // (measured over the cfg 3 / 4 / 5 shapes, tools/kprobe.py: 512 x 512 float 91 -> 74 us, coded 71 -> 61 us)
     if (atomic && g.M > 64 && g.N > 64) mi = 2;
     if (!atomic && g.M > 128 && g.N > 64) mi = cdiv(g.M, 128) * cdiv(g.N, 128) * zdim < 320 ? 1 : 2;
-    if (x3_force_mi() && ni == 2 && g.M > 64) mi = x3_force_mi() == 2 ? 2 : 1;
-    if (x3_force_mi() == 3 && ni == 2 && g.M > 64) ni = 1;
     dim3 grid((unsigned)cdiv(g.N, 64 * ni), (unsigned)cdiv(g.M, 64 * mi), (unsigned)zdim), block(256);
 #define FQSS_X3Q(AK, AT, Q)                                                                                      \
     do {                                                                                                         \
-        if (mi == 1 && ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 1, 1, Q>), grid, block, x3_lds_pad(1, 1, true), s, g);  \
-        else if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 2, 2, Q>), grid, block, x3_lds_pad(2, 2, true), s, g);  \
-        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 2, 1, Q>), grid, block, x3_lds_pad(2, 1, true), s, g);        \
-        else hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 1, 2, Q>), grid, block, x3_lds_pad(1, 2, true), s, g);                     \
+        if (mi == 1 && ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 1, 1, Q>), grid, block, 0, s, g);  \
+        else if (mi == 2 && ni == 2) hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 2, 2, Q>), grid, block, 0, s, g);  \
+        else if (ni == 1) hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 2, 1, Q>), grid, block, 0, s, g);        \
+        else hipLaunchKernelGGL((k_gemm_x3<AK, false, AT, 1, 2, Q>), grid, block, 0, s, g);                     \
     } while (0)
     if (bq == 1) FQSS_X3Q(false, true, 1);
     else FQSS_X3Q(true, false, 2);
@@ -716,8 +696,7 @@ extern "C" int fqss_qrow_bwd_w_group(const FqssRowWgradJob* jobs, int njobs, fqs
             for (int q = 0; q < n; ++q) tiles += cdiv(jobs[idx[n0 + q]].Co, 64 * mi) * cdiv(jobs[idx[n0 + q]].Ci, 64 * ni);
             // aim for ~6 workgroups per CU over the launch (sweep on cfg 4, profiles/r05_ab_steps.txt: 512 .. 6144 within 2.5 %, 1536 best); every
             // k-slice ADDS its whole tile with float atomics, so no finer than needed
-            static const int wgs = [] { const char* e = getenv("FQSS_ROWGROUP_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1536; }();
-            int want = (int)cdiv(wgs, tiles);
+            int want = (int)cdiv(1536, tiles);
             X3WMulti m{};
             m.n = n;
             int start = 0;

@@ -33,12 +33,6 @@ namespace fqss {
 
 constexpr int kNB = 2;   // sequences per workgroup
 
-// timing experiments only (make variant SRC=lstm DEFS=-DFQSS_LSTM_ABL=n; never in the product library): 1 no FMAs, 2 no LDS reads of h,
-// 4 no gate transcendentals, 8 no tanh(c), 16 no global stores, 32 no input-projection loads
-#ifndef FQSS_LSTM_ABL
-#define FQSS_LSTM_ABL 0
-#endif
-
 struct LstmBiasGrads {      // gradient buffers of b_ih / b_hh, forward and reverse direction ([4H] each; null: not wanted)
     float *ih_f, *hh_f, *ih_r, *hh_r;
 };
@@ -49,35 +43,19 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // whh   [2][4H][H], bhh [2][4H]
 // hout  [S][B][2H]     (forward | reverse halves)
 // gsav  [S][B][2][4H]  gate activations, csav [S][B][2][2][H] cell states c | tanh(c) (the backward needs both: no tanh in its loop)
-template <int HT>
-__global__ __launch_bounds__(HT > 0 ? 4 * HT : 1024) void k_lstm_fwd(const float* __restrict__ pre, const float* __restrict__ whh,
-                                                                      const float* __restrict__ bhh, float* __restrict__ hout,
-                                                                      float* __restrict__ gsav, float* __restrict__ csav, int S,
-                                                                      int B, int Hrt) {
-    const int H = HT > 0 ? HT : Hrt;
+// Any H <= 256 (H = 128 runs k_lstm_fwd_st below).
+__global__ __launch_bounds__(1024) void k_lstm_fwd(const float* __restrict__ pre, const float* __restrict__ whh,
+                                                   const float* __restrict__ bhh, float* __restrict__ hout,
+                                                   float* __restrict__ gsav, float* __restrict__ csav, int S,
+                                                   int B, int H) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* hs = smem;                 // [kNB][H]
-    float* gs = smem + kNB * (H + 16);       // [kNB][4H]   (hs: [kNB][4 quarters][H/4 + 4] when H is compile-time)
+    float* gs = smem + kNB * (H + 16);       // [kNB][4H]
     const int dir = blockIdx.y;
     const int b0 = blockIdx.x * kNB;
     const int j = threadIdx.x;        // gate row (j < 4H)
     const bool jv = j < 4 * H;
     const float* W = whh + ((int64_t)dir * 4 * H + (jv ? j : 0)) * H;
-    // HT > 0: a QUAD of lanes shares four gate rows (4q .. 4q+3), lane kq of the quad keeps the k-quarter [32 kq, 32 kq + 32) of
-    // each of them: the same 128 weight registers as "one row per thread", but a lane now reads a quarter of h per step instead
-    // of all of it (every lane fetching all 2 x 128 values was 512 KB of LDS reads per step = the whole step time at 128 B/clk);
-    // the four partial sums of a row meet by two quad-permute DPP adds
-    constexpr int KQ = HT > 0 ? HT / 4 : 1;                 // k values per lane and row
-    constexpr int HQS = KQ + 4;                             // quarter stride in LDS (floats): the 4 quarters hit different banks
-    const int q4 = j >> 2, kq = j & 3;
-    float wreg[HT > 0 ? HT : 1];
-    if constexpr (HT > 0) {
-        const float* Wq = whh + ((int64_t)dir * 4 * H + q4 * 4) * H + kq * KQ;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int k = 0; k < KQ; ++k) wreg[r * KQ + k] = Wq[(int64_t)r * H + k];
-    }
     const float bj = jv ? bhh[dir * 4 * H + j] : 0.f;
     for (int e = threadIdx.x; e < kNB * (H + 16); e += blockDim.x) hs[e] = 0.f;
     float c = 0.f;                    // cell state of (nb, k) = (threadIdx / H, threadIdx % H) for threadIdx < kNB*H
@@ -96,7 +74,7 @@ __global__ __launch_bounds__(HT > 0 ? 4 * HT : 1024) void k_lstm_fwd(const float
         const int tn = dir == 0 ? sn : S - 1 - sn;
 #pragma unroll
         for (int nb = 0; nb < kNB; ++nb)
-            dst[nb] = (FQSS_LSTM_ABL & 32) != 0 ? 0.25f : pre[(((int64_t)tn * B + min(b0 + nb, B - 1)) * 2 + dir) * 4 * H + jc];
+            dst[nb] = pre[(((int64_t)tn * B + min(b0 + nb, B - 1)) * 2 + dir) * 4 * H + jc];
     };
 #pragma unroll
     for (int u = 0; u < kPF; ++u) fetch(pf[u], u);
@@ -106,51 +84,10 @@ __global__ __launch_bounds__(HT > 0 ? 4 * HT : 1024) void k_lstm_fwd(const float
             float acc[kNB];
 #pragma unroll
             for (int nb = 0; nb < kNB; ++nb) acc[nb] = 0.f;
-            if constexpr (HT > 0) {
-                float part[4][kNB];
+            for (int k = 0; k < H; ++k) {
+                const float wv = W[k];
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int nb = 0; nb < kNB; ++nb) part[r][nb] = 0.f;
-#pragma unroll
-                for (int k = 0; k < KQ; k += 4) {
-#pragma unroll
-                    for (int nb = 0; nb < kNB; ++nb) {
-                        float4 hv;
-                        if constexpr ((FQSS_LSTM_ABL & 2) != 0) hv = make_float4(wreg[k], wreg[k + 1], wreg[k + 2], wreg[k + 3]);
-                        else hv = *reinterpret_cast<const float4*>(hs + (nb * 4 + kq) * HQS + k);
-                        if constexpr ((FQSS_LSTM_ABL & 1) != 0) {
-                            part[k & 3][nb] += (hv.x + hv.y) + (hv.z + hv.w);
-                            continue;
-                        }
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            part[r][nb] = fmaf(wreg[r * KQ + k], hv.x, part[r][nb]);
-                            part[r][nb] = fmaf(wreg[r * KQ + k + 1], hv.y, part[r][nb]);
-                            part[r][nb] = fmaf(wreg[r * KQ + k + 2], hv.z, part[r][nb]);
-                            part[r][nb] = fmaf(wreg[r * KQ + k + 3], hv.w, part[r][nb]);
-                        }
-                    }
-                }
-                // sum over the quad (lanes kq = 0..3), then lane kq keeps row 4q + kq = its own row j
-#pragma unroll
-                for (int nb = 0; nb < kNB; ++nb) {
-                    float mine = 0.f;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float t = part[r][nb];
-                        t += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-                        t += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(t), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-                        mine = (kq == r) ? t : mine;
-                    }
-                    acc[nb] = mine;
-                }
-            } else {
-                for (int k = 0; k < H; ++k) {
-                    const float wv = W[k];
-#pragma unroll
-                    for (int nb = 0; nb < kNB; ++nb) acc[nb] = fmaf(wv, hs[nb * H + k], acc[nb]);
-                }
+                for (int nb = 0; nb < kNB; ++nb) acc[nb] = fmaf(wv, hs[nb * H + k], acc[nb]);
             }
             // every gate row applies its OWN non-linearity here, all waves busy and the kNB sequences of a lane independent (the cell
             // threads used to do all four per element: 3 sigmoids + 2 tanh as one dependent chain on half of the waves, the longest
@@ -159,9 +96,9 @@ __global__ __launch_bounds__(HT > 0 ? 4 * HT : 1024) void k_lstm_fwd(const float
 #pragma unroll
             for (int nb = 0; nb < kNB; ++nb) {
                 const float pre_act = pcur[nb] + (acc[nb] + bj);
-                const float a = (FQSS_LSTM_ABL & 4) != 0 ? pre_act * 0.01f : (is_g ? tanhf(pre_act) : sigmoidf_(pre_act));
+                const float a = is_g ? tanhf(pre_act) : sigmoidf_(pre_act);
                 gs[nb * 4 * H + j] = a;
-                if ((FQSS_LSTM_ABL & 16) == 0 && gsav != nullptr && b0 + nb < B) gsav[((((int64_t)t * B + b0 + nb) * 2) + dir) * 4 * H + j] = a;   // (NULL: inference)
+                if (gsav != nullptr && b0 + nb < B) gsav[((((int64_t)t * B + b0 + nb) * 2) + dir) * 4 * H + j] = a;   // (NULL: inference)
             }
         }
         __syncthreads();
@@ -169,13 +106,12 @@ __global__ __launch_bounds__(HT > 0 ? 4 * HT : 1024) void k_lstm_fwd(const float
             const float* g = gs + cn * 4 * H;
             const float gi = g[ck], gf = g[H + ck], gg = g[2 * H + ck], go = g[3 * H + ck];
             c = gf * c + gi * gg;
-            const float tc = (FQSS_LSTM_ABL & 8) != 0 ? c * 0.5f : tanhf(c);
+            const float tc = tanhf(c);
             const float h = go * tc;
-            if constexpr (HT > 0) hs[(cn * 4 + ck / KQ) * HQS + (ck % KQ)] = h;
-            else hs[cn * H + ck] = h;
+            hs[cn * H + ck] = h;
             const int64_t sb = (int64_t)t * B + b0 + cn;
-            if ((FQSS_LSTM_ABL & 16) == 0 || step == S - 1) hout[sb * 2 * H + dir * H + ck] = h;
-            if ((FQSS_LSTM_ABL & 16) == 0 && csav != nullptr) {
+            hout[sb * 2 * H + dir * H + ck] = h;
+            if (csav != nullptr) {
                 csav[(sb * 2 + dir) * 2 * H + ck] = c;
                 csav[(sb * 2 + dir) * 2 * H + H + ck] = tc;
             }
@@ -532,17 +468,13 @@ extern "C" int fqss_lstm_fwd(const float* pre, const float* whh, const float* bh
     FQSS_REQUIRE(S > 0 && B > 0 && H > 0 && H <= 256, "bad shape (H <= 256)");
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)cdiv(B, kNB), 2);
-    const size_t lds = (size_t)(kNB * (H + 16) + kNB * 4 * H) * sizeof(float);
-    // FQSS_LSTM_V1=1 (read per call: tests and A/B runs toggle it): the round-2 form of the H = 128 forward
-    const char* v1 = getenv("FQSS_LSTM_V1");
-    if (H == 128 && !(v1 && atoi(v1) != 0)) {
+    if (H == 128) {
         const size_t lds2 = (size_t)(kNB * 4 * (H / 4 + 4) + kNB * 4 * H) * sizeof(float);
         hipLaunchKernelGGL(k_lstm_fwd_st<128>, grid, dim3(512), lds2, s, pre, whh, bhh, hout, gsav, csav, S, B);
-    } else if (H == 128) {
-        hipLaunchKernelGGL((k_lstm_fwd<128>), grid, dim3(512), lds, s, pre, whh, bhh, hout, gsav, csav, S, B, H);
     } else {
+        const size_t lds = (size_t)(kNB * (H + 16) + kNB * 4 * H) * sizeof(float);
         const int threads = (int)cdiv(4 * H, 64) * 64;
-        hipLaunchKernelGGL((k_lstm_fwd<0>), grid, dim3(threads), lds, s, pre, whh, bhh, hout, gsav, csav, S, B, H);
+        hipLaunchKernelGGL(k_lstm_fwd, grid, dim3(threads), lds, s, pre, whh, bhh, hout, gsav, csav, S, B, H);
     }
     return launch_status("fqss_lstm_fwd");
 }

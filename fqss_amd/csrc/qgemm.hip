@@ -21,7 +21,7 @@
 // global loads, XCD-aware tile order, LDS-staged 16-B/lane epilogue.  The forward epilogue can also apply the layer's
 // own non-linearity + fake-quant and emit the output codes (fqss_qpw_fwdq); two layers on one input (res | skip)
 // run as one GEMM over concatenated channels (fqss_qpw_*2).
-// wgrad (k_qwgrad): register-direct fragments, no LDS, 4-stage hand-scheduled load ring, float atomics.
+// wgrad (k_qwgrad2): LDS-tiled 64 x 128 x 64 stages, a ring of four hand-scheduled register stages, float atomics.
 //
 // Reference replaced: F.conv1d(k=1) of Conv1dQ / Conv1dNlQ (qat_layers.py:137-146, 202-212) and its autograd.
 #include <cstdlib>
@@ -44,9 +44,7 @@ constexpr int QBM = 128, QBN = 64, QBK = 32;
 constexpr int LDK = 40;    // bf16 per row of a k-contiguous image (32 + 8 pad = 80 B: conflict-free ds_read_b128)
 constexpr int LDN = 96;    // bf16 per row of an n-contiguous image (64 + 32 pad = 192 B: conflict-free tr reads)
 constexpr int LDT = 36;    // fp32 per row of the epilogue staging tile (32 + 4 pad, 16-B aligned rows)
-#ifndef FQSS_WGRAD_BLOCKS
-#define FQSS_WGRAD_BLOCKS 256   // one workgroup per CU: the fp32 atomics of the epilogue cost ~20 ns per workgroup-tile, more slices lose
-#endif
+constexpr int WGRAD_BLOCKS = 256;   // one workgroup per CU: the fp32 atomics of the epilogue cost ~20 ns per workgroup-tile, more slices lose
 
 __device__ __forceinline__ unsigned short f2bf_trunc(float f) { return (unsigned short)(__float_as_uint(f) >> 16); }
 __device__ __forceinline__ float bf_trunc(float f) { return __uint_as_float(__float_as_uint(f) & 0xFFFF0000u); }
@@ -143,7 +141,7 @@ struct QGemmArgs {
 };
 
 // MODE 0 fwd (int8 A codes, u8 B codes)            1 dgrad (int8 A codes, fp32 B split3)
-//      3 plain fp32 x fp32 (A split3 x B split3 = 9 exact products; GP = 2: the six above 2^-24)   (wgrad: k_qwgrad below)
+//      3 plain fp32 x fp32 (A split3 x B split3 = 9 exact products; GP = 2: the six above 2^-24)   (wgrad: k_qwgrad2 below)
 // GP (dgrad only): bf16 pieces of the fp32 gradient operand.  3 = exact products (a = h1 + h2 + h3, truncations): the default.  2 = an
 // OPT-IN fast form (FQSS_GRAD_PIECES=2): a ~ h1 + RNE_bf16(a - h1), 16-17 significant bits, |error| <= 2^-16 |a|, unbiased; one third
 // fewer MFMAs and LDS bytes: -1.7 / -5.5 us (dgrad), -4 / -6 us (wgrad) = -0.4 ms per cfg-2 step.  Measured against fp64
@@ -593,23 +591,9 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// wgrad, register-direct:  gW_q[co][ci] += dx * sum_n gz[co][n]*c[ci][n] + min_x * sum_n gz[co][n]
-// Both operands are n-contiguous in HBM and n is the reduction index, so every lane can load its MFMA
-// fragment straight from global memory: lane (row lr, half lh) of a 32-wide k chunk owns the 16
-// consecutive positions n0+16*lh .. +15 of "its" gz row (64 B) and of "its" code row (16 B); the two k-steps
-// of the chunk use the first / second 8 of them for A and B alike (the k labelling inside an MFMA is
-// arbitrary as long as A and B agree).  No LDS, no barriers: each wave free-runs over its n range with a
-// ring of WG_STAGES chunk loads in flight (an LDS-tiled version of this kernel was load-latency bound at
-// 2x the time: 12 exposed global-load round trips per workgroup, two barriers each).
-// Wave tile 32(co) x 64(ci); workgroup = 2x2 waves = 64 x 128; grid.z = batch x n-split.
-constexpr int WG_STAGES = 4;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-struct WgStage {
-    f32x4 a[4];   // 16 gz values of this lane's row
-    u32x4 c[2];   // 16 codes for each of the two 32-column tiles
-};
-// The ring is hand-scheduled: the compiler sinks plain loads next to their first use (draining the ring to
+// Load rings are hand-scheduled: the compiler sinks plain loads next to their first use (draining the ring to
 // vmcnt(0) every chunk), so the loads are issued through asm and retired with an explicit s_waitcnt that
 // carries the stage's registers as in/out operands (every use of the data is ordered after the wait).
 __device__ __forceinline__ void wg_load16(f32x4& d, const void* p) {
@@ -618,129 +602,9 @@ __device__ __forceinline__ void wg_load16(f32x4& d, const void* p) {
 __device__ __forceinline__ void wg_load16(u32x4& d, const void* p) {
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
 }
-template <int N>
-__device__ __forceinline__ void wg_wait(WgStage& st) {
-    asm volatile("s_waitcnt vmcnt(%6)"
-                 : "+v"(st.a[0]), "+v"(st.a[1]), "+v"(st.a[2]), "+v"(st.a[3]), "+v"(st.c[0]), "+v"(st.c[1])
-                 : "n"(N)
-                 : "memory");
-}
-
-__global__ __launch_bounds__(256, 2) void k_qwgrad(QGemmArgs g) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform on purpose: everything derived from it stays in SGPRs
-    const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
-    // group = one (batch, n-slice): its tiles_m x tiles_n workgroups share the gz rows / code rows of that slice
-    int slice, t;
-    if (!xcd_tile(g.batches * g.ksplit, g.tiles_m * g.tiles_n, slice, t)) return;
-    const int b = slice / g.ksplit, ks_id = slice % g.ksplit;
-    const int kbeg = ks_id * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-    const int row0 = (t / g.tiles_n) * 64 + wr * 32, col0 = (t % g.tiles_n) * 128 + wc * 64;
-    const int nchunks = (kend - kbeg + 31) >> 5;
-
-    const bool arow_ok = row0 + lr < g.M;
-    const int arow = arow_ok ? row0 + lr : 0;
-    const float* Ap = (arow < g.M1) ? (const float*)g.A + (int64_t)b * g.sAb + (int64_t)arow * g.lda
-                                    : (const float*)g.A2 + (int64_t)b * g.sA2b + (int64_t)(arow - g.M1) * g.lda2;
-    const unsigned char* Bb = (const unsigned char*)g.B + (int64_t)b * g.sBb;
-    const unsigned char* Bp[2] = {Bb + (int64_t)min(col0 + lr, g.N - 1) * g.ldb, Bb + (int64_t)min(col0 + 32 + lr, g.N - 1) * g.ldb};
-
-    // Loads are unconditional: addresses are clamped into the row, values masked at use.
-    const int ka_last = (kend - 1) & ~3, kb_last = (kend - 1) & ~15;
-    auto load = [&](WgStage& st, int chunk) {
-        const int k = kbeg + chunk * 32 + 16 * lh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wg_load16(st.a[q], Ap + min(k + 4 * q, ka_last));
-#pragma unroll
-        for (int t = 0; t < 2; ++t) wg_load16(st.c[t], Bp[t] + min(k, kb_last));
-    };
-
-    f32x16 acc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    float rowsum = 0.0f;
-
-    auto compute = [&](WgStage& st, int chunk) {
-        float x[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[4 * q + e] = st.a[q][e];
-        // positions >= kend (row padding, clamped re-reads) and rows >= Co contribute exact zeros; codes need no
-        // mask (finite, and they only ever meet a zero)
-        const int nvalid = arow_ok ? kend - (kbeg + chunk * 32 + 16 * lh) : 0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) x[e] = (e < nvalid) ? x[e] : 0.0f;
-        // exact 3-way split, packed as bf16 pairs with v_perm (high halves of two fp32 words)
-        union { uint32_t u[8]; bf16x8 v[2]; } A1, A2, A3;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float a0 = x[2 * e], a1 = x[2 * e + 1];
-            rowsum += a0 + a1;
-            const float r0 = a0 - bf_trunc(a0), r1 = a1 - bf_trunc(a1);
-            const float s0 = r0 - bf_trunc(r0), s1 = r1 - bf_trunc(r1);
-            A1.u[e] = __builtin_amdgcn_perm(__float_as_uint(a1), __float_as_uint(a0), 0x07060302u);
-            A2.u[e] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
-            A3.u[e] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const uint32_t w[4] = {st.c[t][0], st.c[t][1], st.c[t][2], st.c[t][3]};
-            union { uint32_t u[8]; bf16x8 v[2]; } Bc;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float f0 = (float)(w[q] & 0xFFu), f1 = (float)((w[q] >> 8) & 0xFFu);
-                const float f2 = (float)((w[q] >> 16) & 0xFFu), f3 = (float)(w[q] >> 24);
-                Bc.u[2 * q] = __builtin_amdgcn_perm(__float_as_uint(f1), __float_as_uint(f0), 0x07060302u);
-                Bc.u[2 * q + 1] = __builtin_amdgcn_perm(__float_as_uint(f3), __float_as_uint(f2), 0x07060302u);
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {   // smallest pieces first
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A3.v[s], Bc.v[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2.v[s], Bc.v[s], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1.v[s], Bc.v[s], acc[t], 0, 0, 0);
-            }
-        }
-    };
-
-    WgStage st[WG_STAGES];
-#pragma unroll
-    for (int s = 0; s < WG_STAGES - 1; ++s) load(st[s], s);
-    for (int c0 = 0; c0 < nchunks; c0 += WG_STAGES) {
-#pragma unroll
-        for (int s = 0; s < WG_STAGES; ++s) {
-            load(st[(s + WG_STAGES - 1) % WG_STAGES], c0 + s + WG_STAGES - 1);   // 4 stages x 6 loads in flight ...
-            wg_wait<6 * (WG_STAGES - 1)>(st[s]);                                 // ... the oldest stage has landed
-            compute(st[s], c0 + s);   // chunks past the end are fully masked: the body stays branch-free
-        }
-    }
-
-    // the ring's trailing (clamped, unused) loads still target the stage registers, which the compiler
-    // considers dead from here on: drain them before anything else may be allocated there
-#pragma unroll
-    for (int s = 0; s < WG_STAGES; ++s) wg_wait<0>(st[s]);   // in/out operands keep every stage register reserved up to here
-
-    // epilogue: the gz row sums (min_x term) live in lane == row; results are atomically added (n-split, batch)
-    const float lo = *g.qmin_x, hi = *g.qmax_x;
-    const float dx = (hi - lo) / 255.0f, mnx = lo;
-    const float rtot = rowsum + __shfl_xor(rowsum, 32, 64);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int rl = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const float rsum = __shfl(rtot, rl, 64);
-        const int row = row0 + rl;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int col = col0 + 32 * t + lr;
-            if (row < g.M && col < g.N) grad_add(&g.C[(int64_t)row * g.ldc + col], dx * acc[t][r] + mnx * rsum);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------
-// wgrad, LDS-tiled (round 2): the register-direct kernel above is VALU-issue bound (PMC: 47 % of wave time issuing, 39 % stalled
+// wgrad, LDS-tiled (round 2): the round-1 register-direct kernel (each lane loading its MFMA fragments straight from HBM) was VALU-issue bound (PMC: 47 % of wave time issuing, 39 % stalled
 // on issue; ~5 cycles per wave instruction and SIMD): every wave splits its own gz fragment and converts its own code fragments,
 // so inside a 2 x 2 workgroup each gz value is split twice and each code converted twice.  Here the workgroup converts a
 // 64 (co) x 128 (ci) x 64 (n) stage ONCE -- coalesced 16-B global loads (full 256-B / 64-B row pieces), exact 3-way bf16 split /
@@ -1373,11 +1237,6 @@ static int qpw_bwd_x_impl(const char* who, const float* gz1, const float* gz2, c
         FQSS_REQUIRE(aligned16(addend) && ld_add % 4 == 0 && ld_add >= ((M + 3) & ~3), "addend rows must be 16-B aligned and padded to 4");
         g.C2 = const_cast<float*>(addend); g.ldc2 = ld_add; g.sC2b = (int64_t)Ci * ld_add;
     }
-#ifdef FQSS_EXPERIMENTS
-    // round 4 experiment (csrc/experiments/qgemm_ring.hip; `make experiments`, FQSS_DGRAD_RING=1): the ring form, measured slower
-    if (grad_pieces() == 3 && qdgrad_ring_ok(Ci, Co1, Co2) && (!addend || ld_add < (1ll << 26)))
-        return qdgrad_ring(who, gz1, gz2, wiT, dw, addend, gx, B, Ci, Co1, Co2, M, ld_gz1, ld_gz2, ld_add, ld_gx, stream);
-#endif
     g.tiles_n = (int)cdiv(M, QBN); g.tiles_m = (int)cdiv(Ci, QBM); g.batches = B;
     if (grad_pieces() == 3)
         hipLaunchKernelGGL((k_qgemm<1, 3>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
@@ -1422,26 +1281,18 @@ static int qpw_bwd_w_impl(const char* who, const float* gz1, const float* gz2, c
     g.sAb = (int64_t)Co1 * ld_gz1; g.sBb = (int64_t)Ci * ld_xc; g.sCb = 0;
     g.M1 = Co1; g.A2 = gz2; g.lda2 = ld_gz2; g.sA2b = (int64_t)Co2 * ld_gz2; g.K1 = M;
     g.qmin_x = qmin_x; g.qmax_x = qmax_x;
-    // one workgroup = 64 (co) x 128 (ci); split n so that ~FQSS_WGRAD_BLOCKS workgroups stream the operands
+    // one workgroup = 64 (co) x 128 (ci); split n so that ~WGRAD_BLOCKS workgroups stream the operands
     const int64_t tiles = cdiv(Co, 64) * cdiv(Ci, 128) * B;
-    int want = (int)((FQSS_WGRAD_BLOCKS + tiles / 2) / tiles);
+    int want = (int)((WGRAD_BLOCKS + tiles / 2) / tiles);
     if (want < 1) want = 1;
     g.tiles_n = (int)cdiv(Ci, 128); g.tiles_m = (int)cdiv(Co, 64); g.batches = B;
-    static const bool reg_direct = getenv("FQSS_WGRAD_REGDIRECT") != nullptr;   // the round-1 kernel, kept for A/B measurements
-    if (reg_direct) {
-        int kchunk = (int)cdiv(cdiv(M, want), 32 * WG_STAGES) * 32 * WG_STAGES;   // whole rounds of the load ring
-        g.kchunk = kchunk;
-        g.ksplit = (int)cdiv(M, kchunk);
-        hipLaunchKernelGGL(k_qwgrad, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(256), 0, (hipStream_t)stream, g);
-    } else {
-        int kchunk = (int)cdiv(cdiv(M, want), W2_RING * W2_TK) * W2_RING * W2_TK;   // whole rounds of the stage ring
-        g.kchunk = kchunk;
-        g.ksplit = (int)cdiv(M, kchunk);
-        if (grad_pieces() == 3)
-            hipLaunchKernelGGL(k_qwgrad2<3>, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(512), 0, (hipStream_t)stream, g);
-        else
-            hipLaunchKernelGGL(k_qwgrad2<2>, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(512), 0, (hipStream_t)stream, g);
-    }
+    const int kchunk = (int)cdiv(cdiv(M, want), W2_RING * W2_TK) * W2_RING * W2_TK;   // whole rounds of the stage ring
+    g.kchunk = kchunk;
+    g.ksplit = (int)cdiv(M, kchunk);
+    if (grad_pieces() == 3)
+        hipLaunchKernelGGL(k_qwgrad2<3>, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(512), 0, (hipStream_t)stream, g);
+    else
+        hipLaunchKernelGGL(k_qwgrad2<2>, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(512), 0, (hipStream_t)stream, g);
     return launch_status(who);
 }
 

@@ -211,11 +211,8 @@ static int check_fft(int N, int hop, int* logn) {
 
 using namespace fqss;
 
-// threads per frame and whether the twiddles are staged in LDS (A/B knobs FQSS_FFT_THREADS / FQSS_FFT_TW_LDS; see k-comments)
-static int fft_threads() {
-    static const int v = [] { const char* e = getenv("FQSS_FFT_THREADS"); const int t = e ? atoi(e) : 512; return (t == 256 || t == 1024) ? t : 512; }();
-    return v;
-}
+constexpr int kFftThreads = 512;     // threads per frame
+// whether the twiddles are staged in LDS (A/B knob FQSS_FFT_TW_LDS, see fft_lds)
 static int fft_tw_lds() {
     static const int v = [] { const char* e = getenv("FQSS_FFT_TW_LDS"); return e ? atoi(e) : 0; }();
     return v;
@@ -231,7 +228,7 @@ extern "C" int fqss_stft(const float* x, float* z, const float* win, const float
     FQSS_REQUIRE(rows > 0 && rows <= 65535 && T > 0 && L > 1 && ld_x >= L, "bad shape");
     const int64_t last = (int64_t)(T - 1) * hop + N - 1 - pad;       // right-most sample index touched
     FQSS_REQUIRE(pad >= 0 && pad < L && last - (L - 1) < L, "reflect padding longer than the signal");
-    hipLaunchKernelGGL(k_stft, dim3((unsigned)T, (unsigned)rows), dim3(fft_threads()), fft_lds_bytes(N), (hipStream_t)stream, x, z, win,
+    hipLaunchKernelGGL(k_stft, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, x, z, win,
                        reinterpret_cast<const float2*>(tw), N, logn, hop, T, pad, L, ld_x, fft_tw_lds());
     return launch_status("fqss_stft");
 }
@@ -243,7 +240,7 @@ extern "C" int fqss_istft(const float* z, float* frames, float* y, const float* 
     int logn;
     if (int rc = check_fft(N, hop, &logn)) return rc;
     FQSS_REQUIRE(rows > 0 && rows <= 65535 && T > 0 && length > 0 && ld_y >= length && pad >= 0, "bad shape");
-    hipLaunchKernelGGL(k_istft_frames, dim3((unsigned)T, (unsigned)rows), dim3(fft_threads()), fft_lds_bytes(N), (hipStream_t)stream, z, frames, win,
+    hipLaunchKernelGGL(k_istft_frames, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, z, frames, win,
                        reinterpret_cast<const float2*>(tw), N, logn, T, fft_tw_lds());
     int64_t gx = cdiv(length, 1024);
     if (gx > 1024) gx = 1024;
@@ -258,7 +255,7 @@ extern "C" int fqss_istft_bwd(const float* g, float* gz, const float* win, const
     int logn;
     if (int rc = check_fft(N, hop, &logn)) return rc;
     FQSS_REQUIRE(rows > 0 && rows <= 65535 && T > 0 && length > 0 && ld_g >= length && pad >= 0, "bad shape");
-    hipLaunchKernelGGL(k_istft_bwd, dim3((unsigned)T, (unsigned)rows), dim3(fft_threads()), fft_lds_bytes(N), (hipStream_t)stream, g, gz, win, env,
+    hipLaunchKernelGGL(k_istft_bwd, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, g, gz, win, env,
                        reinterpret_cast<const float2*>(tw), N, logn, hop, T, pad, length, ld_g, fft_tw_lds());
     return launch_status("fqss_istft_bwd");
 }

@@ -92,12 +92,6 @@ __global__ __launch_bounds__(256) void k_split3_tiles(const float* __restrict__ 
     }
 }
 
-// FQSS_TDIAG (diagnostic builds only, tools/r03_bisect.sh; default 0 = the product): bit 0 no MFMAs | 1 plain ds_read_b64 instead of the
-// transposed reads | 2 no LDS stores of the staged tiles | 3 no global loads in the main loop | 4 no epilogue (results are then garbage:
-// these builds only serve as the AGGRESSOR of tools/ubench/pkadd_next_to_mfma.hip)
-#ifndef FQSS_TDIAG
-#define FQSS_TDIAG 0
-#endif
 typedef float f32x4t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4t __attribute__((ext_vector_type(4)));
 struct TStage {          // one k-tile of global loads per thread: 3 planes x 2 x 16 B of the weight, 4 x 16 B of activations
@@ -137,7 +131,6 @@ struct TGemmArgs {
     float* C1; const float* R1; int64_t ldc1, sC1b;
     float* C2; const float* R2; int64_t ldc2, sC2b;
     int tiles_m, tiles_n, batches;   // logical grid (launched 1-D in XCD-aware order, fqss_dev.h)
-    int stagger;                     // k_tgemm2: cycles by which every second workgroup starts late (0: none; see its header)
 };
 
 template <int PRO>   // prologue on the activation rows: 0 none | 1 GroupNorm affine | 2 PReLU
@@ -202,7 +195,6 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
     const int a_row_c = min(i0 + a_row, g.M - 1);
     const int n_last = (g.N - 1) & ~3;
     auto load_tiles = [&](TStage& st, int k0) {
-        if (FQSS_TDIAG & 8) return;
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -214,7 +206,6 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
     };
     auto store_tiles = [&](TStage& st, int k0) {
         t_wait<10>(st);   // this stage has landed; the 10 younger requests of the other stage stay in flight
-        if (FQSS_TDIAG & 4) return;
         const int kc = min(k0 + bk_row, g.K - 1);
         const float p_a = (PRO == 1) ? pco[0][kc] : 1.f, p_b = (PRO == 1) ? pco[1][kc] : 0.f;
 #pragma unroll
@@ -264,13 +255,8 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
                     const int kr = ks * 16 + 8 * (gq >> 1) + tq;
                     const int nc = wn * 64 + ni * 32 + 16 * (gq & 1) + 4 * tp;
                     union { bf16x8 v; s16x4 h[2]; } u;
-                    if (FQSS_TDIAG & 2) {
-                        u.h[0] = *reinterpret_cast<const s16x4*>(&Bs[p][kr][nc]);
-                        u.h[1] = *reinterpret_cast<const s16x4*>(&Bs[p][kr + 4][nc]);
-                    } else {
-                        u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
-                        u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
-                    }
+                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
+                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
                     bfr[p][ni] = u.v;
                 }
             }
@@ -283,8 +269,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                     for (int ni = 0; ni < 2; ++ni)
-                        if (!(FQSS_TDIAG & 1)) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[IA[sp]][mi], bfr[IB[sp]][ni], acc[mi][ni], 0, 0, 0);
-                        else acc[mi][ni][sp] += (float)af[IA[sp]][mi][0] + (float)bfr[IB[sp]][ni][0];      // keeps the fragment reads alive
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[IA[sp]][mi], bfr[IB[sp]][ni], acc[mi][ni], 0, 0, 0);
         }
     };
 
@@ -317,10 +302,6 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
     // from here on: drain them before anything else is allocated there
     t_wait<0>(stA);
     t_wait<0>(stB);
-    if (FQSS_TDIAG & 16) {      // no epilogue: one store keeps the accumulators alive
-        if (acc[0][0][0] + acc[0][1][1] + acc[1][0][2] + acc[1][1][3] == 12345.678f) g.C1[0] = 1.0f;
-        return;
-    }
     // (every wave has passed the barrier behind the last tile's fragment reads: the tile buffer is free)
     if (tid < TBM) rowb[tid] = (g.bias != nullptr && i0 + tid < g.M) ? g.bias[i0 + tid] : 0.0f;
     __syncthreads();
@@ -429,11 +410,6 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
 //     next row tile while the compute waves store the previous one's results.
 // LDS: 163,840 B (everything the CU has): 4 x (24,576 + 15,360) + 4,096 (GroupNorm coefficients | bias); the epilogue's staging
 // tiles live in slot 3 (the slot of the row tile's LAST k-tile).  One workgroup per CU, grid = panels (256 at the benchmark's size).
-#ifndef FQSS_T2_ABL
-#define FQSS_T2_ABL 0
-#endif
-// FQSS_T2_ABL (timing experiments only, tools/r04_abl.sh; default 0 = the product; results are garbage otherwise): bit 0 no MFMAs |
-// 1 no fragment reads | 2 no split / LDS store of the activations | 3 no weight DMA | 4 no activation loads | 5 no result stores
 constexpr int T2BM = 256, T2BN = 128, T2BK = 16;
 constexpr int T2_A_SLOT = 3 * T2BM * T2BK * 2;            // 24,576: [plane][256 rows][16 k] bf16, 32-B rows, swizzled chunks
 constexpr int T2_B_SLOT = 3 * T2BK * TLDN * 2;            // 15,360: [plane][16 k][128 + 32 pad] bf16 (the row layout of k_tgemm)
@@ -470,23 +446,8 @@ __device__ __forceinline__ void t2_unroll(F& f) {      // f(integral_constant<T>
     }
 }
 
-// every barrier of k_tgemm2 goes through T2_SYNC(<s_waitcnt in front of it, or "">).  FQSS_T2_STAMP (diagnostic builds, tools/t2_stamps.py):
-// workgroup 0 records, per wave and barrier, the cycle counter before the wait, before the barrier and behind it.
-#ifdef FQSS_T2_STAMP
-__device__ unsigned long long g_t2_stamp[8][160][3];
-#define T2_SYNC(W)                                                                                       \
-    do {                                                                                                 \
-        const bool st_on = blockIdx.x == 0 && lane == 0 && sidx < 160;                                   \
-        if (st_on) g_t2_stamp[wave][sidx][0] = __builtin_amdgcn_s_memtime();                             \
-        asm volatile(W ::: "memory");                                                                    \
-        if (st_on) g_t2_stamp[wave][sidx][1] = __builtin_amdgcn_s_memtime();                             \
-        asm volatile("s_barrier" ::: "memory");                                                          \
-        if (st_on) g_t2_stamp[wave][sidx][2] = __builtin_amdgcn_s_memtime();                             \
-        ++sidx;                                                                                          \
-    } while (0)
-#else
+// every barrier of k_tgemm2 goes through T2_SYNC(<s_waitcnt in front of it, or "">)
 #define T2_SYNC(W) asm volatile(W "\n\ts_barrier" ::: "memory")
-#endif
 
 template <int PRO>
 __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
@@ -500,16 +461,6 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int panel = blockIdx.x;
     const int b = panel / g.tiles_n, j0 = (panel % g.tiles_n) * T2BN;
-    // Phase stagger (round 5): the 256 workgroups (one per CU) run in lockstep -- k-loop (matrix pipes busy, HBM nearly idle), then the
-    // epilogue (every workgroup storing its 128 KB tile at once: HBM-write bound, matrix pipes dark; 44 % of T1 by its barrier stamps).
-    // Starting every second workgroup late by roughly half an epilogue puts one half's stores under the other half's MFMAs.
-    if (g.stagger > 0 && (panel & 1)) {
-        const unsigned long long t0 = __builtin_readcyclecounter();
-        while (__builtin_readcyclecounter() - t0 < (unsigned long long)g.stagger) __builtin_amdgcn_s_sleep(16);
-    }
-#ifdef FQSS_T2_STAMP
-    int sidx = 0;
-#endif
 
     if (PRO == 1) {
         t_stats_finalize(g.pro_stats + (int64_t)b * kTSlots * kTSlotStride, g.pro_count, g.pro_eps, pms);
@@ -540,11 +491,7 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
         // stay in flight) in front of the barrier that publishes it.
         const int dw = wave - 6;
         const unsigned voff = lane * 16;
-#ifdef FQSS_T2_MPRIO
-        __builtin_amdgcn_s_setprio(FQSS_T2_MPRIO);
-#endif
         auto dma_tile = [&](int64_t tile) {                   // tile = row tile * nkt + k-tile -> slot k-tile & 3
-            if (FQSS_T2_ABL & 8) return;
             const unsigned char* src = reinterpret_cast<const unsigned char*>(g.A) + tile * (3 * 4096 * 2) + dw * (12 * 1024);
             const unsigned dst = lds_base + (unsigned)(tile & 3) * T2_A_SLOT + dw * (12 * 1024);      // nkt % 4 == 0: tile & 3 == k-tile & 3
 #pragma unroll
@@ -569,9 +516,6 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
         // from HBM (microseconds under load) and a tile is 8 KB per workgroup, so SIX tiles are kept in flight in a register ring
         // (48 KB per CU; with one or two 16-KB tiles in flight the memory skeleton alone ran at 9 GB/s per CU).
         const int lt = tid - 256;
-#ifdef FQSS_T2_MPRIO
-        __builtin_amdgcn_s_setprio(FQSS_T2_MPRIO);
-#endif
         float pslope = (PRO == 2) ? *g.pro_slope : 0.0f;
         if (PRO == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pslope));
         // thread -> k-rows (lt >> 5) + 4 q (q < 4), columns 4 (lt & 31) .. + 4: a wave instruction reads two whole 512-B row segments
@@ -582,12 +526,10 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
         const int64_t bstep = (int64_t)T2BK * g.ldb, brow4 = 4 * g.ldb;
         struct LStage { f32x4t rb[4]; };
         auto load_b = [&](LStage& st, int t) {
-            if (FQSS_T2_ABL & 16) return;
 #pragma unroll
             for (int q = 0; q < 4; ++q) t_load16s(st.rb[q], bbase + t * bstep + q * brow4, bvoff);
         };
         auto store_b = [&](LStage& st, int t) {
-            if (FQSS_T2_ABL & 4) return;
             unsigned char* bs = smem2 + T2_B_OFF + (t & 3) * T2_B_SLOT + (bk_row * TLDN + bk_c) * 2;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -655,9 +597,6 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
         const int gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
         const float nscale = (g.act == FQSS_ACT_PRELU) ? *g.slope : (g.act == FQSS_ACT_RELU ? 0.0f : 1.0f);
         const bool has_bias = g.bias != nullptr;
-#ifdef FQSS_T2_PRIO
-        __builtin_amdgcn_s_setprio(FQSS_T2_PRIO);
-#endif
         f32x16 acc[4][2];
         // fragments of one k-tile: the three planes of the wave's 64 columns (B, 6 fragments) and of 64 of its 128 rows (A, 6 fragments
         // per half): 24 MFMAs per half.  12 + 6 fragments of the NEXT tile are requested before the barrier that ends the current one
@@ -673,7 +612,6 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
                     const int kr = 8 * (gq >> 1) + tq;
                     const int nc = wn * 64 + ni * 32 + 16 * (gq & 1) + 4 * tp;
                     union { bf16x8 v; s16x4 h[2]; } u;
-                    if (FQSS_T2_ABL & 2) { bfr[p][ni] = bf16x8{}; asm volatile("" : "+v"(bfr[p][ni])); continue; }
                     u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
                     u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
                     bfr[p][ni] = u.v;
@@ -686,7 +624,6 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi) {
                     const int row = wm * 128 + (2 * mh + mi) * 32 + lr;
-                    if (FQSS_T2_ABL & 2) { af[p][mi] = bf16x8{}; asm volatile("" : "+v"(af[p][mi])); continue; }
                     af[p][mi] = *reinterpret_cast<const bf16x8*>(as + p * (T2BM * T2BK * 2) + row * 32 + ((lh ^ ((row >> 3) & 1)) << 4));
                 }
         };
@@ -699,9 +636,7 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                     for (int ni = 0; ni < 2; ++ni)
-                        if (!(FQSS_T2_ABL & 1))
-                            acc[2 * mh + mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[IA[sp]][mi], bfr[IB[sp]][ni], acc[2 * mh + mi][ni], 0, 0, 0);
-                        else asm volatile("" : "+v"(acc[2 * mh + mi][ni]) : "v"(af[IA[sp]][mi]), "v"(bfr[IB[sp]][ni]));
+                        acc[2 * mh + mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[IA[sp]][mi], bfr[IB[sp]][ni], acc[2 * mh + mi][ni], 0, 0, 0);
         };
         using H0 = std::integral_constant<int, 0>;
         using H1 = std::integral_constant<int, 1>;
@@ -799,8 +734,7 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
                             t.x += q.x; t.y += q.y; t.z += q.z; t.w += q.w;
                         }
                         if (col < g.N) {
-                            if (!(FQSS_T2_ABL & 32)) store16(Cb + (int64_t)rl * ldc + col, t);
-                            else asm volatile("" : : "v"(t.x), "v"(t.y), "v"(t.z), "v"(t.w));
+                            store16(Cb + (int64_t)rl * ldc + col, t);
                             if (want_stats) {
                                 const float v[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
@@ -842,11 +776,6 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
 // row blocks of a column group sit on one XCD (xcd_tile), so an activation tile comes from HBM once.  Same six exact partial
 // products, smallest first, as k_tgemm / k_tgemm2; the accumulation runs over k in the same order.
 // ---------------------------------------------------------------------------------------------------------------------------
-// FQSS_K1_ABL (timing experiments only: make variant SRC=teacher NAME=.. DEFS=-DFQSS_K1_ABL=n, tools/r05_t1_probe.py; never the product):
-// 1 no MFMAs | 2 no split / LDS stores of the activation tile | 4 no result stores | 8 no activation loads | 16 no LDS fragment reads
-#ifndef FQSS_K1_ABL
-#define FQSS_K1_ABL 0
-#endif
 constexpr int K1_BN = 64, K1_LDN = 72, K1_ROWS = 128;
 struct K1X { f32x4t v[8]; };
 __device__ __forceinline__ void k1_wait(K1X& x) {
@@ -885,7 +814,6 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
     auto load_x = [&](int ct) {
         const int b = ct / tiles_n64, j0 = (ct - b * tiles_n64) * K1_BN;
         const float* Bb = g.B + (int64_t)b * g.sBb + min(j0 + xc, n_last);
-        if (FQSS_K1_ABL & 8) return;
 #pragma unroll
         for (int q = 0; q < 8; ++q) t_load16(xr.v[q], Bb + (int64_t)(q * 16 + xk) * g.ldb);
     };
@@ -904,12 +832,6 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
     };
     int ct = group;
     if (ct < ntiles) load_x(ct);
-    if (g.stagger > 0 && ((g.stagger & 1) ? ((blockIdx.x >> 3) & 1) : (blockIdx.x >= gridDim.x / 2))) {
-        // experiment knob (FQSS_T1_STAGGER=<cycles>; odd: every second workgroup of an XCD, even: the second half of the grid): start late,
-        // so that the two workgroups of a CU are in opposite phases (one's memory side under the other's MFMAs)
-        const long long t0 = __builtin_readcyclecounter();
-        while (__builtin_readcyclecounter() - t0 < g.stagger) __builtin_amdgcn_s_sleep(8);
-    }
     for (; ct < ntiles; ct += ngroups) {
         const int b = ct / tiles_n64, j0 = (ct - b * tiles_n64) * K1_BN;
         if (b != sb) {
@@ -920,7 +842,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
         // previous tile's fragment reads)
         k1_wait(xr);
 #pragma unroll
-        for (int q = 0; q < ((FQSS_K1_ABL & 2) ? 0 : 8); ++q) {
+        for (int q = 0; q < 8; ++q) {
             const float x[4] = {xr.v[q][0], xr.v[q][1], xr.v[q][2], xr.v[q][3]};
             float r1[4], r2[4];
 #pragma unroll
@@ -948,7 +870,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ni][r] = 0.0f;
         // (the fragments of step ks + 1 are requested before the MFMAs of step ks: with two waves per SIMD the LDS round trip was not
-        //  hidden otherwise -- ablation, tools/r05_t1_probe.py: 36 us per launch, 26 with the fragment reads removed)
+        //  hidden otherwise -- ablation: 36 us per launch, 26 with the fragment reads removed)
         // Two fragment buffers of one 32-column tile and one k-step each (3 planes x 4 registers): while the six MFMAs of one run, the
         // fragments of the next are on their way -- 24 registers, what the un-pipelined form held for both column tiles of a step (the
         // kernel sits at the 256-register limit of two waves per SIMD, and a spill next to the asm loads in flight is not an option).
@@ -958,12 +880,8 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
                 const int kr = ks * 16 + 8 * (gq >> 1) + tq;
                 const int nc = ni * 32 + 16 * (gq & 1) + 4 * tp;
                 union { bf16x8 v; s16x4 h[2]; } u;
-                if (FQSS_K1_ABL & 16) {
-                    u.v = wf[ks][p];
-                } else {
-                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
-                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
-                }
+                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
+                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
                 bfr[p] = u.v;
             }
         };
@@ -971,8 +889,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
             constexpr int IA[6] = {2, 0, 1, 1, 0, 0}, IB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
             for (int sp = 0; sp < 6; ++sp) {
-                if (!(FQSS_K1_ABL & 1)) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks][IA[sp]], bfr[IB[sp]], acc[ni], 0, 0, 0);
-                else acc[ni][sp] += (float)wf[ks][IA[sp]][0] + (float)bfr[IB[sp]][0];
+                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks][IA[sp]], bfr[IB[sp]], acc[ni], 0, 0, 0);
             }
         };
         bf16x8 fr[2][3];
@@ -999,7 +916,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
                 const int rl = pass * 8 + (lane >> 3);
                 const float4 t = *reinterpret_cast<const float4*>(&Tt[rl][c4]);
                 if (col < g.N) {
-                    if (!(FQSS_K1_ABL & 4)) store16(Cb + (int64_t)rl * g.ldc1 + col, t);
+                    store16(Cb + (int64_t)rl * g.ldc1 + col, t);
                     const float v[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -1193,25 +1110,19 @@ static int tgemm_launch(bool tiled, const char* fn, const uint16_t* planes, cons
             return ok;
         }();
         TG_REQUIRE(attr_ok, "k_tgemm2 needs 160 KB of dynamic LDS");
-        static const bool k128 = [] { const char* e = getenv("FQSS_T1_K128"); return !(e && e[0] == '0'); }();
-        if (k128 && pro == 0 && Ci == 128 && Co % K1_ROWS == 0 && M1 == Co && r1 == nullptr && r2 == nullptr && (stats_out == nullptr || B <= 64)) {
+        if (pro == 0 && Ci == 128 && Co % K1_ROWS == 0 && M1 == Co && r1 == nullptr && r2 == nullptr && (stats_out == nullptr || B <= 64)) {
             // T1 of the TCN teacher: weights in registers, two workgroups per CU (k_tgemm_k128)
             const int tiles_n64 = (int)cdiv(M, K1_BN), ntiles = tiles_n64 * B;
             // 64 column groups x 4 row blocks = 256 workgroups = ONE per CU although two fit: alone on the chip the launch is slower
-            // that way (45 us against 36 at 128 groups), but the step is faster (13.00 against 13.07 ms, FQSS_T1_GROUPS=64 / 128 interleaved
+            // that way (45 us against 36 at 128 groups), but the step is faster (13.00 against 13.07 ms, 64 / 128 groups interleaved
             // on one box; 48: 13.00, 32: 13.08, 16: 13.05, 192: 13.11) -- the teacher runs one batch ahead on its own stream with 10 ms
             // of slack, and what it should leave free is the second workgroup slot of every CU for the student's kernels
-            static const int want_groups = [] { const char* e = getenv("FQSS_T1_GROUPS"); const int v = e ? atoi(e) : 64; return v >= 8 ? v / 8 * 8 : 64; }();
-            int ngroups = want_groups;
+            int ngroups = 64;
             while (ngroups > 8 && ngroups * 2 > ntiles) ngroups >>= 1;
-            static const int t1_stagger = [] { const char* e = getenv("FQSS_T1_STAGGER"); return e ? atoi(e) : 0; }();
-            g.stagger = t1_stagger;
             hipLaunchKernelGGL(k_tgemm_k128, dim3(xcd_grid(ngroups, Co / K1_ROWS)), dim3(256), 0, (hipStream_t)stream, g, ngroups, tiles_n64);
             return launch_status(fn);
         }
         g.tiles_m = Co / T2BM;
-        static const int stagger = [] { const char* e = getenv("FQSS_T2_STAGGER"); return e ? atoi(e) : 0; }();
-        g.stagger = stagger;
         const dim3 grid2((unsigned)(g.tiles_n * B));
         if (pro == 0) hipLaunchKernelGGL(k_tgemm2<0>, grid2, dim3(512), T2_SMEM, (hipStream_t)stream, g);
         else if (pro == 1) hipLaunchKernelGGL(k_tgemm2<1>, grid2, dim3(512), T2_SMEM, (hipStream_t)stream, g);
@@ -1219,31 +1130,12 @@ static int tgemm_launch(bool tiled, const char* fn, const uint16_t* planes, cons
         return launch_status(fn);
     }
     const dim3 grid(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m));
-    // FQSS_TGEMM_PAD_LDS=<bytes> (experiment knob, read once): unused dynamic LDS that caps the workgroups per CU -- with > 16 KB on top
-    // of the 60-64 KB tile buffer only ONE teacher workgroup fits a CU, which leaves half of every SIMD's registers to the student's
-    // waves when the teacher runs on its own stream beside the step (docs/history/DESIGN_rounds_1-5.md 9)
-    static const size_t pad = [] {
-        const char* e = getenv("FQSS_TGEMM_PAD_LDS");
-        const size_t v = e ? (size_t)atol(e) : 0;
-        if (v) {
-            (void)hipFuncSetAttribute((const void*)k_tgemm<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v);
-            (void)hipFuncSetAttribute((const void*)k_tgemm<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v);
-            (void)hipFuncSetAttribute((const void*)k_tgemm<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v);
-        }
-        return v;
-    }();
-    if (pro == 0) hipLaunchKernelGGL(k_tgemm<0>, grid, dim3(256), pad, (hipStream_t)stream, g);
-    else if (pro == 1) hipLaunchKernelGGL(k_tgemm<1>, grid, dim3(256), pad, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(k_tgemm<2>, grid, dim3(256), pad, (hipStream_t)stream, g);
+    if (pro == 0) hipLaunchKernelGGL(k_tgemm<0>, grid, dim3(256), 0, (hipStream_t)stream, g);
+    else if (pro == 1) hipLaunchKernelGGL(k_tgemm<1>, grid, dim3(256), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL(k_tgemm<2>, grid, dim3(256), 0, (hipStream_t)stream, g);
     return launch_status(fn);
 #undef TG_REQUIRE
 }
-
-#ifdef FQSS_T2_STAMP
-extern "C" int fqss_debug_t2_stamps(unsigned long long* out) {      // host buffer [8][160][3]
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t2_stamp), sizeof(unsigned long long) * 8 * 160 * 3) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int fqss_tgemm_tiled_ok(int Ci, int Co, int M1) {
     return Co > 0 && Co % T2BM == 0 && Ci % (4 * TBK) == 0 && Ci >= 4 * TBK && Ci <= 512 && M1 > 0 && M1 % 32 == 0;

@@ -40,8 +40,8 @@ class HipSequential(nn.Sequential):
             # layer's backward needs to run the producer's epilogue backward on the fly (ops._Producer)
             nxt = next((n for n in mods[i + 1:] if not isinstance(n, nn.Identity)), None)
             QL.ops.NEXT_IS_GROUPNORM = isinstance(nxt, QL.GroupNormQ)
-            # a GroupNormQ whose one consumer is a 3-tap depthwise Conv1dNlQ (the TCN block's gLN -> depthwise conv): that layer's kernel
-            # runs the GroupNorm too (ops.GroupNormActQ leaves its launch record on the tensor; run_conv1d launches it if it cannot fuse)
+            # a GroupNormQ whose one consumer is a 3-tap depthwise Conv1dNlQ (the TCN block's gLN -> depthwise conv): the two backward
+            # passes hand work over between them (ops._GnHand)
             QL.ops.NEXT_IS_DW3 = isinstance(m, QL.GroupNormQ) and QL.is_depthwise3(nxt)
             # the owner of the sequence may vouch for its OUTPUT instead (fqss_sole_consumer: the mask network, whose output only
             # feeds the masking MulQ): the last layer then hands its producer record to that consumer

@@ -255,7 +255,6 @@ def run_conv1d(conv, x, weight, nl, aq, pad_to=None):
     if L.kind == "dw" and xq is not None and q.qmode == ops.Q_QUANT and conv.kernel_size[0] <= 8:
         y = ops.DwConvQ.apply(x, weight, conv.bias, slope, q.qmin, q.qmax, L, act, q, xq)
     else:
-        ops.flush_defer(x)
         if not (L.kind == "pw" and xq is not None and wc is not None):
             x = ops.real(x)             # no coded-input kernel for this case: decode a carrier first
         y = ops.LinearActQ.apply(x, weight, conv.bias, slope, q.qmin, q.qmax, L, act, q, xq, wc)

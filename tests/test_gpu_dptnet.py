@@ -222,12 +222,8 @@ def test_lstm_gate_functions():
     assert sg[0::2].tolist() == [1.0] * 4 and float(sg[1::2].max()) <= 2e-38 and float(sg[1::2].min()) >= 0.0
 
 
-@pytest.mark.parametrize("v1", ["0", "1"])
 @pytest.mark.parametrize("S,B,I,H", [(9, 5, 16, 12), (40, 7, 64, 128), (250, 3, 64, 128)])
-def test_lstm_kernels(S, B, I, H, v1, monkeypatch):
-    if v1 == "1" and H != 128:
-        pytest.skip("FQSS_LSTM_V1 only selects among the H = 128 forward kernels")
-    monkeypatch.setenv("FQSS_LSTM_V1", v1)
+def test_lstm_kernels(S, B, I, H):
     from fqss_amd import ops_dp
     names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l0_reverse", "weight_hh_l0_reverse",
              "bias_ih_l0_reverse", "bias_hh_l0_reverse")

@@ -1422,7 +1422,7 @@ def test_mha_prep_matches_the_unfused_quantizer_chain(L, B, E, nh):
 
 @pytest.mark.parametrize("Co,Ci,pro,act,split,B,M", [
     (256, 512, 1, 0, 128, 3, 300),      # T3 of the teacher chain: GroupNorm prologue, res | skip split, both residuals, ragged last tile
-    (512, 128, 0, 1, 512, 2, 391),      # T1: PReLU + GroupNorm statistics (k_tgemm_k128 since round 5; k_tgemm2<0> behind FQSS_T1_K128=0)
+    (512, 128, 0, 1, 512, 2, 391),      # T1: PReLU + GroupNorm statistics (k_tgemm_k128 since round 5)
     (1024, 128, 2, 2, 1024, 1, 130),    # mask conv: PReLU prologue, ReLU, four row tiles (k_tgemm2<2>: eight k-tiles of 16)
     (256, 64, 1, 0, 256, 2, 128),       # Ci = 64 < 128: not a shape of the tiled form -> k_tgemm, two 32-deep k-tiles (its peeled head and tail meet)
     (256, 256, 0, 1, 256, 2, 200),      # no prologue at Ci = 256: k_tgemm2<0> (Ci = 128 goes to k_tgemm_k128)
@@ -1576,44 +1576,6 @@ def test_depthwise_backward_takes_the_groupnorm_passes(B, C, M, dil, which):
         assert float(b.abs().max()) > 0
     for k in ("gbias", "gw"):
         assert float((F[k] - R[k]).abs().max()) <= 1e-5 * max(1e-6, float(R[k].abs().max())), k
-
-
-@pytest.mark.parametrize("B,C,M,dil", [(2, 24, 3999, 1), (1, 16, 3999, 128), (3, 8, 777, 4), (2, 600, 130, 2), (1, 4, 4096, 64)])
-def test_gn_dw_fused_bit_identical(B, C, M, dil):
-    """(EXPERIMENT, include/fqss_experiments.h: not in the product library -- runs when FQSS_LIB points at `make -C fqss_amd/csrc
-    experiments`' variants/libfqss_experiments.so, skipped otherwise.)  fqss_gndwq_fwd (round 5: on per-row code tables, k_gndwq_fwd_t;
-    the per-element form of round 4 is fqss_gndwq_fwd_v1): GroupNormQ + 3-tap depthwise Conv1dNlQ (PReLU), both quantizing, as ONE launch -- against the two
-    launches it replaces (fqss_gnq_fwd, fqss_dwq_fwd): the GroupNorm's output codes, its mean / rstd, the depthwise layer's output
-    codes and the integer statistics of those codes, bit for bit (dilations 1 .. 128: unaligned taps out of the LDS row, the
-    zero-padded row ends, rows shorter than a workgroup's 4096 positions, several rows per workgroup)."""
-    from fqss_amd import _lib
-    if not hasattr(_lib.load(), "fqss_gndwq_fwd"):
-        pytest.skip("fqss_gndwq_fwd is an experiment: build `make -C fqss_amd/csrc experiments` and set FQSS_LIB to run this gate")
-    dev = "cuda"
-    g = torch.Generator().manual_seed(B * 1000 + C + M + dil)
-    xc = K.empty_codes((B, C, M), dev)
-    xc.copy_(torch.randint(0, 256, (B, C, M), generator=g, dtype=torch.uint8).to(dev))
-    T1 = lambda v: torch.tensor([v], device=dev)
-    lo, hi, lo1, hi1, lo2, hi2 = T1(-1.7), T1(2.9), T1(-2.2), T1(2.4), T1(-0.6), T1(1.9)
-    gamma, beta = (1.0 + 0.3 * torch.randn(C, generator=g)).to(dev), (0.2 * torch.randn(C, generator=g)).to(dev)
-    w, bias = (torch.randn(C, 1, 3, generator=g) * 0.6).to(dev), (torch.randn(C, generator=g) * 0.1).to(dev)
-    slope = T1(0.2)
-    xi = xc.to(torch.int64)
-    st = K.CodeStats(torch.stack([xi.sum(dim=(1, 2)), (xi * xi).sum(dim=(1, 2))], 1).reshape(-1).contiguous(), 1)
-    _, yc1, mr = K.gnq_fwd(xc, lo, hi, gamma, beta, 1e-8, lo1, hi1, write_out=False, stats=st)
-    std = K.new_stats("dwq", B, C, M, dev)
-    _, yc2 = K.dwq_fwd(yc1, lo1, hi1, w, bias, dil, dil, K.ACT_PRELU, slope, lo2, hi2, write_out=False, stats=std)
-    _, y1, mr_f = K.gnq_fwd_deferred(xc)
-    d = dict(xc=xc, qmin_x=lo, qmax_x=hi, gamma=gamma, beta=beta, eps=1e-8, qmin=lo1, qmax=hi1, stats=st, yc=y1, mean_rstd=mr_f, done=False)
-    _, y2, st2 = K.gndwq_fwd(d, w, bias, dil, dil, K.ACT_PRELU, slope, lo2, hi2, True)
-    assert torch.equal(y1, yc1) and torch.equal(mr_f, mr)
-    assert torch.equal(y2, yc2)
-    if std is not None and st2 is not None:
-        a = std.ws.view(B, -1, 2).sum(1)
-        b = st2.ws.view(B, -1, 2).sum(1)
-        assert torch.equal(a, b)
-        yi = yc2.to(torch.int64)
-        assert torch.equal(b[:, 0], yi.sum(dim=(1, 2))) and torch.equal(b[:, 1], (yi * yi).sum(dim=(1, 2)))
 
 
 def test_unary_maps_read_a_column_block_in_place():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """times the streaming attention core at the cfg 5 shapes (and the dual-path shapes of cfg 3 / 4) in its forms: float operands on the bf16
-matrix cores (exact 3-piece split; FQSS_ATTN_MFMA=f32 in the environment: the fp32-MFMA kernels of rounds 1-2) and coded operands (GPU box)"""
+matrix cores (exact 3-piece split) and coded operands (GPU box)"""
 import sys, os
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

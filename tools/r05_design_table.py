@@ -43,7 +43,7 @@ setrow("| `k_tgemm", {}) if False else None
 for i, l in enumerate(lines):
     if l.startswith("| `k_tgemm2<0>` (24; round 4)") or l.startswith("| `k_tgemm_k128` (24; round 5)"):
         lines[i] = (f"| `k_tgemm_k128` (24; round 5) | teacher T1: 1×1 conv 128→512 + PReLU + GN statistics with the WEIGHTS IN REGISTERS (K = 128: 96 VGPRs per lane in A-fragment order), "
-                    f"64-column activation tiles split into 55 KB of LDS, 96 MFMAs per wave and tile, 74 KB of LDS = two workgroups per CU (`k_tgemm2<0>`, 41.5 us, behind `FQSS_T1_K128=0`) "
+                    f"64-column activation tiles split into 55 KB of LDS, 96 MFMAs per wave and tile, 74 KB of LDS = two workgroups per CU (`k_tgemm2<0>` took 41.5 us) "
                     f"| {mb(t1)} | {tm(t1)} | floor 10.2 us (bound: HBM; 10.1 us of MFMA issue): {K[t1]['frac']:.2f}; traffic {tr(t1)} |")
         break
 else:

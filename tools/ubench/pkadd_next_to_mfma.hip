@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void k_mfma_asm(float* out, int iters) {
     if (iters < 0) out[0] = 1.f;
 }
 
-// the skeleton of the teacher GEMM (its FQSS_TDIAG=30 build still triggers the effect): 128 x 128 x 32 tiles, 4 waves as 2 x 2, three bf16 planes
+// the skeleton of the teacher GEMM (with its global loads and epilogue removed it still triggered the effect): 128 x 128 x 32 tiles, 4 waves as 2 x 2, three bf16 planes
 // per operand in 60 KB of static LDS, per k-tile 2 x (12 fragment reads + 24 MFMAs) between workgroup barriers, FOUR k-tiles per workgroup
 __global__ __launch_bounds__(256, 2) void k_gemm_skel(float* out, int ktiles) {
     __shared__ __attribute__((aligned(16))) unsigned short As[3][128][40], Bs[3][32][160];
