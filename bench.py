@@ -8,15 +8,18 @@ phase is passed in an untimed calibration before the warm-up).  Inputs are resid
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
   python bench.py ... --dump-outputs DIR                  (also writes what the last timed step returned: DIR/<name>.npy)
+  python bench.py ... --full                              (also measures everything beyond the headline, below)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed live) and `cpu_baseline` (oracle/ = CPU port of the reference path, rank 0, N=1).
+Prints ONE JSON line on rank 0.  A plain run does only what the line's headline (`value`, `ms_per_step`) needs: set-up and the
+untimed calibration, the warm-up, the timed steps, --dump-outputs.  `--full` adds, after the timed steps, `roofline` (dominant
+kernel, HIP-event timed live) and, at N=1, `cpu_baseline` (oracle/ = CPU port of the reference path); at cfg 2 also `dist` (what
+the gradient exchange ran on; at N>1 its exposed time over 10 more replays) and, at N=1, the deterministic leg.
 
 `--workload cfg3` / `cfg4` / `cfg5` time the other built configurations of BASELINE.json the same way (DPTNet 2spk, 1 x 3 s per
 GPU; Sepformer 2spk, 1 x 4 s per GPU; HTDemucs 4 x 10 s stereo 44.1 kHz per GPU: SURVEY.md §8 rows a13 / a14 / a15) -- same step, same
-JSON shape.  The default run (cfg 2, N = 1) keeps cfg 2 as the headline -- it is the configuration the metric is quoted on -- and
+JSON shape.  `--full` at cfg 2, N = 1 keeps cfg 2 as the headline -- it is the configuration the metric is quoted on -- and
 APPENDS those three legs to the same JSON line as `other_workloads` (5 warm-up + 10 timed replays each, same process, each model
-freed before the next), so that the driver's own run carries all four workloads.
+freed before the next), so that one run carries all four workloads.
 
 Every `roofline` object is priced by fqss_amd/roofline_cases.priced(): floor = max(ISSUED flops / dense peak of the matrix dtype the
 kernel executes (bf16 2.5 PF, i8 5 PF; fp32 vector 157.3 TF), algorithmic bytes / 8 TB/s); frac = floor / measured time (<= 1).
@@ -41,6 +44,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: `roofline`, `cpu_baseline` (N=1); "
+                         "cfg2: `dist`, the deterministic leg (N=1), `other_workloads` (N=1).  --no-cpu-baseline, --no-det-leg and "
+                         "--no-other-workloads drop parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--cpu-threads", type=int, default=0)
@@ -51,7 +58,7 @@ def parse():
                          "cfg5 HTDemucs 4 x 10 s stereo 44.1 kHz")
     ap.add_argument("--no-det-leg", action="store_true", help="skip the FQSS_DETERMINISTIC=1 leg (`deterministic_ms_per_step`)")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="cfg2 at N=1 only: skip the cfg 3 / 4 / 5 legs that the default run appends as `other_workloads`")
+                    help="cfg2 at N=1 only: skip the cfg 3 / 4 / 5 legs that --full appends as `other_workloads`")
     ap.add_argument("--other-steps", type=int, default=10, help="timed replays of each `other_workloads` leg")
     ap.add_argument("--other-warmup", type=int, default=5, help="warm-up replays of each `other_workloads` leg")
     ap.add_argument("--hd-batch", type=int, default=4, help="cfg5: samples per GPU (htdemucs.yaml: 32 over 8 GPUs)")
@@ -432,8 +439,6 @@ def main_dualpath(a, comm=None):
     comm.all_reduce_sum(sisdr)
     if comm.rank == 0:
         ms = dt / a.steps * 1e3
-        L = (T - 1) if a.workload == "cfg3" else (T - 16) // 8 + 1
-        rows = 250 * dp_chunks(L, 250)[1]
         out = {"metric": f"QAT-step samples/sec + SI-SDR, {W['name']} 2spk 8kHz W8A8", "value": round(comm.world * a.steps / dt, 3),
                "unit": "samples/s", "n_gpus": comm.world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 3),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -441,10 +446,13 @@ def main_dualpath(a, comm=None):
                           "global_batch": comm.world, "segment_samples": T, "parallelism": f"dp{comm.world}", "kd_lambda": 0.1,
                           "optimizer": f"adam lr {W['lr']:g} + clip 5.0", "launch": launch},
                "si_sdr_db": round(sisdr.item() / comm.world, 4), "loss_db": round(r["loss"].item(), 4),
-               "params": sum(p.numel() for p in model.parameters()),
-               "roofline": dominant_kernel_roofline_dualpath(a.workload, rows, *W["gemm"], seqs=(250, dp_chunks(L, 250)[1]))}
-        if comm.world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_dualpath(a.workload, model, fmodel, W["lr"], T)
+               "params": sum(p.numel() for p in model.parameters())}
+        if a.full:
+            L = (T - 1) if a.workload == "cfg3" else (T - 16) // 8 + 1
+            rows = 250 * dp_chunks(L, 250)[1]
+            out["roofline"] = dominant_kernel_roofline_dualpath(a.workload, rows, *W["gemm"], seqs=(250, dp_chunks(L, 250)[1]))
+            if comm.world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_dualpath(a.workload, model, fmodel, W["lr"], T)
         if leg:
             return out
         print(json.dumps(out), flush=True)
@@ -591,17 +599,18 @@ def main_htdemucs(a, comm=None):
     dt = dt.item()
     if comm.rank == 0:
         ms = dt / a.steps * 1e3
-        Fr, le = 8, -(-T // 1024)
         out = {"metric": "QAT-step samples/sec, HTDemucs 4 stems stereo 44.1kHz W8A8", "value": round(comm.world * B * a.steps / dt, 3),
                "unit": "samples/s", "n_gpus": comm.world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 3),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "config": {"workload": f"HTDemucs 4-stem stereo 44.1 kHz W8A8 QAT step (cfg5), batch {B} x {a.hd_seconds:g} s per GPU, "
                                       "quantizing phase, bottom_channels 512", "global_batch": comm.world * B, "segment_samples": T,
                           "parallelism": f"dp{comm.world}", "kd_lambda": 0.1, "optimizer": "adam lr 0.0003, no clipping", "launch": launch},
-               "loss": round(r["loss"].item(), 6), "params": sum(p.numel() for p in model.parameters()),
-               "roofline": htdemucs_roofline(B, 8, Fr * le, 64)}
-        if comm.world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_htdemucs(model, fmodel, B, T)
+               "loss": round(r["loss"].item(), 6), "params": sum(p.numel() for p in model.parameters())}
+        if a.full:
+            Fr, le = 8, -(-T // 1024)
+            out["roofline"] = htdemucs_roofline(B, 8, Fr * le, 64)
+            if comm.world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_htdemucs(model, fmodel, B, T)
         if leg:
             return out
         print(json.dumps(out), flush=True)
@@ -813,7 +822,8 @@ def main():
         dump_outputs(a.dump_outputs, r)          # before exchange_report's replays overwrite the graphs' static outputs
     sisdr = r["sisdr"].mean().reshape(1).double()
     comm.all_reduce_sum(sisdr)
-    dist_info = exchange_report(step, comm, ldev, lambda i: step(X[i & 1], TG[i & 1], x_next=X[(i + 1) & 1]), it)
+    if a.full:
+        dist_info = exchange_report(step, comm, ldev, lambda i: step(X[i & 1], TG[i & 1], x_next=X[(i + 1) & 1]), it)
 
     if comm.rank == 0:
         ms = dt / a.steps * 1e3
@@ -831,40 +841,41 @@ def main():
             "step_algorithmic_GB": 74.8,
             "step_algorithmic_frac_of_hbm_peak": round(74.8 / (ms * 1e-3) / HBM_PEAK_GBS, 4),
         }
-        out["dist"] = dist_info
-        # ... and the bytes this build actually has to move (every kernel's operands read once / results written once at their real width)
-        out["roofline"], out["roofline_other_kernels"], step = dominant_kernel_roofline(dev, ms)
-        out.update(step)
-        if comm.world == 1 and not a.no_det_leg and not a.no_graph:
-            out.update(deterministic_leg(a, dev))
-        if comm.world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(a.cpu_threads)
-        if comm.world == 1 and not a.no_other_workloads:
-            # the other three BASELINE configurations in the SAME driver-run line: the cfg-2 model, its graphs and
-            # its memory pools are released first, each leg frees its own before the next
-            import copy
-            import gc
-            del step, model, fmodel, r
-            legs = []
-            for w in ("cfg3", "cfg4", "cfg5"):
-                gc.collect()
-                torch.cuda.empty_cache()
-                torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)))))
-                b = copy.copy(a)
-                b.workload, b.steps, b.warmup = w, a.other_steps, a.other_warmup
-                t_leg = time.perf_counter()
-                try:                                        # a failing leg must not lose the cfg-2 line measured above
-                    o = main_htdemucs(b, comm) if w == "cfg5" else main_dualpath(b, comm)
-                except Exception as e:                      # noqa: BLE001
-                    legs.append({"workload": w, "error": f"{type(e).__name__}: {e}"[:400], "leg_wall_s": round(time.perf_counter() - t_leg, 1)})
-                    continue
-                leg = {"workload": o["config"]["workload"], "metric": o["metric"], "steps": o["steps"], "warmup": o["warmup"],
-                       "ms_per_step": o["ms_per_step"], "value": o["value"], "unit": o["unit"], "launch": o["config"]["launch"],
-                       "roofline": o["roofline"], "leg_wall_s": round(time.perf_counter() - t_leg, 1)}
-                if "cpu_baseline" in o:
-                    leg["cpu_baseline"] = o["cpu_baseline"]
-                legs.append(leg)
-            out["other_workloads"] = legs
+        if a.full:
+            out["dist"] = dist_info
+            # ... and the bytes this build actually has to move (every kernel's operands read once / results written once at their real width)
+            out["roofline"], out["roofline_other_kernels"], step = dominant_kernel_roofline(dev, ms)
+            out.update(step)
+            if comm.world == 1 and not a.no_det_leg and not a.no_graph:
+                out.update(deterministic_leg(a, dev))
+            if comm.world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(a.cpu_threads)
+            if comm.world == 1 and not a.no_other_workloads:
+                # the other three BASELINE configurations in the SAME line: the cfg-2 model, its graphs and
+                # its memory pools are released first, each leg frees its own before the next
+                import copy
+                import gc
+                del step, model, fmodel, r
+                legs = []
+                for w in ("cfg3", "cfg4", "cfg5"):
+                    gc.collect()
+                    torch.cuda.empty_cache()
+                    torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)))))
+                    b = copy.copy(a)
+                    b.workload, b.steps, b.warmup = w, a.other_steps, a.other_warmup
+                    t_leg = time.perf_counter()
+                    try:                                        # a failing leg must not lose the cfg-2 line measured above
+                        o = main_htdemucs(b, comm) if w == "cfg5" else main_dualpath(b, comm)
+                    except Exception as e:                      # noqa: BLE001
+                        legs.append({"workload": w, "error": f"{type(e).__name__}: {e}"[:400], "leg_wall_s": round(time.perf_counter() - t_leg, 1)})
+                        continue
+                    leg = {"workload": o["config"]["workload"], "metric": o["metric"], "steps": o["steps"], "warmup": o["warmup"],
+                           "ms_per_step": o["ms_per_step"], "value": o["value"], "unit": o["unit"], "launch": o["config"]["launch"],
+                           "roofline": o["roofline"], "leg_wall_s": round(time.perf_counter() - t_leg, 1)}
+                    if "cpu_baseline" in o:
+                        leg["cpu_baseline"] = o["cpu_baseline"]
+                    legs.append(leg)
+                out["other_workloads"] = legs
         print(json.dumps(out), flush=True)
     comm.barrier()
     comm.close()

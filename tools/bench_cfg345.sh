@@ -7,8 +7,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof_$R
 mkdir -p $O
 for w in cfg3 cfg4 cfg5; do
-  python3 bench.py --workload $w > $O/${R}_${w}_bench.json 2> $O/${w}_bench.err || { tail -5 $O/${w}_bench.err; exit 1; }
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${w}_prof -- python3 bench.py --workload $w --no-cpu-baseline > $O/${w}_prof.log 2>&1
+  python3 bench.py --workload $w --full > $O/${R}_${w}_bench.json 2> $O/${w}_bench.err || { tail -5 $O/${w}_bench.err; exit 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${w}_prof -- python3 bench.py --workload $w --full --no-cpu-baseline > $O/${w}_prof.log 2>&1
   cp "$(find $O/${w}_prof -name '*kernel_stats.csv' | head -1)" $O/${R}_${w}_kernel_stats.csv
   rm -rf $O/${w}_prof
   rocprofv3 --kernel-trace --output-format csv -d $O/${w}_trace -- python3 bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-graph > $O/${w}_trace.log 2>&1

@@ -1,5 +1,5 @@
 #!/bin/bash
-# the cfg 3 / 4 / 5 roofline kernels under the two counter passes (the second half of tools/make_profiles.sh on its own) + the default bench line
+# the cfg 3 / 4 / 5 roofline kernels under the two counter passes (the second half of tools/make_profiles.sh on its own) + the full bench line
 set -o pipefail
 R=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
@@ -11,4 +11,4 @@ python3 tools/roofline_probe.py --reduce "$(find $O/rl2_fetch -name '*counter_co
     gpurun_out/rl_manifest.json $O/${R}_pmc_traffic_cfg345.json > $O/${R}_pmc_traffic_cfg345.txt || exit 1
 rm -rf $O/rl2_fetch $O/rl2_write
 cp $O/${R}_pmc_traffic_cfg345.json profiles/
-python3 bench.py > $O/${R}_bench_line.json 2> $O/bench2.err
+python3 bench.py --full > $O/${R}_bench_line.json 2> $O/bench2.err
