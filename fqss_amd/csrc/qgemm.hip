@@ -1457,8 +1457,10 @@ static int conv2_impl(const char* who, int mode, const void* A, const float* Bsi
         }
     }
     FQSS_REQUIRE(smin >= 0, "implicit convolution: a tap reaches in front of the packed plane");
+    // the loader moves 8-column groups and clamps a group's start to cmax: the last live group, at ((N - 1) / 8) * 8, must not be clamped
+    // (a clamped live group would be read from shifted columns: wrong outputs, no fault)
     const int64_t cmax = plane_in - smax - 8;
-    FQSS_REQUIRE(cmax >= N - 8 && cmax >= 0, "implicit convolution: the packed plane is too short for the last row's taps");
+    FQSS_REQUIRE(cmax >= ((N - 1) / 8) * 8, "implicit convolution: the packed plane is too short for the last row's taps");
     QGemmArgs g{};
     g.A = A; g.B = Bsig; g.C = C; g.M = M; g.N = (int)N; g.K = (int)K;
     g.lda = K; g.ldb = plane_in; g.ldc = plane_out;

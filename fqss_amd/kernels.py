@@ -989,13 +989,15 @@ def axpby(a, b, sb, sa=1.0):
 
 
 def axpby_(a, b, sb, sa=1.0):
-    """a = sa*a + sb*b in place (element-wise: the output may alias an operand)"""
+    """a = sa*a + sb*b in place (element-wise: the output may alias an operand).  Bumps a's version counter like a torch in-place op,
+    so that caches keyed on it (ops_dp._frozen_cache) see the write"""
     _need_gpu(a, b)
     assert a.shape == b.shape and a.is_contiguous()
     rm = rowmat(a)
     b, rows, cols, ld_b = as_rowmat(b)
     assert rm is not None and (rm[0], rm[1]) == (rows, cols)
     _lib.call("fqss_axpby", _p(a), _p(b), float(sa), float(sb), _p(a), rows, cols, rm[2], ld_b, rm[2], _stream())
+    torch.autograd.graph.increment_version(a)
     return a
 
 

@@ -829,15 +829,19 @@ class ConvHalo(Function):
 
 def _frozen_cache(w, key, make):
     """the regrouped image of a weight that cannot change under the caller (no autograd in flight: the frozen float teacher,
-    mysystem.py:132-133 -- runtime.KDTrainStep sets requires_grad False on its parameters and nothing but load_state_dict, which bumps the
-    version, writes them): built once per (parameter, in-place version) and kept on the parameter -- the student's weights change every
-    step and are regrouped inside the step"""
+    mysystem.py:132-133 -- runtime.KDTrainStep sets requires_grad False on its parameters): built once per (in-place version, storage,
+    device) of the parameter and kept on it -- the student's weights change every step and are regrouped inside the step.
+    Seen: in-place torch writes (copy_, load_state_dict: they bump the version), `param.data = new` (the version stays, the storage
+    changes; the cache holds the storage it was stamped with, so its address cannot be recycled meanwhile) and the library's in-place
+    wrappers (K.axpby_ bumps the version of what it writes).  Not seen: a write through a raw pointer that bypasses both, e.g. a direct
+    _lib.call into the parameter -- such a writer bumps the version itself (torch.autograd.graph.increment_version)."""
     base = w._base if (w._is_view() and w._base is not None) else w          # (the layer hands a view of its parameter)
     if torch.is_grad_enabled() or base.requires_grad or not isinstance(base, torch.nn.Parameter):
         return make()
+    stamp = (base._version, base.data_ptr(), base.device)
     cache = getattr(base, "_fqss_regroup", None)
-    if cache is None or cache[0] != base._version:
-        cache = (base._version, {})
+    if cache is None or cache[0] != stamp:
+        cache = (stamp, {}, base.data)
         base._fqss_regroup = cache
     if key not in cache[1]:
         cache[1][key] = make()

@@ -191,7 +191,11 @@ int fqss_conv1d_s1_bwd_w(const float* gz, const float* x, float* gw, int B, int 
  *   dgrad  the same sum over (co, t) on the packed gradient gzp (halo (kh-1) dh - ph, (kw-1) dw - pw) with the caller's regrouped
  *          weight codes [Ci][Co*taps]: base (kh-1) dh Wp + (kw-1) dw, row_step -dh Wp, col_step -dw
  *   wgrad  gw[co][ci*taps + t] += sum_{b,m} gzp[b][co][m] xp[b][ci][m + (t / kw) row_step + (t % kw) col_step - off]   (gw caller-zeroed;
- *          off = the gradient's own halo offset, (ph_g Wp + pw_g); zero outside the plane) */
+ *          off = the gradient's own halo offset, (ph_g Wp + pw_g); zero outside the plane)
+ *   plane slack (fwd / dgrad): with smax the largest tap shift, plane_in >= ((N - 1) / 8) * 8 + 8 + smax -- the loader reads 8-column
+ *          groups, the last one starting at ((N - 1) / 8) * 8, whole; a shorter plane is refused.  plane_in and plane_out % 4 == 0,
+ *          plane_out >= N; N needs no alignment.  Each output plane gets columns [0, roundup4(N)): the epilogue's 4-wide store may write
+ *          [N, roundup4(N)), nothing past it */
 int fqss_halo_pack(const float* x, float* xp, int64_t B, int64_t C, int64_t H, int64_t W, int64_t sb, int64_t sc, int64_t sh,
                    int ph, int pw, int64_t Wp, int64_t plane, fqss_stream_t stream);
 /* Strided convolutions along one axis (kernel k = T s taps, stride s, padding p: the k8 s4 p2 encoder / decoder layers) on the same
