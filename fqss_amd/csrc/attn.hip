@@ -305,10 +305,10 @@ __global__ __launch_bounds__(256) void k_attn_bwd_mfma(const float* __restrict__
     }
 }
 
-// Matrix-core forward (head_dim 16 / 32, L <= 256).  A wave owns a 32-row query tile and works on TRANSPOSED logits tiles
-// T = K_jt Q_it^T (lane = query row i, 16 keys in registers), so the row max / row sum are in-lane reductions plus one exchange
-// between the two lane halves, and exp(T - m) is already the A operand of O_it += P V_jt.  Two passes over the keys (max, then
-// exp / sum / PV), like the VALU kernel: same arithmetic, same saved statistics.
+// Matrix-core forward (head_dim 32, L <= 256; fqss_attn_fwd keeps head_dim 16 on the VALU kernel, see there).  A wave owns a 32-row
+// query tile and works on TRANSPOSED logits tiles T = K_jt Q_it^T (lane = query row i, 16 keys in registers), so the row max / row
+// sum are in-lane reductions plus one exchange between the two lane halves, and exp(T - m) is already the A operand of
+// O_it += P V_jt.  Two passes over the keys (max, then exp / sum / PV), like the VALU kernel: same arithmetic, same saved statistics.
 template <int HD>
 __global__ __launch_bounds__(256) void k_attn_fwd_mfma(const float* __restrict__ q, const float* __restrict__ k,
                                                         const float* __restrict__ v, float* __restrict__ o, float* __restrict__ stats,
@@ -428,15 +428,9 @@ extern "C" int fqss_attn_fwd(const float* q, const float* k, const float* v, flo
         const int Lp = (L + 31) / 32 * 32;
         const size_t ldsm = (size_t)3 * Lp * (hd + 1) * sizeof(float);
         grid.y = (unsigned)cdiv(Lp / 32, 4);      // one 32-row tile per wave: (b, h) pairs alone leave CUs idle or wrap around (272 on 256)
-        if (hd == 16) {
-            int rc = ensure_lds(k_attn_fwd_mfma<16>, ldsm, "fqss_attn_fwd");
-            if (rc != FQSS_OK) return rc;
-            hipLaunchKernelGGL((k_attn_fwd_mfma<16>), grid, block, ldsm, s, q, k, v, o, stats, L, B, nh, ld_q, ld_k, ld_v, ld_o, obs_attn, obs_soft);
-        } else {
-            int rc = ensure_lds(k_attn_fwd_mfma<32>, ldsm, "fqss_attn_fwd");
-            if (rc != FQSS_OK) return rc;
-            hipLaunchKernelGGL((k_attn_fwd_mfma<32>), grid, block, ldsm, s, q, k, v, o, stats, L, B, nh, ld_q, ld_k, ld_v, ld_o, obs_attn, obs_soft);
-        }
+        int rc = ensure_lds(k_attn_fwd_mfma<32>, ldsm, "fqss_attn_fwd");
+        if (rc != FQSS_OK) return rc;
+        hipLaunchKernelGGL((k_attn_fwd_mfma<32>), grid, block, ldsm, s, q, k, v, o, stats, L, B, nh, ld_q, ld_k, ld_v, ld_o, obs_attn, obs_soft);
         return launch_status("fqss_attn_fwd");
     }
     const size_t lds = (size_t)2 * L * hd * sizeof(float);

@@ -490,8 +490,9 @@ extern "C" int fqss_lstm_gate_fn(const float* x, float* sigmoid_out, float* tanh
 
 static int lstm_bwd_impl(const char* who, const float* gout, const float* whh, const float* gsav, const float* csav, float* dG, float* gbias,
                          int S, int B, int H, fqss_stream_t stream, LstmBiasGrads gb4 = LstmBiasGrads{nullptr, nullptr, nullptr, nullptr}) {
-    FQSS_REQUIRE(gout && whh && gsav && csav && dG, "null tensor");
-    FQSS_REQUIRE(S > 0 && B > 0 && H > 0 && H <= 256, "bad shape (H <= 256)");
+    // (not FQSS_REQUIRE: its __func__ would name this helper, and the message has to name the entry the caller used)
+    if (!(gout && whh && gsav && csav && dG)) { set_error("%s: null tensor", who); return FQSS_EINVAL; }
+    if (!(S > 0 && B > 0 && H > 0 && H <= 256)) { set_error("%s: bad shape (H <= 256)", who); return FQSS_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)cdiv(B, kNB), 2);
     const size_t lds = (size_t)(kNB * 4 * H + 4 * kNB * H) * sizeof(float);

@@ -776,7 +776,14 @@ int fqss_ola2_bwd(const float* g, float* gy, int64_t N, int64_t L, int64_t ld_gy
 
 /* Attention core of MultiheadAttentionQ (qat_layers.py:903-911): o = softmax(q k^T) v per (sequence b, head h).
  * q, k, v, o: row matrices [l*B + b][nh*hd] (head h = column block h); q is the already scaled + quantized query.
- * stats [B*nh][L][2] = (row max, row sum) saved for the backward, which recomputes the probabilities.
+ * stats [B*nh][L][2], row i of pair b*nh + h = (m_i, l_i) with l_i = sum_j exp(s_ij - m_i), saved for the backward, which recomputes
+ * the probabilities as exp(s_ij - m_i) / l_i and uses the pair in no other way.  fqss_attn_fwd writes m_i = max_j s_ij (the row maximum
+ * itself) in every kernel form.  Any pair that satisfies the identity is read alike by every backward form of BOTH attention families:
+ * stats written by fqss_attn_long_fwd (whose m_i may lie below the row maximum, see there) serve fqss_attn_bwd and the other way
+ * round (tests/test_gpu_sequence_kernels.py::test_attention_stats_pair_across_families).
+ * Lengths: the kernels keep a head in LDS (160 KiB): forward 2 L hd floats (head_dim 32, L <= 256: 3 Lp (hd + 1), Lp = L rounded up to 32),
+ * backward 4 L hd + 3 L floats (head_dim 16 / 32, L <= 256: 4 Lp (hd + 1) + 3 Lp).  A longer sequence is refused with FQSS_EINVAL before
+ * any launch; the backward's limit is the lower one (head_dim 32: forward L <= 640, backward L <= 312).
  * obs_attn / obs_soft (both or neither): ordered-uint (min, max) of the logits / probabilities -- the reference's
  * `activation_fake_quantize_attn/_softmax` observe them during the first 50 calls and discard their outputs. */
 int fqss_attn_fwd(const float* q, const float* k, const float* v, float* o, float* stats, int L, int B, int nh,
@@ -826,7 +833,7 @@ int fqss_lstm_bwd(const float* gout, const float* whh, const float* gsav, const 
 /* Test hook: the H = 128 forward's own gate functions (short dependent chains on v_exp_f32 / v_rcp_f32 in place of libm's
  * expf / tanhf and an IEEE division; <= 4 ulp from the exact value) over n arguments: sigmoid_out[i], tanh_out[i] of x[i] */
 int fqss_lstm_gate_fn(const float* x, float* sigmoid_out, float* tanh_out, int64_t n, fqss_stream_t stream);
-/* fqss_lstm_bwd that also ADDS the column sums of dG over (step, sequence) into gbias [2][4H] (caller-zeroed): the gradient of
+/* fqss_lstm_bwd that also ADDS the column sums of dG over (step, sequence) into gbias [2][4H] ("+=" on whatever it holds): the gradient of
  * b_ih and b_hh of each direction (torch's LSTM backward, reached from qat_layers.py:571-600), kept in registers by the
  * threads that produce dG */
 int fqss_lstm_bwd_b(const float* gout, const float* whh, const float* gsav, const float* csav, float* dG, float* gbias, int S,
@@ -939,7 +946,11 @@ int fqss_chan_sum(const float* g, float* out, int64_t B, int64_t C, int64_t M, i
 /* Streaming attention core for long sequences and cross attention (HTDemucs transformer, htdemucsq.py:138-329; the arithmetic of
  * MultiheadAttentionQ.forward between the quantized q / k / v and the heads, qat_layers.py:903-911, with Lq != Lk allowed).
  * Rows are x[l*sl + b*sb + h*hd + d]; `strides` is a HOST array of (sl, sb) element-stride pairs: q, k, v, o for the forward,
- * q, k, v, o, go, gq, gk, gv for the backward.  stats [B*nh][Lq][2] = (row max, row sum); dsum: workspace of B*nh*Lq floats.
+ * q, k, v, o, go, gq, gk, gv for the backward.  dsum: workspace of B*nh*Lq floats.
+ * stats [B*nh][Lq][2] = (m_i, l_i) with l_i = sum_j exp(s_ij - m_i), the contract of fqss_attn_fwd / fqss_attn_bwd: the backward uses
+ * exp(s_ij - m_i) / l_i alone, and either family's backward reads either family's stats.  m_i is a REFERENCE value, not necessarily the
+ * row maximum: the split-bf16 forward moves it only when a key tile's maximum exceeds it by more than 8, so max_j s_ij - 8 <= m_i <=
+ * max_j s_ij (exp(s_ij - m_i) <= e^8); m_i + log(l_i) is the row's log-sum-exp whatever m_i is.
  * obs_attn / obs_soft: optional observer workspaces (min / max of the logits and of the probabilities), as fqss_attn_fwd.  */
 int fqss_attn_long_fwd(const float* q, const float* k, const float* v, float* o, float* stats, int Lq, int Lk, int B, int nh, int hd,
                        const int64_t* strides, uint32_t* obs_attn, uint32_t* obs_soft, fqss_stream_t stream);

@@ -157,6 +157,12 @@ def test_unary_and_data_movement_kernels(golden):
 @pytest.mark.parametrize("L,B,nh,hd", [(9, 5, 4, 4), (250, 6, 4, 16), (194, 3, 4, 16), (37, 4, 4, 2), (300, 2, 8, 32), (250, 3, 8, 32), (34, 5, 8, 32),
                                        (256, 2, 4, 16), (33, 2, 4, 16)])
 def test_attention_kernels(L, B, nh, hd):
+    """K.attn_fwd / K.attn_bwd against the oracle's fp32 attention core.  Which kernels a case runs is the dispatcher's choice
+    (kernels._attn_stream_ok; pinned by test_attention_dispatch below): q dense, k / v column blocks of an [L, B, 3E] buffer with E a
+    multiple of 16 are 16-B aligned views, so the seven cases with head_dim 16 / 32 run the streaming kernels of csrc/attn_long.hip
+    (fqss_attn_long_fwd / _bwd, as test_attn_long does); only (9, 5, 4, 4) and (37, 4, 4, 2) run the LDS-resident kernels of
+    csrc/attn.hip (k_attn_fwd<4>, <2>, k_attn_bwd<4>, <2>).  The LDS-resident family has its own test against float64 at every head
+    width and kernel form: tests/test_gpu_sequence_kernels.py."""
     from fqss_amd import kernels as K
     E = nh * hd
     X = rnd(L, B, 3 * E, seed=13, scale=0.8)
@@ -187,6 +193,41 @@ def test_attention_kernels(L, B, nh, hd):
         return np.array([u], dtype=np.uint32).view(np.float32)[0]
     np.testing.assert_allclose([dec(w[0]), dec(w[1])], [float(s.min()), float(s.max())], rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose([dec(w[2]), dec(w[3])], [float(p.min()), float(p.max())], rtol=1e-4, atol=1e-12)
+
+
+def test_attention_dispatch(monkeypatch):
+    """which C entry K.attn_fwd / K.attn_bwd choose: the streaming kernels (fqss_attn_long_*) for 16-B aligned head_dim-16 views, the
+    LDS-resident ones (fqss_attn_*) for head_dim 8, for a view whose base is one float off alignment, and whenever K.ATTN_STREAM is off.
+    A change of the predicate then shows up here instead of silently moving test_attention_kernels to another kernel family."""
+    from fqss_amd import _lib
+    from fqss_amd import kernels as K
+    called = []
+    real = _lib.call
+
+    def spy(name, *args):
+        called.append(name)
+        return real(name, *args)
+    monkeypatch.setattr(_lib, "call", spy)
+
+    def entries(L, B, nh, hd, shift=0):
+        E = nh * hd
+        flat = rnd(L * B * 3 * E + 4, seed=15, scale=0.5).cuda()
+        X = flat[shift:shift + L * B * 3 * E].view(L, B, 3 * E)
+        q = X[..., :E].contiguous() if shift == 0 else X[..., :E]
+        del called[:]
+        o, st = K.attn_fwd(q, X[..., E:2 * E], X[..., 2 * E:], L, B, nh)
+        K.attn_bwd(q, X[..., E:2 * E], X[..., 2 * E:], o, torch.ones(L, B, E, device="cuda"), st, L, B, nh)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(o).all())
+        return [n for n in called if "attn" in n]
+
+    monkeypatch.setattr(K, "ATTN_STREAM", True)
+    assert entries(40, 2, 4, 16) == ["fqss_attn_long_fwd", "fqss_attn_long_bwd"]
+    assert entries(40, 2, 4, 8) == ["fqss_attn_fwd", "fqss_attn_bwd"]
+    assert entries(40, 2, 4, 16, shift=1) == ["fqss_attn_fwd", "fqss_attn_bwd"]
+    monkeypatch.setattr(K, "ATTN_STREAM", False)
+    assert entries(40, 2, 4, 16) == ["fqss_attn_fwd", "fqss_attn_bwd"]
+    assert entries(40, 2, 8, 32) == ["fqss_attn_fwd", "fqss_attn_bwd"]
 
 
 def test_lstm_gate_functions():
