@@ -24,8 +24,11 @@ _PROTOS = {
     "fqss_wq_observe": [P, I64, I64, I64, P, P, P],
     "fqss_wq_fwd": [P, P, P, I64, I64, I64, P, P, P],
     "fqss_wq_bwd": [P, P, P, P, P, I64, I64, I64, P, P, I32, P],
+    "fqss_wq_fwd_bits": [P, P, P, I64, I64, I64, P, P, I32, P],
+    "fqss_wq_bwd_bits": [P, P, P, P, P, I64, I64, I64, P, P, I32, I32, P],
     "fqss_gacc_flush": [P, P, P, P, P],
     "fqss_gacc_flush_multi": [P, I32, P],
+    "fqss_wq_table_check": [P, I32],
     "fqss_wq_multi_fwd": [P, I32, I32, P],
     "fqss_wq_multi_bwd": [P, I32, I32, P],
     "fqss_pwconv_fwd": [P, P, P, P, I32, I32, I32, I32, I64, I64, P],
@@ -44,6 +47,7 @@ _PROTOS = {
     "fqss_pwconv_bwd_x": [P, P, P, I32, I32, I32, I32, I64, I64, P],
     "fqss_pwconv_bwd_w": [P, P, P, I32, I32, I32, I32, I64, I64, P],
     "fqss_wq_codes": [P, P, P, P, P, I32, I32, P, P, P],
+    "fqss_wq_codes_bits": [P, P, P, P, P, I32, I32, P, P, I32, P],
     "fqss_qpw_fwd": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I64, I64, P],
     "fqss_qpw_bwd_x": [P, P, P, P, I32, I32, I32, I32, I64, I64, P],
     "fqss_qpw_bwd_x_add": [P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, P],

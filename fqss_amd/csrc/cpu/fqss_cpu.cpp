@@ -55,7 +55,11 @@ inline float fq_asym(float t, const QRange& r, float& c, float& u, bool& inr) {
     c = fminf(fmaxf(X, 0.0f), 255.0f);
     return r.delta * c + r.lo;
 }
-inline float wq_delta(float lo, float hi) { return (2.0f * fmaxf(fabsf(lo), fabsf(hi))) / 255.0f; }
+// weight grid at width n in [2, 8]: L = 2^n - 1 levels, codes in [-2^(n-1), 2^(n-1) - 1] (exact floats)
+inline float wq_levels(int n_bits) { return (float)((1 << n_bits) - 1); }
+inline float wq_qlo(int n_bits) { return -(float)(1 << (n_bits - 1)); }
+inline float wq_qhi(int n_bits) { return (float)((1 << (n_bits - 1)) - 1); }
+inline float wq_delta(float lo, float hi, float L) { return (2.0f * fmaxf(fabsf(lo), fabsf(hi))) / L; }
 }  // namespace
 
 extern "C" {
@@ -218,41 +222,50 @@ int fqss_wq_observe(const float* w, int64_t outer, int64_t C, int64_t inner, flo
     return FQSS_OK;
 }
 
-int fqss_wq_fwd(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax,
-                fqss_stream_t) {
+int fqss_wq_fwd_bits(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax,
+                     int n_bits, fqss_stream_t) {
     REQUIRE(w && wq && qmin && qmax && outer > 0 && C > 0 && inner > 0, "bad args");
+    REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
     const int64_t n = outer * C * inner;
     for (int64_t e = 0; e < n; ++e) {
         const int64_t c = (e / inner) % C;
-        const float delta = wq_delta(qmin[c], qmax[c]);
+        const float delta = wq_delta(qmin[c], qmax[c], L);
         const float X = nearbyintf(w[e] / delta);
-        const float q = fminf(fmaxf(X, -128.0f), 127.0f);
+        const float q = fminf(fmaxf(X, qlo), qhi);
         wq[e] = delta * q;
         if (idx) idx[e] = (int8_t)q;
     }
     return FQSS_OK;
 }
 
-int fqss_wq_bwd(const float* w, const float* g, float* gw, float* gmin, float* gmax, int64_t outer, int64_t C, int64_t inner,
-                const float* qmin, const float* qmax, int accumulate, fqss_stream_t) {
+int fqss_wq_fwd(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax,
+                fqss_stream_t s) {
+    return fqss_wq_fwd_bits(w, wq, idx, outer, C, inner, qmin, qmax, 8, s);
+}
+
+int fqss_wq_bwd_bits(const float* w, const float* g, float* gw, float* gmin, float* gmax, int64_t outer, int64_t C, int64_t inner,
+                     const float* qmin, const float* qmax, int accumulate, int n_bits, fqss_stream_t) {
     REQUIRE(w && g && gw && gmin && gmax && qmin && qmax && outer > 0 && C > 0 && inner > 0, "bad args");
+    REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
     for (int64_t c = 0; c < C; ++c) {
         const float lo = qmin[c], hi = qmax[c];
-        const float delta = wq_delta(lo, hi);
+        const float delta = wq_delta(lo, hi, L);
         double p = 0.0;
         for (int64_t o = 0; o < outer; ++o)
             for (int64_t i = 0; i < inner; ++i) {
                 const int64_t k = (o * C + c) * inner + i;
                 const float u = w[k] / delta;
                 const float X = nearbyintf(u);
-                const bool inr = (X >= -128.0f) && (X <= 127.0f);
-                const float q = fminf(fmaxf(X, -128.0f), 127.0f);
+                const bool inr = (X >= qlo) && (X <= qhi);
+                const float q = fminf(fmaxf(X, qlo), qhi);
                 const float gk = g[k];
                 const float gwk = inr ? (gk * delta) / delta : 0.0f;
                 gw[k] = accumulate ? gw[k] + gwk : gwk;
                 p += (double)(gk * (inr ? (q - u) : q));
             }
-        const double D = p * (2.0 / 255.0);
+        const double D = p * (2.0 / (double)L);
         const float al = fabsf(lo), ah = fabsf(hi);
         const double wl = al > ah ? 1.0 : (al == ah ? 0.5 : 0.0), wh = ah > al ? 1.0 : (al == ah ? 0.5 : 0.0);
         const double sl = lo > 0.0f ? 1.0 : (lo < 0.0f ? -1.0 : 0.0), sh = hi > 0.0f ? 1.0 : (hi < 0.0f ? -1.0 : 0.0);
@@ -261,6 +274,11 @@ int fqss_wq_bwd(const float* w, const float* g, float* gw, float* gmin, float* g
         gmax[c] = accumulate ? gmax[c] + dmax : dmax;
     }
     return FQSS_OK;
+}
+
+int fqss_wq_bwd(const float* w, const float* g, float* gw, float* gmin, float* gmax, int64_t outer, int64_t C, int64_t inner,
+                const float* qmin, const float* qmax, int accumulate, fqss_stream_t s) {
+    return fqss_wq_bwd_bits(w, g, gw, gmin, gmax, outer, C, inner, qmin, qmax, accumulate, 8, s);
 }
 
 // ------------------------------------------------------------------------------------------------ pointwise conv (qat_layers.py:137-146)

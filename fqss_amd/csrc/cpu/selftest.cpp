@@ -42,6 +42,14 @@ int main() {
     CHECK(fqss_wq_observe(w.data(), Co, C, 3, qlo.data(), qhi.data(), nullptr) == 0);
     CHECK(fqss_wq_fwd(w.data(), wq.data(), wi.data(), Co, C, 3, qlo.data(), qhi.data(), nullptr) == 0);
     CHECK(fqss_wq_bwd(w.data(), wq.data(), gw.data(), glo.data(), ghi.data(), Co, C, 3, qlo.data(), qhi.data(), 0, nullptr) == 0);
+    // ... at every supported width: codes stay inside the width's range; widths outside 2..8 are refused
+    for (int nb = FQSS_WQ_MIN_BITS; nb <= FQSS_WQ_MAX_BITS; ++nb) {
+        CHECK(fqss_wq_fwd_bits(w.data(), wq.data(), wi.data(), Co, C, 3, qlo.data(), qhi.data(), nb, nullptr) == 0);
+        for (size_t k = 0; k < wi.size(); ++k) CHECK(wi[k] >= -(1 << (nb - 1)) && wi[k] <= (1 << (nb - 1)) - 1);
+        CHECK(fqss_wq_bwd_bits(w.data(), wq.data(), gw.data(), glo.data(), ghi.data(), Co, C, 3, qlo.data(), qhi.data(), 0, nb, nullptr) == 0);
+    }
+    CHECK(fqss_wq_fwd_bits(w.data(), wq.data(), wi.data(), Co, C, 3, qlo.data(), qhi.data(), 1, nullptr) == FQSS_EINVAL);
+    CHECK(fqss_wq_bwd_bits(w.data(), wq.data(), gw.data(), glo.data(), ghi.data(), Co, C, 3, qlo.data(), qhi.data(), 0, 9, nullptr) == FQSS_EINVAL);
     // pointwise conv and its gradients; <gz, W x> == <W^T gz, x>
     auto pw = rnd((size_t)Co * C), bias = rnd(Co), gzc = rnd((size_t)B * Co * ld);
     std::vector<float> z((size_t)B * Co * ld), gx((size_t)B * C * ld), gpw((size_t)Co * C, 0.f);

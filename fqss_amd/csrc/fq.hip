@@ -581,9 +581,9 @@ __global__ __launch_bounds__(256) void k_actq_bwd_colbias(const float* __restric
 // =============================================================================================
 // per-channel symmetric weight quantizer; tensor layout [outer][C][inner]
 // =============================================================================================
-__device__ __forceinline__ float wq_delta(float lo, float hi) {
+__device__ __forceinline__ float wq_delta(float lo, float hi, float L) {
     const float a = fmaxf(fabsf(lo), fabsf(hi));
-    return (2.0f * a) / 255.0f;
+    return (2.0f * a) / L;
 }
 
 __global__ __launch_bounds__(256) void k_wq_observe(const float* __restrict__ w, int64_t outer, int64_t C,
@@ -617,12 +617,13 @@ __global__ __launch_bounds__(256) void k_wq_observe(const float* __restrict__ w,
 
 __global__ __launch_bounds__(256) void k_wq_fwd(const float* __restrict__ w, float* __restrict__ wq,
                                                  int8_t* __restrict__ idx, int64_t n, int64_t C, int64_t inner,
-                                                 const float* __restrict__ qmin, const float* __restrict__ qmax) {
+                                                 const float* __restrict__ qmin, const float* __restrict__ qmax, int n_bits) {
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t c = (e / inner) % C;
-        const float delta = wq_delta(qmin[c], qmax[c]);
+        const float delta = wq_delta(qmin[c], qmax[c], L);
         const float X = rintf(w[e] / delta);
-        const float q = fminf(fmaxf(X, -128.0f), 127.0f);
+        const float q = fminf(fmaxf(X, qlo), qhi);
         wq[e] = delta * q;
         if (idx != nullptr) idx[e] = (int8_t)q;
     }
@@ -631,11 +632,12 @@ __global__ __launch_bounds__(256) void k_wq_fwd(const float* __restrict__ w, flo
 __global__ __launch_bounds__(256) void k_wq_bwd(const float* __restrict__ w, const float* __restrict__ g,
                                                  float* __restrict__ gw, float* gmin, float* gmax, int64_t outer,
                                                  int64_t C, int64_t inner, const float* __restrict__ qmin,
-                                                 const float* __restrict__ qmax, int accumulate) {
+                                                 const float* __restrict__ qmax, int accumulate, int n_bits) {
     __shared__ double red[4];
     const int64_t c = blockIdx.x;
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
     const float lo = qmin[c], hi = qmax[c];
-    const float delta = wq_delta(lo, hi);
+    const float delta = wq_delta(lo, hi, L);
     const int64_t n = outer * inner;
     float p = 0.0f;
     for (int64_t e = threadIdx.x; e < n; e += blockDim.x) {
@@ -643,8 +645,8 @@ __global__ __launch_bounds__(256) void k_wq_bwd(const float* __restrict__ w, con
         const int64_t k = (o * C + c) * inner + i;
         const float u = w[k] / delta;
         const float X = rintf(u);
-        const bool inr = (X >= -128.0f) && (X <= 127.0f);
-        const float q = fminf(fmaxf(X, -128.0f), 127.0f);
+        const bool inr = (X >= qlo) && (X <= qhi);
+        const float q = fminf(fmaxf(X, qlo), qhi);
         const float gk = g[k];
         const float gwk = inr ? (gk * delta) / delta : 0.0f;
         gw[k] = accumulate ? gw[k] + gwk : gwk;
@@ -653,7 +655,7 @@ __global__ __launch_bounds__(256) void k_wq_bwd(const float* __restrict__ w, con
     double v[1] = {(double)p};
     block_sum<double, 1>(v, red);
     if (threadIdx.x == 0) {
-        const double D = v[0] * (2.0 / 255.0);
+        const double D = v[0] * (2.0 / (double)L);
         const float al = fabsf(lo), ah = fabsf(hi);
         // torch.maximum routes the gradient to the larger operand, 1/2-1/2 on ties; |x|' = sign(x)
         const double wl = al > ah ? 1.0 : (al == ah ? 0.5 : 0.0);
@@ -915,14 +917,21 @@ extern "C" int fqss_wq_observe(const float* w, int64_t outer, int64_t C, int64_t
     return launch_status("fqss_wq_observe");
 }
 
-extern "C" int fqss_wq_fwd(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner,
-                           const float* qmin, const float* qmax, fqss_stream_t stream) {
+extern "C" int fqss_wq_fwd_bits(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner,
+                                const float* qmin, const float* qmax, int n_bits, fqss_stream_t stream) {
     FQSS_REQUIRE(w && wq && qmin && qmax && outer > 0 && C > 0 && inner > 0, "bad args");
+    FQSS_REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
     const int64_t n = outer * C * inner;
     int64_t nb = cdiv(n, 256);
     if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(k_wq_fwd, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, wq, idx, n, C, inner, qmin, qmax);
-    return launch_status("fqss_wq_fwd");
+    hipLaunchKernelGGL(k_wq_fwd, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, wq, idx, n, C, inner, qmin, qmax,
+                       n_bits);
+    return launch_status("fqss_wq_fwd_bits");
+}
+
+extern "C" int fqss_wq_fwd(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner,
+                           const float* qmin, const float* qmax, fqss_stream_t stream) {
+    return fqss_wq_fwd_bits(w, wq, idx, outer, C, inner, qmin, qmax, 8, stream);
 }
 
 extern "C" int fqss_gacc_flush(double* gacc, float* gmin, float* gmax, float* gslope, fqss_stream_t stream) {
@@ -931,13 +940,20 @@ extern "C" int fqss_gacc_flush(double* gacc, float* gmin, float* gmax, float* gs
     return launch_status("fqss_gacc_flush");
 }
 
+extern "C" int fqss_wq_bwd_bits(const float* w, const float* g, float* gw, float* gmin, float* gmax, int64_t outer,
+                                int64_t C, int64_t inner, const float* qmin, const float* qmax, int accumulate, int n_bits,
+                                fqss_stream_t stream) {
+    FQSS_REQUIRE(w && g && gw && gmin && gmax && qmin && qmax && outer > 0 && C > 0 && inner > 0, "bad args");
+    FQSS_REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    hipLaunchKernelGGL(k_wq_bwd, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, w, g, gw, gmin, gmax, outer, C,
+                       inner, qmin, qmax, accumulate, n_bits);
+    return launch_status("fqss_wq_bwd_bits");
+}
+
 extern "C" int fqss_wq_bwd(const float* w, const float* g, float* gw, float* gmin, float* gmax, int64_t outer,
                            int64_t C, int64_t inner, const float* qmin, const float* qmax, int accumulate,
                            fqss_stream_t stream) {
-    FQSS_REQUIRE(w && g && gw && gmin && gmax && qmin && qmax && outer > 0 && C > 0 && inner > 0, "bad args");
-    hipLaunchKernelGGL(k_wq_bwd, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, w, g, gw, gmin, gmax, outer, C,
-                       inner, qmin, qmax, accumulate);
-    return launch_status("fqss_wq_bwd");
+    return fqss_wq_bwd_bits(w, g, gw, gmin, gmax, outer, C, inner, qmin, qmax, accumulate, 8, stream);
 }
 
 static bool gluq_rows_ok(const void* a, const void* b, int64_t lda, int64_t ldb, int64_t M) {

@@ -215,6 +215,12 @@ __device__ __forceinline__ float div_by(float a, float b, float y) {
     const float r = fmaf(-b, q, a);
     return fmaf(r, y, q);
 }
+// Grid of the symmetric weight quantizer at width n in [FQSS_WQ_MIN_BITS, FQSS_WQ_MAX_BITS]: L = 2^n - 1 levels, codes in
+// [qlo, qhi] = [-2^(n-1), 2^(n-1) - 1] (qat_quant.py:126-135, sym=True, sign=True).  Small integers, exact as floats; the kernels derive
+// them once per workgroup, outside their element loops.
+__device__ __forceinline__ float wq_levels(int n_bits) { return (float)((1 << n_bits) - 1); }
+__device__ __forceinline__ float wq_qlo(int n_bits) { return -(float)(1 << (n_bits - 1)); }
+__device__ __forceinline__ float wq_qhi(int n_bits) { return (float)((1 << (n_bits - 1)) - 1); }
 // Pins a wave-uniform value (typically a field of a by-value kernel-argument struct) in SGPRs.  Such fields live in the
 // kernarg segment; when two of them are selected per lane (`row < split ? g.ld1 : g.ld2`) the compiler selects the ADDRESS
 // and issues a per-lane global load from the kernarg segment followed by s_waitcnt vmcnt(0) -- a memory round trip in the

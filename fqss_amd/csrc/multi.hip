@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void k_gacc_flush_multi(const long long* __res
 
 // weight descriptor (int64 words): 0 w, 1 wq, 2 idx, 3 idxT, 4 dw, 5 rw, 6 qmin, 7 qmax, 8 gwq, 9 gw, 10 gmin, 11 gmax,
 //                                  12 outer, 13 C, 14 inner, 15 first block, 16 row stride of idxT (>= C: the codes of
-//                                  paired layers are concatenated along the output channels)
+//                                  paired layers are concatenated along the output channels), 17 width in bits (2..8)
 __device__ __forceinline__ const long long* find_desc(const long long* table, int n, int blk) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {   // last descriptor whose first block <= blk
@@ -69,8 +69,10 @@ __global__ __launch_bounds__(256) void k_wq_multi_fwd(const long long* __restric
     const int outer = (int)d[12], C = (int)d[13], inner = (int)d[14];
     const int c = blockIdx.x - (int)d[15];
     const int64_t ldT = d[16];
+    const int n_bits = (int)d[17];
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
     const float a = fmaxf(fabsf(qmin[c]), fabsf(qmax[c]));
-    const float delta = (2.0f * a) / 255.0f;
+    const float delta = (2.0f * a) / L;
     const float inv = 1.0f / delta;
     float s = 0.0f;
     const int nel = outer * inner;
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(256) void k_wq_multi_fwd(const long long* __restric
         const int o = e / inner, i = e - o * inner;
         const int64_t k = ((int64_t)o * C + c) * inner + i;
         const float X = rintf(div_by(w[k], delta, inv));
-        const float q = __builtin_amdgcn_fmed3f(X, -128.0f, 127.0f);
+        const float q = __builtin_amdgcn_fmed3f(X, qlo, qhi);
         wq[k] = delta * q;
         if (idx) {   // pointwise conv weight [C][outer*inner == Ci]: codes for the q-GEMMs
             idx[(int64_t)c * nel + e] = (signed char)q;
@@ -108,9 +110,11 @@ __global__ __launch_bounds__(256) void k_wq_multi_bwd(const long long* __restric
     float* gmax = reinterpret_cast<float*>(d[11]);
     const int outer = (int)d[12], C = (int)d[13], inner = (int)d[14];
     const int c = blockIdx.x - (int)d[15];
+    const int n_bits = (int)d[17];
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
     const float lo = qmin[c], hi = qmax[c];
     const float a = fmaxf(fabsf(lo), fabsf(hi));
-    const float delta = (2.0f * a) / 255.0f;
+    const float delta = (2.0f * a) / L;
     const float inv = 1.0f / delta;
     float p = 0.0f;
     const int nel = outer * inner;
@@ -119,8 +123,8 @@ __global__ __launch_bounds__(256) void k_wq_multi_bwd(const long long* __restric
         const int64_t k = ((int64_t)o * C + c) * inner + i;
         const float u = div_by(w[k], delta, inv);
         const float X = rintf(u);
-        const bool inr = (X >= -128.0f) && (X <= 127.0f);
-        const float q = __builtin_amdgcn_fmed3f(X, -128.0f, 127.0f);
+        const bool inr = (X >= qlo) && (X <= qhi);
+        const float q = __builtin_amdgcn_fmed3f(X, qlo, qhi);
         const float gk = gwq[k];
         gw[k] += inr ? div_by(gk * delta, delta, inv) : 0.0f;
         p += gk * (inr ? (q - u) : q);
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void k_wq_multi_bwd(const long long* __restric
     double v[1] = {(double)p};
     block_sum<double, 1>(v, red);
     if (threadIdx.x == 0) {
-        const double D = v[0] * (2.0 / 255.0);
+        const double D = v[0] * (2.0 / (double)L);
         const float al = fabsf(lo), ah = fabsf(hi);
         const double wl = al > ah ? 1.0 : (al == ah ? 0.5 : 0.0);
         const double wh = ah > al ? 1.0 : (al == ah ? 0.5 : 0.0);
@@ -148,6 +152,17 @@ extern "C" int fqss_gacc_flush_multi(const int64_t* table, int n, fqss_stream_t 
     if (n == 0) return FQSS_OK;
     hipLaunchKernelGGL(k_gacc_flush_multi, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, (const long long*)table);
     return launch_status("fqss_gacc_flush_multi");
+}
+
+// The tables live in device memory, so the launches cannot inspect them: the host validates its rows with this before the upload.
+extern "C" int fqss_wq_table_check(const int64_t* host_table, int n) {
+    FQSS_REQUIRE(n >= 0 && (host_table || n == 0), "bad args");
+    for (int i = 0; i < n; ++i) {
+        const int64_t* d = host_table + (int64_t)i * kWqFields;
+        FQSS_REQUIRE(d[17] >= FQSS_WQ_MIN_BITS && d[17] <= FQSS_WQ_MAX_BITS, "descriptor word 17: weight width outside 2..8 bits");
+        FQSS_REQUIRE(d[12] > 0 && d[13] > 0 && d[14] > 0, "descriptor words 12-14: empty weight");
+    }
+    return FQSS_OK;
 }
 
 extern "C" int fqss_wq_multi_fwd(const int64_t* table, int n, int total_channels, fqss_stream_t stream) {

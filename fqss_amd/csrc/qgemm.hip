@@ -1080,15 +1080,16 @@ __global__ __launch_bounds__(512, 1) void k_qwgrad_group(WGroupArgs ga) {
 // per-channel weight codes for the q-GEMMs: idx [Co][Ci], idxT [Ci][Co], dw[Co], rw[Co] (one block per channel)
 __global__ __launch_bounds__(256) void k_wq_codes(const float* __restrict__ w, signed char* __restrict__ idx,
                                                    signed char* __restrict__ idxT, float* dw, float* rw, int Co, int Ci,
-                                                   const float* __restrict__ qmin, const float* __restrict__ qmax) {
+                                                   const float* __restrict__ qmin, const float* __restrict__ qmax, int n_bits) {
     __shared__ float red[4];
     const int co = blockIdx.x;
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
     const float a = fmaxf(fabsf(qmin[co]), fabsf(qmax[co]));
-    const float delta = (2.0f * a) / 255.0f;
+    const float delta = (2.0f * a) / L;
     float s = 0.0f;
     for (int ci = threadIdx.x; ci < Ci; ci += 256) {
         const float X = rintf(w[(int64_t)co * Ci + ci] / delta);
-        const float q = fminf(fmaxf(X, -128.0f), 127.0f);
+        const float q = fminf(fmaxf(X, qlo), qhi);
         idx[(int64_t)co * Ci + ci] = (signed char)q;
         idxT[(int64_t)ci * Co + co] = (signed char)q;
         s += q;   // |sum| <= 512*128 : exact in fp32
@@ -1112,12 +1113,18 @@ static int grad_pieces() {
     return (e != nullptr && e[0] == '2') ? 2 : 3;
 }
 
+extern "C" int fqss_wq_codes_bits(const float* w, int8_t* idx, int8_t* idxT, float* dw, float* rw, int Co, int Ci,
+                                  const float* qmin, const float* qmax, int n_bits, fqss_stream_t stream) {
+    FQSS_REQUIRE(w && idx && idxT && dw && rw && qmin && qmax && Co > 0 && Ci > 0, "bad args");
+    FQSS_REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    hipLaunchKernelGGL(k_wq_codes, dim3((unsigned)Co), dim3(256), 0, (hipStream_t)stream, w, (signed char*)idx,
+                       (signed char*)idxT, dw, rw, Co, Ci, qmin, qmax, n_bits);
+    return launch_status("fqss_wq_codes_bits");
+}
+
 extern "C" int fqss_wq_codes(const float* w, int8_t* idx, int8_t* idxT, float* dw, float* rw, int Co, int Ci,
                              const float* qmin, const float* qmax, fqss_stream_t stream) {
-    FQSS_REQUIRE(w && idx && idxT && dw && rw && qmin && qmax && Co > 0 && Ci > 0, "bad args");
-    hipLaunchKernelGGL(k_wq_codes, dim3((unsigned)Co), dim3(256), 0, (hipStream_t)stream, w, (signed char*)idx,
-                       (signed char*)idxT, dw, rw, Co, Ci, qmin, qmax);
-    return launch_status("fqss_wq_codes");
+    return fqss_wq_codes_bits(w, idx, idxT, dw, rw, Co, Ci, qmin, qmax, 8, stream);
 }
 
 struct QpwQuant {   // optional fused output quantizer of fqss_qpw_fwdq

@@ -12,6 +12,8 @@ ACT_GELU = 3          # nn.GELU (erf form) in front of a quantizer: fqss_actq_fw
 ACT_POST_RELU = 4     # a ReLU BEHIND the quantizer, relu(fq(x)): fqss_actq_fwd / fqss_actq_bwd only (qat_layers.fq_node(post_relu=True))
 
 GACC_DOUBLES = 2048 * 3   # FQSS_GACC_SLOTS x (dmin, dmax, dslope)
+WQ_DESC_WORDS = 18        # FQSS_WQ_DESC_WORDS: int64 words per weight descriptor (word 17 = the weight's width in bits)
+WQ_BITS = (2, 8)          # FQSS_WQ_MIN_BITS, FQSS_WQ_MAX_BITS
 USE_X3 = True            # route plain fp32 pointwise convs through the bf16 3x3-split GEMM
 LD_ALIGN = 16  # row stride of activation buffers is padded to 16 floats (64 B) -> 16-B/lane path
 
@@ -269,17 +271,18 @@ def wq_observe(w, axis, qmin, qmax):
     _lib.call("fqss_wq_observe", _p(w.contiguous()), o, c, i, _p(qmin), _p(qmax), _stream())
 
 
-def wq_fwd(w, axis, qmin, qmax, want_idx=False):
+def wq_fwd(w, axis, qmin, qmax, want_idx=False, n_bits=8):
+    """n_bits: the weight width, 2..8 (codes in [-2^(n-1), 2^(n-1) - 1], always stored as int8)"""
     _need_gpu(w, qmin, qmax)
     w = w.contiguous()
     o, c, i = _w_layout(w.shape, axis)
     wq = torch.empty_like(w)
     idx = torch.empty(w.shape, device=w.device, dtype=torch.int8) if want_idx else None
-    _lib.call("fqss_wq_fwd", _p(w), _p(wq), _p(idx), o, c, i, _p(qmin), _p(qmax), _stream())
+    _lib.call("fqss_wq_fwd_bits", _p(w), _p(wq), _p(idx), o, c, i, _p(qmin), _p(qmax), int(n_bits), _stream())
     return (wq, idx) if want_idx else wq
 
 
-def wq_bwd(w, g, axis, qmin, qmax, out=None):
+def wq_bwd(w, g, axis, qmin, qmax, out=None, n_bits=8):
     """out=None: fresh (gw, gmin, gmax); out=(gw, gmin, gmax): accumulate (+=) into the given buffers"""
     _need_gpu(w, g, qmin, qmax)
     w, g = w.contiguous(), g.contiguous()
@@ -289,12 +292,18 @@ def wq_bwd(w, g, axis, qmin, qmax, out=None):
     else:
         (gw, gmin, gmax), acc = out, 1
         assert gw.is_contiguous() and gmin.is_contiguous() and gmax.is_contiguous()
-    _lib.call("fqss_wq_bwd", _p(w), _p(g), _p(gw), _p(gmin), _p(gmax), o, c, i, _p(qmin), _p(qmax), acc, _stream())
+    _lib.call("fqss_wq_bwd_bits", _p(w), _p(g), _p(gw), _p(gmin), _p(gmax), o, c, i, _p(qmin), _p(qmax), acc, int(n_bits), _stream())
     return gw, gmin, gmax
 
 
 def gacc_flush_multi(table):
     _lib.call("fqss_gacc_flush_multi", _p(table), table.shape[0], _stream())
+
+
+def wq_table_check(rows):
+    """validate the host rows of a weight descriptor table (FQSS_WQ_DESC_WORDS int64 words each) before they are uploaded"""
+    t = torch.tensor(rows, dtype=torch.int64).reshape(-1, WQ_DESC_WORDS).contiguous()
+    _lib.call("fqss_wq_table_check", t.data_ptr(), t.shape[0])
 
 
 def wq_multi_fwd(table, total_channels):
@@ -401,7 +410,7 @@ class WCodes:
     __slots__ = ("idx", "idxT", "dw", "rw", "Co", "Ci")
 
 
-def wq_codes(w, qmin, qmax):
+def wq_codes(w, qmin, qmax, n_bits=8):
     _need_gpu(w, qmin, qmax)
     Co, Ci = w.shape[0], w.shape[1]
     assert w.numel() == Co * Ci and w.is_contiguous()
@@ -411,7 +420,7 @@ def wq_codes(w, qmin, qmax):
     c.idxT = torch.empty(Ci, Co, device=w.device, dtype=torch.int8)
     c.dw = torch.empty(Co, device=w.device, dtype=torch.float32)
     c.rw = torch.empty(Co, device=w.device, dtype=torch.float32)
-    _lib.call("fqss_wq_codes", _p(w), _p(c.idx), _p(c.idxT), _p(c.dw), _p(c.rw), Co, Ci, _p(qmin), _p(qmax), _stream())
+    _lib.call("fqss_wq_codes_bits", _p(w), _p(c.idx), _p(c.idxT), _p(c.dw), _p(c.rw), Co, Ci, _p(qmin), _p(qmax), int(n_bits), _stream())
     return c
 
 

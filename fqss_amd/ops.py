@@ -1056,10 +1056,10 @@ class WeightFq(Function):
     """w_q = per-channel symmetric fake-quant of w  -- GradientWeightFakeQuantize (quantizing call)"""
 
     @staticmethod
-    def forward(ctx, w, qmin, qmax, axis, owner, w_param):
-        wq = K.wq_fwd(w, axis, qmin, qmax)
+    def forward(ctx, w, qmin, qmax, axis, owner, w_param, n_bits=8):
+        wq = K.wq_fwd(w, axis, qmin, qmax, n_bits=n_bits)
         ctx.save_for_backward(w, qmin, qmax)
-        ctx.axis, ctx.owner, ctx.w_param = axis, owner, w_param
+        ctx.axis, ctx.owner, ctx.w_param, ctx.n_bits = axis, owner, w_param, n_bits
         return wq
 
     @staticmethod
@@ -1068,8 +1068,8 @@ class WeightFq(Function):
         gw, d0 = _grad_buf(ctx.w_param, w)
         gmn, d1 = _grad_buf(ctx.owner.min_range if ctx.owner is not None else None, qmin)
         gmx, d2 = _grad_buf(ctx.owner.max_range if ctx.owner is not None else None, qmax)
-        K.wq_bwd(w, g, ctx.axis, qmin, qmax, out=(gw, gmn, gmx))
-        return (None if d0 else gw), (None if d1 else gmn), (None if d2 else gmx), None, None, None
+        K.wq_bwd(w, g, ctx.axis, qmin, qmax, out=(gw, gmn, gmx), n_bits=ctx.n_bits)
+        return (None if d0 else gw), (None if d1 else gmn), (None if d2 else gmx), None, None, None, None
 
 
 class Combine2(Function):

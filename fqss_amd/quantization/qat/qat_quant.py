@@ -4,14 +4,23 @@ Same public names, constructor signatures, parameter names/shapes (=> same state
 host-side state (`n_iter`, `observer_mode`, `max_observations`, `alpha`) as the reference's
 quantization/qat/qat_quant.py; the arithmetic runs in the HIP kernels of csrc/fq.hip:
 
-  linear_quantize                    qat_quant.py:125-147  -> fqss_actq_fwd/bwd, fqss_wq_fwd/bwd
+  linear_quantize                    qat_quant.py:125-147  -> fqss_actq_fwd/bwd, fqss_wq_fwd_bits/bwd_bits
   GradientActivationFakeQuantize     qat_quant.py:206-242  -> observer: fqss_actq_fwd(OBSERVE)+fqss_observer_ema
-  GradientWeightFakeQuantize         qat_quant.py:350-381  -> fqss_wq_observe / fqss_wq_fwd / fqss_wq_bwd
+  GradientWeightFakeQuantize         qat_quant.py:350-381  -> fqss_wq_observe / fqss_wq_fwd_bits / fqss_wq_bwd_bits
+
+Supported widths:
+  * weights (`weight_n_bits`, GradientWeightFakeQuantize, linear_quantize(sym=True)): every integer from 2 to 8.  Width n
+    quantizes to L = 2^n - 1 levels, delta = 2 max(|min|, |max|) / L, codes clip(rint(w / delta), -2^(n-1), 2^(n-1) - 1).  The codes
+    stay int8 images, so the q-GEMMs, row GEMMs and grouped weight gradients downstream run unchanged; one model may mix widths.
+    Width 1 (a degenerate, one-sided grid) and widths above 8 (no int8 image) raise NotImplementedError.
+  * activations (`act_n_bits`, `in_act_n_bits`, `out_act_n_bits`): 8 only.  The fused kernels carry the 8-bit activation grid as a
+    compile-time constant (uint8 code images, /255); other widths raise NotImplementedError.
 
 Deliberate differences (documented in DESIGN.md):
   * no host syncs: the reference does `.item()` + `assert max >= min` on every training forward
     (qat_quant.py:235-238); here nothing reads device memory from the host.
-  * 8-bit only (every shipped config); other widths raise NotImplementedError.
+  * asymmetric (sym=False on weights, sym=True on activations) and scale_grad=True quantizers raise NotImplementedError: no
+    FQSS config reaches them.
 """
 import torch
 import torch.nn as nn
@@ -25,9 +34,20 @@ def ops_dp_qrow():
     return ops_dp.QROW
 
 
-def _check_bits(n_bits):
+WEIGHT_BITS = tuple(range(K.WQ_BITS[0], K.WQ_BITS[1] + 1))
+
+
+def _check_weight_bits(n_bits):
+    if isinstance(n_bits, bool) or n_bits not in WEIGHT_BITS or int(n_bits) != n_bits:
+        raise NotImplementedError(f"weight quantizers support n_bits = {WEIGHT_BITS[0]} to {WEIGHT_BITS[-1]} (integers), got {n_bits!r}: "
+                                  "1 bit has a degenerate one-sided grid, more than 8 bits do not fit the int8 code images")
+    return int(n_bits)
+
+
+def _check_act_bits(n_bits):
     if n_bits != 8:
-        raise NotImplementedError("fqss_amd kernels implement the 8-bit quantizers of the shipped FQSS configs")
+        raise NotImplementedError(f"activation quantizers support n_bits = 8 only, got {n_bits!r}: the fused fqss_amd kernels carry "
+                                  "the 8-bit activation grid as a constant (weights: 2 to 8 bits)")
 
 
 # ---- public STE helpers (qat_quant.py:88-107 of the reference): `(f(x) - x).detach() + x` -> value f(x), gradient of x ------------
@@ -71,13 +91,17 @@ def clip_ste(x, min_val=-1.0, max_val=1.0):
 
 def linear_quantize(x, min_range, max_range, n_bits, sign=True, sym=False, scale_grad=False):
     """Functional form (differentiable w.r.t. x, min_range, max_range) on device tensors."""
-    _check_bits(n_bits)
     if scale_grad:
         raise NotImplementedError("scale_grad=True is not used by any FQSS config")
     if sym:
+        n_bits = _check_weight_bits(n_bits)
         shape = tuple(min_range.shape)
-        axis = next((i for i, s in enumerate(shape) if s != 1), 0)
-        return ops.WeightFq.apply(x, min_range, max_range, axis, None, None)
+        axis = next((i for i, s in enumerate(shape) if s != 1), None)
+        if axis is None:        # one range for the whole tensor: a single channel over the flattened weight
+            y = ops.WeightFq.apply(x.reshape(1, -1), min_range.reshape(1, 1), max_range.reshape(1, 1), 0, None, None, n_bits)
+            return y.reshape(x.shape)
+        return ops.WeightFq.apply(x, min_range, max_range, axis, None, None, n_bits)
+    _check_act_bits(n_bits)
     q = ops.QCtx(ops.Q_QUANT, min_range, max_range, None, None, None)
     return ops.NlActQ.apply(x, None, min_range, max_range, ops.ACT_NONE, q, None)
 
@@ -87,7 +111,7 @@ class GradientActivationFakeQuantize(nn.Module):
 
     def __init__(self, gradient_based, n_bits=8, sym=False, scale_grad=False):
         super().__init__()
-        _check_bits(n_bits)
+        _check_act_bits(n_bits)
         if sym or scale_grad:
             raise NotImplementedError("sym/scale_grad activation quantizers are not reachable from the FQSS configs")
         self.n_bits = n_bits
@@ -130,11 +154,11 @@ class GradientActivationFakeQuantize(nn.Module):
 
 
 class GradientWeightFakeQuantize(nn.Module):
-    """Per-output-channel symmetric weight quantizer; the first call only records amax/amin."""
+    """Per-output-channel symmetric weight quantizer at n_bits = 2 to 8; the first call only records amax/amin."""
 
     def __init__(self, gradient_based, weight_shape, n_bits=8, sym=True, ch_out_idx=0, scale_grad=False):
         super().__init__()
-        _check_bits(n_bits)
+        n_bits = _check_weight_bits(n_bits)
         if not sym or scale_grad:
             raise NotImplementedError("asymmetric/scale_grad weight quantizers are not reachable from the FQSS configs")
         self.n_bits = n_bits
@@ -159,13 +183,13 @@ class GradientWeightFakeQuantize(nn.Module):
         pre = getattr(x, "_fqss_wq", None)
         if pre is not None and ops.DEFER is not None:
             return pre        # already fake-quantized this step by fqss_wq_multi_fwd (runtime.QuantTables)
-        wq = ops.WeightFq.apply(x, self.min_range, self.max_range, self.axis, self, w_param if w_param is not None else x)
+        wq = ops.WeightFq.apply(x, self.min_range, self.max_range, self.axis, self, w_param if w_param is not None else x, self.n_bits)
         if self.axis == 0 and x.dim() == 3 and x.shape[2] == 1 and K.q_eligible(x.shape[1], x.shape[0]):
             # pointwise-conv weight: also hand its int8 codes to the bf16-MFMA q-GEMMs (csrc/qgemm.hip)
-            wq._fqss_wcodes = K.wq_codes(x.detach(), self.min_range.detach(), self.max_range.detach())
+            wq._fqss_wcodes = K.wq_codes(x.detach(), self.min_range.detach(), self.max_range.detach(), n_bits=self.n_bits)
         elif self.axis == 0 and x.dim() == 2 and K.qrow_eligible(x.shape[1]) and ops_dp_qrow():
             # row-major linear weight (LinearQ, attention projections, LSTM input projection): codes for csrc/qrow.hip
-            wq._fqss_wcodes = K.wq_codes(x.detach(), self.min_range.detach(), self.max_range.detach())
+            wq._fqss_wcodes = K.wq_codes(x.detach(), self.min_range.detach(), self.max_range.detach(), n_bits=self.n_bits)
         return wq
 
 

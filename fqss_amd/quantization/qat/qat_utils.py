@@ -162,7 +162,8 @@ def replace_dym_activation_quantizer(model, module_to_replace, module):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Integer checkpoint (the reference only sketches the export: qat_utils.py:334-351 swaps quantizers for their
 # torch affine twins and keeps fp32 weights).  Here the trained model is STORED as what a W8A8 deployment loads: int8 weight codes +
-# per-channel steps on the training grid (delta = 2 max(|min|, |max|) / 255, codes in [-128, 127]: qat_quant.py:126-135), every
+# per-channel steps on the training grid (delta = 2 max(|min|, |max|) / (2^n - 1), codes in [-2^(n-1), 2^(n-1) - 1], n = the
+# quantizer's weight_n_bits: [-128, 127] at 8 bits; qat_quant.py:126-135), every
 # activation quantizer's range (the 8-bit grid delta = (max - min) / 255) next to its torch affine form (scale, zero point), and
 # the few float tensors that are not quantized (biases, norms, PReLU slopes).  Loading rebuilds W_q = delta * code -- bit for bit the
 # weight the QAT forward multiplies with -- so the eval output of a model restored from the integer file equals the original's.
@@ -212,9 +213,9 @@ def integer_state(model):
     for wqm, w, pname in weight_quantizer_owners(model):
         if wqm.observer_mode:
             raise ValueError(f"{pname}: its weight observer never ran (nothing to export before the first training forward)")
-        wq, codes = K.wq_fwd(w.detach(), wqm.axis, wqm.min_range.detach(), wqm.max_range.detach(), want_idx=True)
+        wq, codes = K.wq_fwd(w.detach(), wqm.axis, wqm.min_range.detach(), wqm.max_range.detach(), want_idx=True, n_bits=wqm.n_bits)
         a = torch.maximum(wqm.min_range.detach().abs(), wqm.max_range.detach().abs())
-        weights[pname] = {"codes": codes.cpu(), "delta": ((2.0 * a) / 255.0).flatten().cpu(), "axis": wqm.axis,
+        weights[pname] = {"codes": codes.cpu(), "delta": ((2.0 * a) / float(2 ** wqm.n_bits - 1)).flatten().cpu(), "axis": wqm.axis,
                           "min_range": wqm.min_range.detach().cpu(), "max_range": wqm.max_range.detach().cpu(), "quantizer": qname[id(wqm)]}
         covered |= {pname, qname[id(wqm)] + ".min_range", qname[id(wqm)] + ".max_range"}
     acts = {}

@@ -310,7 +310,7 @@ class QuantTables:
             rows.append([w.data_ptr(), wq.data_ptr(), wc.idx.data_ptr() if coded else 0, idxT_ptr if coded else 0,
                          wc.dw.data_ptr() if coded else 0, wc.rw.data_ptr() if coded else 0, wqm.min_range.data_ptr(),
                          wqm.max_range.data_ptr(), gwq.data_ptr(), w.grad.data_ptr(), wqm.min_range.grad.data_ptr(),
-                         wqm.max_range.grad.data_ptr(), outer, C, inner, blk, ldT])
+                         wqm.max_range.grad.data_ptr(), outer, C, inner, blk, ldT, int(wqm.n_bits)])
             wq._fqss_gwq = gwq
             if pw:
                 wq._fqss_wcodes = wc
@@ -321,6 +321,7 @@ class QuantTables:
             off += (w.numel() + 63) // 64 * 64
             blk += C
         assert pending is None
+        K.wq_table_check(rows)      # the launches cannot read the device table: widths (word 17) and extents are checked here
         self.wq_table = torch.tensor(rows, dtype=torch.int64, device=dev)
         self.total_channels = blk
         # grouped, atomics-free weight gradients of the quantized 1x1 convolutions (csrc/qgemm.hip k_qwgrad_group); FQSS_GROUP_WGRAD=0:

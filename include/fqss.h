@@ -119,27 +119,42 @@ int fqss_minmax(const float* x, int64_t rows, int64_t cols, int64_t ld, uint32_t
  * K2  per-channel symmetric weight fake-quant.  Weight layout [outer][C][inner]:
  *     ch_out_idx=0 -> outer=1 (Conv1d), ch_out_idx=1 -> outer=shape[0] (ConvTranspose1d).
  * replaces: qat_quant.py:126-135, :372-381 and their autograd
+ * Width n_bits in [FQSS_WQ_MIN_BITS, FQSS_WQ_MAX_BITS] (else FQSS_EINVAL): L = 2^n - 1, delta = 2 max(|min|, |max|) / L,
+ * codes clip(rint(w / delta), -2^(n-1), 2^(n-1) - 1), always stored as int8.  fqss_wq_fwd / fqss_wq_bwd are the *_bits forms
+ * at n_bits = 8.
  * ------------------------------------------------------------------------------------------- */
+#define FQSS_WQ_MIN_BITS 2
+#define FQSS_WQ_MAX_BITS 8
 int fqss_wq_observe(const float* w, int64_t outer, int64_t C, int64_t inner, float* qmin,
                     float* qmax, fqss_stream_t stream);
 int fqss_wq_fwd(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner,
                 const float* qmin, const float* qmax, fqss_stream_t stream);
+int fqss_wq_fwd_bits(const float* w, float* wq, int8_t* idx, int64_t outer, int64_t C, int64_t inner,
+                     const float* qmin, const float* qmax, int n_bits, fqss_stream_t stream);
 /* accumulate=0: gw = ; gmin[C] = ; gmax[C] =      accumulate=1: all three are "+=" */
 int fqss_wq_bwd(const float* w, const float* g, float* gw, float* gmin, float* gmax,
                 int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax,
                 int accumulate, fqss_stream_t stream);
+int fqss_wq_bwd_bits(const float* w, const float* g, float* gw, float* gmin, float* gmax,
+                     int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax,
+                     int accumulate, int n_bits, fqss_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * multi-tensor forms of the per-quantizer small work (csrc/multi.hip): ONE launch each, driven by a
  * device table of int64 words the host builds once.
  *   flush table  : n x 4  = {gacc, gmin, gmax, gslope} addresses (0 = absent)
  *   weight table : n x FQSS_WQ_DESC_WORDS = {w, wq, idx, idxT, dw, rw, qmin, qmax, gwq, gw, gmin, gmax, outer, C,
- *                  inner, first_block, ldT}; entries sorted by first_block, one workgroup per output channel;
+ *                  inner, first_block, ldT, n_bits}; entries sorted by first_block, one workgroup per output channel;
  *                  idx/idxT/dw/rw only for pointwise-conv weights (0 otherwise); ldT = row stride of idxT
  *                  (C, or the summed C of layers whose codes are concatenated for the paired q-GEMMs);
+ *                  word 17, n_bits: this weight's width in [FQSS_WQ_MIN_BITS, FQSS_WQ_MAX_BITS] -- per descriptor, so one
+ *                  table may mix widths (the members of a pair included: each has its own descriptor);
  *                  bwd: gw += STE(gwq), gmin/gmax += range gradients  (gwq = accumulated dL/dW_q)
+ * The tables are device memory, which the launching entry points do not read: fqss_wq_table_check validates the HOST copy of a
+ * weight table (n rows) before it is uploaded and returns FQSS_EINVAL for a width outside the range or an empty weight.
  * ------------------------------------------------------------------------------------------- */
-#define FQSS_WQ_DESC_WORDS 17
+#define FQSS_WQ_DESC_WORDS 18
+int fqss_wq_table_check(const int64_t* host_table, int n);
 int fqss_gacc_flush_multi(const int64_t* table, int n, fqss_stream_t stream);
 int fqss_wq_multi_fwd(const int64_t* table, int n, int total_channels, fqss_stream_t stream);
 int fqss_wq_multi_bwd(const int64_t* table, int n, int total_channels, fqss_stream_t stream);
@@ -231,6 +246,9 @@ int fqss_pwconv_bwd_w(const float* gz, const float* x, float* gw, int B, int Ci,
  * ------------------------------------------------------------------------------------------- */
 int fqss_wq_codes(const float* w, int8_t* idx, int8_t* idxT, float* dw, float* rw, int Co, int Ci,
                   const float* qmin, const float* qmax, fqss_stream_t stream);
+/* the same at width n_bits (fqss_wq_fwd_bits' grid; fqss_wq_codes is n_bits = 8): |codes| <= 2^(n-1), exact on the bf16 matrix cores */
+int fqss_wq_codes_bits(const float* w, int8_t* idx, int8_t* idxT, float* dw, float* rw, int Co, int Ci,
+                       const float* qmin, const float* qmax, int n_bits, fqss_stream_t stream);
 int fqss_qpw_fwd(const uint8_t* xc, const int8_t* wi, const float* dw, const float* rw,
                  const float* bias, const float* qmin_x, const float* qmax_x, float* z, int B, int Ci,
                  int Co, int M, int64_t ld_xc, int64_t ld_z, fqss_stream_t stream);
