@@ -194,6 +194,8 @@ _PROTOS = {
     "fqss_sisnr_matrix": [P, P, P, P, P, I32, I64, I64, I64, P],
     "fqss_infer_ola": [P, P, P, P, I32, I32, I64, I64, I64, I64, I64, P],
     "fqss_infer_normalize": [P, P, I64, I64, I64, P],
+    "fqss_sdr_ws_doubles": [I32, I64, I32],
+    "fqss_sdr": [P, P, P, I64, P, I32, I64, I64, I64, I32, I32, F64, P],
     "fqss_fq_affine": [P, P, P, I64, I64, I64, P, P, I32, I32, P],
     "fqss_snr_mix": [P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, I32, P],
     "fqss_resample_fir": [P, P, P, I64, I64, I64, I64, I64, I32, I32, I32, P],
@@ -209,7 +211,8 @@ _PROTOS = {
     "fqss_gln_fq_fwd": [P, P, P, P, F32, P, P, P, P, P, C.c_size_t, P, I32, P],
     "fqss_tgemm_desc": [P, P],
 }
-_RESTYPE = {"fqss_last_error": C.c_char_p, "fqss_workspace_bytes": C.c_int64, "fqss_qpw_bwd_w_group_ws": C.c_int64}
+_RESTYPE = {"fqss_last_error": C.c_char_p, "fqss_workspace_bytes": C.c_int64, "fqss_qpw_bwd_w_group_ws": C.c_int64,
+             "fqss_sdr_ws_doubles": C.c_int64}
 
 DT_F32, DT_U8, DT_I8, DT_F64, DT_U16, DT_I64 = range(6)
 

@@ -1,7 +1,8 @@
 // fqss_cpu.cpp -- the CPU backend behind include/fqss.h for cfg 1 of BASELINE.json ("convtasnet_2spks_8k.yaml on asteroid env, CPU,
 // batch 2, 1 s ... plumbing, no GPU"; reference train.py:31: device = "cpu" if use_cpu).  Plain C++ (g++, OpenMP), host pointers, the
 // `stream` argument is ignored, every call is synchronous.  It serves the entry points the UN-FUSED ConvTasNet QAT step uses (the
-// per-layer kernels that the G1 layer fixtures pin: KDTrainStep(coded=False, batched_quantizers=False) with the module-path teacher);
+// per-layer kernels that the G1 layer fixtures pin: KDTrainStep(coded=False, batched_quantizers=False) with the module-path teacher)
+// and the SDR of the evaluation side (fqss_sdr);
 // anything else is absent from this library and fqss_amd/_lib.py raises.  Arithmetic: the same op sequences as the HIP kernels
 // (fp32, one IEEE operation per operator: built with -ffp-contract=off; IEEE division; round-half-even), reductions in fp64.
 // NOT the oracle: oracle/ is test infrastructure and is never loaded by the product; this file is product code selected by --use_cpu.
@@ -813,6 +814,79 @@ int fqss_resample_fir(const float* x, const float* h, float* y, int64_t rows, in
             }
             y[r * ld_y + o] = acc;
         }
+    return FQSS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ signal-to-distortion ratio
+// include/fqss.h, fqss_sdr: the definition in straight fp64 loops (means subtracted and signals normalised first, direct lag sums,
+// Levinson-Durbin); the workspace has the HIP library's size rule and is not used
+int64_t fqss_sdr_ws_doubles(int P, int64_t L, int filter_length) {
+    if (P < 1 || L < 1 || filter_length < 1 || filter_length > 512) return 0;
+    return (int64_t)P * ((L + 1023) / 1024) * (2 * (int64_t)filter_length + 4);
+}
+
+int fqss_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t L, int64_t ld_e, int64_t ld_r,
+             int filter_length, int zero_mean, double load_diag, fqss_stream_t) {
+    REQUIRE(est && ref && ws && db, "null pointer");
+    REQUIRE(P >= 1 && P <= 65535 && L >= 1 && ld_e >= L && ld_r >= L, "bad shape (1 <= P <= 65535, L >= 1, ld >= L)");
+    REQUIRE(filter_length >= 1 && filter_length <= 512, "filter_length outside 1..512");
+    REQUIRE(ws_doubles >= fqss_sdr_ws_doubles(P, L, filter_length), "workspace shorter than fqss_sdr_ws_doubles");
+    const int F = filter_length;
+    for (int p = 0; p < P; ++p) {
+        std::vector<double> t(L), e(L), r(F, 0.0), b(F, 0.0), a(F, 0.0), an(F, 0.0), x(F, 0.0);
+        double st = 0.0, se = 0.0;
+        for (int64_t i = 0; i < L; ++i) {
+            t[i] = ref[p * ld_r + i];
+            e[i] = est[p * ld_e + i];
+            st += t[i];
+            se += e[i];
+        }
+        const double mt = zero_mean ? st / (double)L : 0.0, me = zero_mean ? se / (double)L : 0.0;
+        double tt = 0.0, ee = 0.0;
+        for (int64_t i = 0; i < L; ++i) {
+            t[i] -= mt;
+            e[i] -= me;
+            tt += t[i] * t[i];
+            ee += e[i] * e[i];
+        }
+        const double nt = fmax(sqrt(tt), 1e-6), ne = fmax(sqrt(ee), 1e-6);
+        for (int64_t i = 0; i < L; ++i) {
+            t[i] /= nt;
+            e[i] /= ne;
+        }
+#pragma omp parallel for schedule(static)
+        for (int k = 0; k < F; ++k) {
+            double rk = 0.0, bk = 0.0;
+            for (int64_t i = 0; i + k < L; ++i) {
+                rk += t[i] * t[i + k];
+                bk += t[i] * e[i + k];
+            }
+            r[k] = rk;
+            b[k] = bk;
+        }
+        if (load_diag >= 0.0) r[0] += load_diag;      // (a negative or NaN load_diag: none)
+        double E = r[0];
+        bool ok = E > 0.0;
+        a[0] = 1.0;
+        x[0] = b[0] / E;
+        for (int m = 1; m < F; ++m) {
+            double acc = 0.0, q = 0.0;
+            for (int i = 0; i < m; ++i) {
+                acc += a[i] * r[m - i];
+                q += x[i] * r[m - i];
+            }
+            const double k = -acc / E;
+            E = E * (1.0 - k * k);
+            ok = ok && E > 0.0;
+            const double lam = (b[m] - q) / E;
+            for (int i = 0; i <= m; ++i) an[i] = a[i] + k * a[m - i];
+            a.swap(an);
+            for (int i = 0; i <= m; ++i) x[i] += lam * a[m - i];
+        }
+        double coh = 0.0;
+        for (int i = 0; i < F; ++i) coh += b[i] * x[i];
+        db[p] = (ok && std::isfinite(coh)) ? 10.0 * log10(coh / (1.0 - coh)) : (double)NAN;
+    }
     return FQSS_OK;
 }
 

@@ -110,6 +110,27 @@ int main() {
     const float p7 = p[7];
     CHECK(fqss_adam_clip(p.data(), gp.data(), m1.data(), v1.data(), n, &ss, 5.0f, 1.0f, 1e-3f, 0.9f, 0.999f, 1e-8f, &stp, t0.data(), &gn, nullptr) == 0);
     CHECK(stp == 1 && p[7] == p7 && fabs(gn - sqrt(ss)) < 1e-3);
+    // signal-to-distortion ratio: pitched rows, a signal shorter than the filter, a silent target, refused arguments
+    {
+        const int P = 3, ldp = 310;
+        const int64_t Ls = 300;
+        auto pe = rnd((size_t)P * ldp), pr = rnd((size_t)P * ldp);
+        for (int64_t i = 0; i < Ls; ++i) {
+            pe[i] = pr[i] + 0.1f * pe[i];
+            pr[ldp + i] = 0.0f;
+        }
+        for (int F : {1, 7, 512}) {
+            std::vector<double> wsd((size_t)fqss_sdr_ws_doubles(P, Ls, F)), dbv(P, 0.0);
+            CHECK(wsd.size() == (size_t)P * (2 * F + 4));
+            CHECK(fqss_sdr(pe.data(), pr.data(), wsd.data(), (int64_t)wsd.size(), dbv.data(), P, Ls, ldp, ldp, F, F == 7, F == 7 ? 1e-3 : -1.0, nullptr) == 0);
+            CHECK(std::isfinite(dbv[0]) && dbv[0] > 10.0 && std::isnan(dbv[1]) == (F != 7) && std::isfinite(dbv[2]));
+            CHECK(fqss_sdr(pe.data(), pr.data(), wsd.data(), (int64_t)wsd.size() - 1, dbv.data(), P, Ls, ldp, ldp, F, 0, -1.0, nullptr) == FQSS_EINVAL);
+        }
+        std::vector<double> wsd(4096), dbv(P);
+        CHECK(fqss_sdr(pe.data(), pr.data(), wsd.data(), 4096, dbv.data(), P, Ls, ldp, ldp, 513, 0, -1.0, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_sdr(pe.data(), pr.data(), wsd.data(), 4096, dbv.data(), P, Ls, Ls - 1, ldp, 8, 0, -1.0, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_sdr_ws_doubles(P, 0, 8) == 0);
+    }
     CHECK(fqss_version() == FQSS_VERSION);
     printf("selftest ok\n");
     return 0;

@@ -2641,6 +2641,21 @@ def sisnr_matrix(est, ref, want_map=False):
     return (db, mp) if want_map else db
 
 
+def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):
+    """est, ref [P, L] (rows may be pitched views) -> SDR in dB of each (estimate, target) pair, fp64 [P]: torchmetrics'
+    SignalDistortionRatio (fast_bss_eval) restated, see fqss_sdr in include/fqss.h; NaN for a silent or degenerate target"""
+    _need_gpu(est, ref)
+    est, P, L, ld_e = as_rowmat(est)
+    ref, P2, L2, ld_r = as_rowmat(ref)
+    assert (P, L) == (P2, L2), "sdr: shape mismatch"
+    n_ws = _lib.query("fqss_sdr_ws_doubles", P, L, int(filter_length))
+    ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
+    db = torch.empty(P, device=est.device, dtype=torch.float64)
+    _lib.call("fqss_sdr", _p(est), _p(ref), _p(ws), n_ws, _p(db), P, L, ld_e, ld_r, int(filter_length), 1 if zero_mean else 0,
+              -1.0 if load_diag is None else float(load_diag), _stream())
+    return db
+
+
 def infer_ola(chunk, mp, out, sum_weight, start, n, seg):
     """out[d, c, start:start+n] += w * sign_d * chunk[src_d, c, :n]; sum_weight[start:start+n] += w  (triangular w over `seg`)"""
     _need_gpu(chunk, out, sum_weight)

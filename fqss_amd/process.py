@@ -1,8 +1,9 @@
 """8-bit input splitter / output combiner on MI355X (reference: process.py:10-52).
 
 `preprocess` = global max-normalise + MSB/LSB floor-quantised channels (HIP: fqss_minmax + fqss_splitter2),
-`postprocess` = `x0 + x1 * 2^-8` (HIP: fqss_axpby).  The evaluation helpers of the reference's process.py
-(torchmetrics SI-SNR/SDR/STOI, chunked overlap-add inference) are the "next" rows of SURVEY.md §8(f).
+`postprocess` = `x0 + x1 * 2^-8` (HIP: fqss_axpby).  The evaluation helpers of the reference's process.py run on the device too:
+chunked overlap-add inference with per-chunk source re-ordering, SI-SNR (fqss_sisnr_matrix) and SDR (fqss_sdr) of
+`metric_evaluation`.  STOI is the one metric left out (pystoi is third party and absent: reported as NaN).
 """
 import torch
 
@@ -103,11 +104,32 @@ def model_infer(model, mix, n_srcs=1, segment=None, overlap=0.25, device="cuda",
     return out
 
 
-def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000):
-    """mean over sources of the best-match SI-SNR (process.py:127-154).  SDR (fast_bss_eval) and STOI (pystoi) are third-party CPU
-    metrics outside the hot path: reported as NaN"""
-    db = K.sisnr_matrix(sep_waveform.reshape(clean_waveforms.shape[0], -1), clean_waveforms.reshape(clean_waveforms.shape[0], -1))
-    return db.max(dim=1).values.mean().item(), float("nan"), float("nan")
+def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):
+    """SDR in dB between matching rows of est / ref [..., L] (torchmetrics' SignalDistortionRatio with its defaults, third party: the
+    fast_bss_eval definition restated -- both signals normalised, `filter_length` lags of auto- and cross-correlation, a Toeplitz solve;
+    process.py:145).  Leading dimensions are flattened to pairs; returns fp64 [pairs] on the device, NaN where the target is silent."""
+    return K.sdr(est.reshape(-1, est.shape[-1]), ref.reshape(-1, ref.shape[-1]), filter_length=filter_length, zero_mean=zero_mean,
+                 load_diag=load_diag)
+
+
+def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000, with_sdr=True):
+    """(SI-SNR, SDR, STOI) averaged over the sources (process.py:127-154): every estimate is paired with the target of its best SI-SNR
+    (first maximum) and both metrics are taken on that pair.  The pairing stays on the device (first-maximum index + gather) and all
+    pairs go through one fqss_sdr launch.  A silent matched target makes that pair's SDR, and so the mean, NaN, as numpy.mean does in
+    the reference.  with_sdr=False leaves the SDR slot NaN (val.py's mixture baseline uses the SI-SNR slot only).  STOI (pystoi: its
+    own resampler and band matrices, third party and absent) is reported as NaN."""
+    S = clean_waveforms.shape[0]
+    est, clean = sep_waveform.reshape(S, -1), clean_waveforms.reshape(S, -1)
+    db = K.sisnr_matrix(est, clean)
+    best = db.max(dim=1, keepdim=True).values
+    if not with_sdr:
+        return best.mean().item(), float("nan"), float("nan")
+    cols = torch.arange(S, device=db.device).expand(S, S)
+    first = torch.where(db == best, cols, S).min(dim=1).values          # the first maximum, as the reference's strict `>` scan
+    first = torch.where(first < S, first, 0)                            # (a row of NaN: the scan keeps index 0)
+    sdr_db = K.sdr(est, clean[first])
+    sisnr, sdr_mean = torch.stack([best.mean().double(), sdr_db.mean()]).tolist()
+    return sisnr, sdr_mean, float("nan")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """`val.py -y cfg.yaml` (reference: val.py:17-25, 59-92, 184-226): load the quantized model, run `model_infer` over the evaluation
-set and report SI-SDR and its improvement over the unprocessed mixture.  `dataset_cfg.name: librimix` walks `testing_cfg.test_dir`
-as val.py:28-92 does (mix_clean | mix_both | mix_single, s1..s3; whole utterances, resampled on the device); `synthetic` evaluates
-seeded two-speaker mixtures.  SDR (fast_bss_eval) and STOI (pystoi) are third-party CPU metrics: printed as nan.  MUSDB needs the
-`musdb` package (absent): refused."""
+set and report SI-SDR, its improvement over the unprocessed mixture, and SDR (fqss_sdr: torchmetrics' SignalDistortionRatio
+restated).  `dataset_cfg.name: librimix` walks `testing_cfg.test_dir` as val.py:28-92 does (mix_clean | mix_both | mix_single,
+s1..s3; whole utterances, resampled on the device); `synthetic` evaluates seeded two-speaker mixtures.  STOI (pystoi: third party,
+absent) is printed as nan.  MUSDB needs the `musdb` package (absent): refused.  `val()` returns (SI-SDR, improvement); the SDR of
+the run is in the printed result line."""
 import argparse
 import glob
 import os
@@ -27,17 +28,18 @@ def argument_handler():
 def val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, device):
     n_srcs = model_cfg.get("n_src", 1)
     n, L = testing_cfg.get("n_items", 4), int(testing_cfg.get("length_samples", 32000))
-    sisdr = sisdr_imp = 0.0
+    sisdr = sisdr_imp = sdr = 0.0
     for i in range(n):
         mix, clean = synth_batch(1, L, seed=10_000 + i, device=device)
         mix_wav, clean_wavs = mix[0], clean[0]                         # [1, L], [S, L]
         wavs = model_infer(model, mix_wav, n_srcs=n_srcs, segment=testing_cfg.get("segment_samples", None),
                            overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs)
-        s, _, _ = metric_evaluation(wavs, clean_wavs)
+        s, d, _ = metric_evaluation(wavs, clean_wavs)
         base = K.sisnr_matrix(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous())
         sisdr += s
         sisdr_imp += s - torch.diagonal(base).mean().item()
-    return sisdr / n, sisdr_imp / n
+        sdr += d
+    return sisdr / n, sisdr_imp / n, sdr / n
 
 
 def read_librimix(folder, n_spks=1, noisy=False):
@@ -51,7 +53,7 @@ def read_librimix(folder, n_spks=1, noisy=False):
 
 
 def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
-    """val.py:59-92: per utterance read mixture + sources, resample, model_infer, SI-SDR and its improvement over the mixture.  The
+    """val.py:59-92: per utterance read mixture + sources, resample, model_infer, SI-SDR, its improvement over the mixture, and SDR.  The
     reader thread has utterance i + 1 (WAV reads, upload, resampling) on the device while utterance i is separated."""
     from .loader import Prefetcher
     from .train_env.asteroid_librimix.librimix_dataset import read_wav
@@ -76,18 +78,20 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
                 x = K.resample(x, fs, int(fs * ratio))
             return x[:1].unsqueeze(0), x[1:].unsqueeze(0)
 
-    sisdr = sisdr_imp = 0.0
+    sisdr = sisdr_imp = sdr = 0.0
     for i, (mix, clean) in enumerate(Prefetcher(_Utterances(), [[k] for k in range(n)], device, depth=1)):
         mix_wav, clean_wavs = mix[0], clean[0]
         wavs = model_infer(model, mix_wav, n_srcs=n_srcs, segment=testing_cfg.get("segment_samples", None),
                            overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs)
-        s, _, _ = metric_evaluation(wavs, clean_wavs)
-        base, _, _ = metric_evaluation(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous())     # val.py:86: the sources as estimates, the mixture as target
+        s, d, _ = metric_evaluation(wavs, clean_wavs)
+        # val.py:86: the sources as estimates, the mixture as target; only its SI-SNR is used
+        base, _, _ = metric_evaluation(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous(), with_sdr=False)
         sisdr += s
         sisdr_imp += s - base
+        sdr += d
         if (i % 500 == 0 and i > 0) or i == 1:
-            print("SI-SDR={:0.3f},SI-SDR-imp={:0.3f}".format(sisdr / (i + 1), sisdr_imp / (i + 1)))
-    return sisdr / n, sisdr_imp / n
+            print("SI-SDR={:0.3f},SI-SDR-imp={:0.3f},SDR={:0.3f}".format(sisdr / (i + 1), sisdr_imp / (i + 1), sdr / (i + 1)))
+    return sisdr / n, sisdr_imp / n, sdr / n
 
 
 def val(argv=None):
@@ -106,14 +110,14 @@ def val(argv=None):
         "No support for splitter/combiner with non QAT model."
     dataset_cfg, testing_cfg = conf["dataset_cfg"], conf.get("testing_cfg", {})
     if dataset_cfg["name"] == "librimix":
-        sisnr, imp = val_librimix(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
+        sisnr, imp, sdr = val_librimix(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "synthetic":
-        sisnr, imp = val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
+        sisnr, imp, sdr = val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "musdbhq":
         raise NotImplementedError("dataset musdbhq: val.py:95-178 reads MUSDB18-HQ through the third-party `musdb` package (absent here)")
     else:
         assert False, "Dataset {} is not supported!".format(dataset_cfg["name"])
-    print("SI-SDR={:0.2f},SI-SDR-imp={:0.2f},SDR={:0.2f},STOI={:0.3f}".format(sisnr, imp, float("nan"), float("nan")))
+    print("SI-SDR={:0.2f},SI-SDR-imp={:0.2f},SDR={:0.2f},STOI={:0.3f}".format(sisnr, imp, sdr, float("nan")))
     return sisnr, imp
 
 

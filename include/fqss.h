@@ -1023,6 +1023,19 @@ int fqss_infer_ola(const float* chunk, const int* map, float* out, float* sum_we
                    int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream);
 int fqss_infer_normalize(float* out, const float* sum_weight, int64_t rows, int64_t L, int64_t ld, fqss_stream_t stream);
 
+/* Signal-to-distortion ratio of the evaluation side (csrc/sdr.hip; process.metric_evaluation, process.py:129-152: torchmetrics'
+ * SignalDistortionRatio = fast_bss_eval's sdr, third party, restated from its published definition).  P pairs est[p][:L], ref[p][:L]
+ * (row strides ld_e, ld_r >= L).  Per pair, in fp64: the means are subtracted when zero_mean; both signals are divided by
+ * max(their 2-norm, 1e-6); r[k] = sum_t ref[t] ref[t + k] and b[k] = sum_t ref[t] est[t + k] for k < filter_length (linear: terms with
+ * t + k >= L are absent); r[0] += load_diag unless load_diag is negative or NaN; R sol = b with R the symmetric Toeplitz matrix of r
+ * (Levinson-Durbin); coh = b . sol; db[p] = 10 log10(coh / (1 - coh)).  db[p] is NaN when a prediction error of the recursion is not
+ * positive (a silent or degenerate target) or coh is not finite.  filter_length in 1..512.  ws: a workspace of at least
+ * fqss_sdr_ws_doubles(P, L, filter_length) = P * ceil(L / 1024) * (2 * filter_length + 4) doubles, ws_doubles its size; it need not be
+ * initialised.  No atomics: db is the same bit for bit from run to run.  fqss_sdr_ws_doubles returns 0 for arguments fqss_sdr refuses. */
+int64_t fqss_sdr_ws_doubles(int P, int64_t L, int filter_length);
+int fqss_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t L, int64_t ld_e, int64_t ld_r,
+             int filter_length, int zero_mean, double load_diag, fqss_stream_t stream);
+
 /* Affine (scale, zero-point) form of the learned quantizers for the true-integer export (csrc/export_q.hip; SURVEY.md §8(f) rank 3;
  * replaces torch.fake_quantize_per_tensor_affine / per_channel_affine inside TorchWeightFakeQuantize / TorchActivationFakeQuantize /
  * TorchDymActivationFakeQuantize, qat_quant.py:15-72).  x viewed as [outer][C][inner]; scale / zp [C] on the device (C = 1: per
