@@ -104,6 +104,7 @@ _PROTOS = {
     "fqss_mul_bcast_bwd": [P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I64, I64, P],
     "fqss_splitter2": [P, P, I32, I64, P, P],
     "fqss_splitter2_raw": [P, P, I32, I64, P, P],
+    "fqss_splitter2_rows": [P, P, I32, I64, P, P],
     "fqss_frames_conv_fwd": [P, P, P, I32, I32, I32, I64, I32, I32, I32, I64, P],
     "fqss_frames_conv_add_fwd": [P, P, P, I64, P, I32, I32, I32, I64, I32, I32, I32, I64, P],
     "fqss_ola_convtr_fwd": [P, P, P, I32, I32, I32, I64, I32, I32, I64, P],
@@ -194,6 +195,9 @@ _PROTOS = {
     "fqss_sisnr_matrix": [P, P, P, P, P, I32, I64, I64, I64, P],
     "fqss_infer_ola": [P, P, P, P, I32, I32, I64, I64, I64, I64, I64, P],
     "fqss_infer_normalize": [P, P, I64, I64, I64, P],
+    "fqss_chunk_gather": [P, P, I64, I64, I64, I64, I32, P],
+    "fqss_sisnr_chunks": [P, P, P, P, I32, I32, I64, I64, I64, I64, I64, P],
+    "fqss_infer_ola_chunks": [P, P, P, I32, I32, I64, I64, I64, I64, I64, P],
     "fqss_sdr_ws_doubles": [I32, I64, I32],
     "fqss_sdr": [P, P, P, I64, P, I32, I64, I64, I64, I32, I32, F64, P],
     "fqss_fq_affine": [P, P, P, I64, I64, I64, P, P, I32, I32, P],

@@ -22,19 +22,49 @@ __device__ __forceinline__ float split_q(float x) {
     return fminf(fmaxf(floorf(x / delta), -128.0f), 127.0f) * delta;
 }
 
+// the two channels of one sample under threshold thr (process.py:22-36): k_splitter2 and k_splitter2_rows split through this one body
+__device__ __forceinline__ void split2(float x, float thr, float& msb, float& lsb) {
+    const float delta = 0.0078125f;
+    const float v = x / thr;
+    const float q0 = split_q(v);
+    const float r = ((2.0f * (v - q0)) * 1.0f) / delta - 1.0f;  // process.py:35 op order
+    msb = q0;
+    lsb = split_q(r);
+}
+
 __global__ __launch_bounds__(256) void k_splitter2(const float* __restrict__ x, float* __restrict__ out, int B,
                                                     int64_t T, const uint32_t* obs) {
     const float mn = ord2f(obs[0]), mx = ord2f(obs[1]);
     const float thr = fmaxf(fabsf(mn), fabsf(mx));  // max(abs(x.min()), abs(x.max()))  process.py:24
-    const float delta = 0.0078125f;
     const int64_t n = (int64_t)B * T;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / T, t = i - b * T;
-        const float v = x[i] / thr;
-        const float q0 = split_q(v);
-        const float r = ((2.0f * (v - q0)) * 1.0f) / delta - 1.0f;  // process.py:35 op order
-        out[(b * 2 + 0) * T + t] = q0;
-        out[(b * 2 + 1) * T + t] = split_q(r);
+        split2(x[i], thr, out[(b * 2 + 0) * T + t], out[(b * 2 + 1) * T + t]);
+    }
+}
+
+// per-item form (the reference calls the model once per chunk, so a batch of chunks has one threshold per row): stage 1 leaves
+// max|x[b, :]| in row_max[b] as the bit image of a non-negative float, which orders like the unsigned integer it is (atomicMax: exact,
+// order-free; zeroed by the caller); stage 2 is k_splitter2 with thr = row_max[b].  A silent row divides by zero in its own row only.
+__global__ __launch_bounds__(256) void k_row_absmax(const float* __restrict__ x, int B, int64_t T, uint32_t* __restrict__ row_max) {
+    __shared__ float wmx[4];
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        float vmax = 0.0f;
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (int64_t)gridDim.x * 256) vmax = fmaxf(vmax, fabsf(x[b * T + t]));
+        vmax = wave_max(vmax);
+        if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = vmax;
+        __syncthreads();
+        if (threadIdx.x == 0) atomicMax(row_max + b, __float_as_uint(fmaxf(fmaxf(wmx[0], wmx[1]), fmaxf(wmx[2], wmx[3]))));
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_splitter2_rows(const float* __restrict__ x, float* __restrict__ out, int B, int64_t T,
+                                                         const uint32_t* __restrict__ row_max) {
+    for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+        const float thr = __uint_as_float(row_max[b]);
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (int64_t)gridDim.x * 256)
+            split2(x[b * T + t], thr, out[(b * 2 + 0) * T + t], out[(b * 2 + 1) * T + t]);
     }
 }
 
@@ -434,6 +464,15 @@ extern "C" int fqss_splitter2(const float* x, float* out, int B, int64_t T, cons
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(k_splitter2, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, out, B, T, obs_ws);
     return launch_status("fqss_splitter2");
+}
+
+extern "C" int fqss_splitter2_rows(const float* x, float* out, int B, int64_t T, uint32_t* row_max, fqss_stream_t stream) {
+    FQSS_REQUIRE(x && out && row_max, "null pointer");
+    FQSS_REQUIRE(B > 0 && T > 0, "bad shape");
+    const dim3 grid = grid_rows(B, T, 1, 1024);
+    hipLaunchKernelGGL(k_row_absmax, grid, dim3(256), 0, (hipStream_t)stream, x, B, T, row_max);
+    hipLaunchKernelGGL(k_splitter2_rows, grid, dim3(256), 0, (hipStream_t)stream, x, out, B, T, row_max);
+    return launch_status("fqss_splitter2_rows");
 }
 
 extern "C" int fqss_splitter2_raw(const float* x, float* out, int B, int64_t T, const uint32_t* obs_ws, fqss_stream_t stream) {

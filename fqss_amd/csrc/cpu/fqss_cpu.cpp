@@ -2,7 +2,8 @@
 // batch 2, 1 s ... plumbing, no GPU"; reference train.py:31: device = "cpu" if use_cpu).  Plain C++ (g++, OpenMP), host pointers, the
 // `stream` argument is ignored, every call is synchronous.  It serves the entry points the UN-FUSED ConvTasNet QAT step uses (the
 // per-layer kernels that the G1 layer fixtures pin: KDTrainStep(coded=False, batched_quantizers=False) with the module-path teacher)
-// and the SDR of the evaluation side (fqss_sdr);
+// and, of the evaluation side, the SDR (fqss_sdr) and the batched chunked path (fqss_splitter2_rows, fqss_chunk_gather,
+// fqss_sisnr_chunks, fqss_infer_ola_chunks);
 // anything else is absent from this library and fqss_amd/_lib.py raises.  Arithmetic: the same op sequences as the HIP kernels
 // (fp32, one IEEE operation per operator: built with -ffp-contract=off; IEEE division; round-half-even), reductions in fp64.
 // NOT the oracle: oracle/ is test infrastructure and is never loaded by the product; this file is product code selected by --use_cpu.
@@ -522,19 +523,34 @@ static inline float split_q(float x) {      // process.py:10-14 with threshold =
     const float delta = 0.0078125f;
     return fminf(fmaxf(floorf(x / delta), -128.0f), 127.0f) * delta;
 }
+static inline void split2(float x, float thr, float& msb, float& lsb) {      // process.py:22-36
+    const float delta = 0.0078125f;
+    const float v = x / thr;
+    const float q0 = split_q(v);
+    const float r = ((2.0f * (v - q0)) * 1.0f) / delta - 1.0f;          // process.py:35 op order
+    msb = q0;
+    lsb = split_q(r);
+}
 int fqss_splitter2(const float* x, float* out, int B, int64_t T, const uint32_t* obs_ws, fqss_stream_t) {
     if (B == 0 || T == 0) return FQSS_OK;
     REQUIRE(x && out && obs_ws, "null pointer");
     const float thr = fmaxf(fabsf(ord2f(obs_ws[0])), fabsf(ord2f(obs_ws[1])));   // process.py:24
-    const float delta = 0.0078125f;
     for (int64_t b = 0; b < B; ++b)
-        for (int64_t t = 0; t < T; ++t) {
-            const float v = x[b * T + t] / thr;
-            const float q0 = split_q(v);
-            const float r = ((2.0f * (v - q0)) * 1.0f) / delta - 1.0f;          // process.py:35 op order
-            out[(b * 2 + 0) * T + t] = q0;
-            out[(b * 2 + 1) * T + t] = split_q(r);
-        }
+        for (int64_t t = 0; t < T; ++t) split2(x[b * T + t], thr, out[(b * 2 + 0) * T + t], out[(b * 2 + 1) * T + t]);
+    return FQSS_OK;
+}
+// one threshold per row (the reference calls the model chunk by chunk); row_max: B words zeroed by the caller, left holding the bit
+// images of max|x[b][:]| as the HIP library leaves them
+int fqss_splitter2_rows(const float* x, float* out, int B, int64_t T, uint32_t* row_max, fqss_stream_t) {
+    REQUIRE(x && out && row_max, "null pointer");
+    REQUIRE(B > 0 && T > 0, "bad shape");
+    for (int64_t b = 0; b < B; ++b) {
+        float thr;
+        memcpy(&thr, &row_max[b], 4);
+        for (int64_t t = 0; t < T; ++t) thr = fmaxf(thr, fabsf(x[b * T + t]));
+        memcpy(&row_max[b], &thr, 4);
+        for (int64_t t = 0; t < T; ++t) split2(x[b * T + t], thr, out[(b * 2 + 0) * T + t], out[(b * 2 + 1) * T + t]);
+    }
     return FQSS_OK;
 }
 int fqss_frames_conv_fwd(const float* x, const float* w, float* z, int N, int Ci, int Co, int64_t T, int K, int stride, int M, int64_t ld_z,
@@ -887,6 +903,91 @@ int fqss_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles,
         for (int i = 0; i < F; ++i) coh += b[i] * x[i];
         db[p] = (ok && std::isfinite(coh)) ? 10.0 * log10(coh / (1.0 - coh)) : (double)NAN;
     }
+    return FQSS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batched chunked inference
+// include/fqss.h: chunk k covers [k * stride, k * stride + seg), N = ceil(L / stride) chunks, n_k = min(seg, L - k * stride)
+static inline bool chunk_geometry_ok(int64_t L, int64_t seg, int64_t stride) { return L > 0 && seg > 0 && stride > 0 && stride <= seg; }
+static inline int64_t chunk_count(int64_t L, int64_t stride) { return (L + stride - 1) / stride; }
+static inline float tri_weight(int64_t t, int64_t seg) {      // process.py:166-168
+    const int64_t h = seg / 2;
+    const float mx = (float)(seg - h);
+    return (t < h ? (float)(t + 1) : (float)(seg - t)) / mx;
+}
+
+int fqss_chunk_gather(const float* mix, float* out, int64_t L, int64_t seg, int64_t stride, int64_t k0, int G, fqss_stream_t) {
+    REQUIRE(mix && out, "null pointer");
+    REQUIRE(chunk_geometry_ok(L, seg, stride) && G > 0 && G <= 65535 && k0 >= 0 && k0 < chunk_count(L, stride),
+            "bad shape (1 <= stride <= seg, 0 <= k0 < ceil(L / stride), 1 <= G <= 65535)");
+    const int64_t N = chunk_count(L, stride);
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t k = k0 + g < N ? k0 + g : N - 1, n = L - k * stride;
+        for (int64_t t = 0; t < seg; ++t) out[g * seg + t] = t < n ? mix[k * stride + t] : 0.0f;
+    }
+    return FQSS_OK;
+}
+
+int fqss_sisnr_chunks(const float* est, const float* ref, float* db, int* map, int G, int S, int64_t seg, int64_t stride, int64_t k0, int64_t L,
+                      int64_t ld_r, fqss_stream_t) {
+    REQUIRE(est && ref && db && map, "null pointer");
+    REQUIRE(S > 0 && S <= 16 && ld_r >= L, "bad shape (S <= 16, ld_r >= L)");
+    REQUIRE(chunk_geometry_ok(L, seg, stride) && G > 0 && k0 >= 0 && k0 < chunk_count(L, stride),
+            "bad shape (1 <= stride <= seg, 0 <= k0 < ceil(L / stride), G >= 1)");
+    const int64_t N = chunk_count(L, stride);
+    const double eps = 1.1920928955078125e-07;      // torch.finfo(torch.float32).eps
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t k = k0 + g < N ? k0 + g : N - 1, start = k * stride, n = L - start < seg ? L - start : seg;
+        float* dbg = db + g * S * S;
+        for (int p = 0; p < S; ++p)
+            for (int q = 0; q < S; ++q) {
+                const float *e = est + (g * S + p) * seg, *r = ref + q * ld_r + start;
+                double m[5] = {0, 0, 0, 0, 0};
+                for (int64_t i = 0; i < n; ++i) {
+                    const double a = e[i], b = r[i];
+                    m[0] += a; m[1] += b; m[2] += a * b; m[3] += a * a; m[4] += b * b;
+                }
+                const double nn = (double)n;
+                const double spt = m[2] - m[0] * m[1] / nn, spp = m[3] - m[0] * m[0] / nn, stt = m[4] - m[1] * m[1] / nn;
+                const double alpha = (spt + eps) / (stt + eps);
+                const double num = alpha * alpha * stt, den = alpha * alpha * stt - 2.0 * alpha * spt + spp;
+                dbg[p * S + q] = (float)(10.0 * log10((num + eps) / ((den < 0.0 ? 0.0 : den) + eps)));
+            }
+        int* mp = map + g * S * 2;      // swap_channel_order (process.py:105-125): first maximum, later estimates override earlier claims
+        for (int d = 0; d < S; ++d) { mp[2 * d] = d; mp[2 * d + 1] = 1; }
+        for (int p = 0; p < S; ++p) {
+            int best = 0;
+            float bv = -INFINITY;
+            for (int q = 0; q < S; ++q)
+                if (dbg[p * S + q] > bv) { bv = dbg[p * S + q]; best = q; }
+            mp[2 * best] = p;
+            mp[2 * best + 1] = p == best ? 1 : -1;
+        }
+    }
+    return FQSS_OK;
+}
+
+int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S, int C, int64_t L, int64_t seg, int64_t stride,
+                          int64_t ld_chunk, int64_t ld_out, fqss_stream_t) {
+    REQUIRE(chunks && out, "null pointer");
+    REQUIRE(S > 0 && C > 0 && S * C <= 65535 && chunk_geometry_ok(L, seg, stride) && ld_chunk >= seg && ld_out >= L,
+            "bad shape (1 <= stride <= seg, ld_chunk >= seg, ld_out >= L)");
+    const int64_t N = chunk_count(L, stride);
+#pragma omp parallel for collapse(2) schedule(static)
+    for (int64_t d = 0; d < S; ++d)
+        for (int64_t c = 0; c < C; ++c)
+            for (int64_t t = 0; t < L; ++t) {
+                const int64_t k_lo = t < seg ? 0 : (t - seg) / stride + 1;
+                const int64_t k_hi = t / stride < N - 1 ? t / stride : N - 1;
+                float acc = 0.0f, wsum = 0.0f;
+                for (int64_t k = k_lo; k <= k_hi; ++k) {      // increasing k: the order of the chunk-by-chunk overlap-add
+                    const int64_t src = map ? map[(k * S + d) * 2] : d, tt = t - k * stride;
+                    const float sign = map ? (float)map[(k * S + d) * 2 + 1] : 1.0f, w = tri_weight(tt, seg);
+                    acc = acc + w * (sign * chunks[((k * S + src) * C + c) * ld_chunk + tt]);
+                    wsum += w;
+                }
+                out[(d * C + c) * ld_out + t] = acc / wsum;
+            }
     return FQSS_OK;
 }
 

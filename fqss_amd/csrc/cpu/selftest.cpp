@@ -131,6 +131,36 @@ int main() {
         CHECK(fqss_sdr(pe.data(), pr.data(), wsd.data(), 4096, dbv.data(), P, Ls, Ls - 1, ldp, 8, 0, -1.0, nullptr) == FQSS_EINVAL);
         CHECK(fqss_sdr_ws_doubles(P, 0, 8) == 0);
     }
+    // batched chunked inference: a group that runs past the last (short) chunk, per-row splitter, per-chunk maps, gather-form overlap-add
+    {
+        const int64_t Lc = 310, seg = 100, hop = 75, Nc = 5;      // chunk 4 holds 10 samples
+        const int G = 3, Sc = 2;
+        auto mixc = rnd((size_t)Lc), tgt = rnd((size_t)Sc * (Lc + 3));
+        std::vector<float> rows((size_t)G * seg), sp2((size_t)G * 2 * seg), ck((size_t)(Nc + 1) * Sc * seg), dbc((size_t)G * Sc * Sc), oc((size_t)Sc * Lc);
+        std::vector<int> mpc((size_t)(Nc + 1) * Sc * 2);
+        std::vector<uint32_t> rmax(G, 0u);
+        CHECK(fqss_chunk_gather(mixc.data(), rows.data(), Lc, seg, hop, 3, G, nullptr) == 0);
+        for (int64_t t = 0; t < seg; ++t) CHECK(rows[seg + t] == (t < 10 ? mixc[4 * hop + t] : 0.0f) && rows[2 * seg + t] == rows[seg + t]);
+        CHECK(fqss_splitter2_rows(rows.data(), sp2.data(), G, seg, rmax.data(), nullptr) == 0);
+        for (auto v : sp2) CHECK(v >= -1.0f && v < 1.0f);
+        for (int64_t k = 0; k < Nc + 1; ++k)      // est = the targets swapped, so every full chunk's map is (1, -1), (0, -1)
+            for (int s2 = 0; s2 < Sc; ++s2)
+                for (int64_t t = 0; t < seg; ++t) {
+                    const int64_t i = (k < Nc ? k : Nc - 1) * hop + t;
+                    ck[(k * Sc + s2) * seg + t] = i < Lc ? tgt[(1 - s2) * (Lc + 3) + i] : 0.0f;
+                }
+        for (int64_t k0 = 0; k0 < Nc; k0 += G)
+            CHECK(fqss_sisnr_chunks(ck.data() + k0 * Sc * seg, tgt.data(), dbc.data(), mpc.data() + k0 * Sc * 2, G, Sc, seg, hop, k0, Lc, Lc + 3, nullptr) == 0);
+        for (int64_t k = 0; k < Nc; ++k) CHECK(mpc[k * 4] == 1 && mpc[k * 4 + 1] == -1 && mpc[k * 4 + 2] == 0 && mpc[k * 4 + 3] == -1);
+        CHECK(fqss_infer_ola_chunks(ck.data(), mpc.data(), oc.data(), Sc, 1, Lc, seg, hop, seg, Lc, nullptr) == 0);
+        for (int64_t t = 0; t < Lc; ++t) CHECK(fabsf(oc[t] + tgt[t]) <= 1e-6f && fabsf(oc[Lc + t] + tgt[Lc + 3 + t]) <= 1e-6f);
+        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, oc.data(), Sc, 1, Lc, seg, hop, seg, Lc, nullptr) == 0);
+        CHECK(fqss_chunk_gather(mixc.data(), rows.data(), Lc, seg, hop, Nc, G, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_chunk_gather(mixc.data(), rows.data(), Lc, seg, seg + 1, 0, G, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_sisnr_chunks(ck.data(), tgt.data(), dbc.data(), mpc.data(), G, 17, seg, hop, 0, Lc, Lc + 3, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, oc.data(), Sc, 1, Lc, seg, 0, seg, Lc, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_splitter2_rows(rows.data(), sp2.data(), G, seg, nullptr, nullptr) == FQSS_EINVAL);
+    }
     CHECK(fqss_version() == FQSS_VERSION);
     printf("selftest ok\n");
     return 0;

@@ -89,7 +89,7 @@ def infer(argv=None):
         ref_mean, ref_std = wav.mean(), wav.std()
         wav = (wav - ref_mean) / ref_std
     sep_wav = model_infer(run, wav, n_srcs=model_cfg.get("n_src", 1), segment=testing_cfg.get("segment_samples", None),
-                          overlap=testing_cfg.get("overlap", 0.25), device=device)
+                          overlap=testing_cfg.get("overlap", 0.25), device=device, chunk_batch=testing_cfg.get("chunk_batch"))
     if args.normalize:
         sep_wav = sep_wav * ref_std + ref_mean
     paths = []

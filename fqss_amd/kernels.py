@@ -1079,6 +1079,18 @@ def splitter2(x, normalize=True):
     return out
 
 
+def splitter2_rows(x):
+    """x [B,1,T] or [B,T] -> [B,2,T] with one threshold per item, thr_b = max|x[b]| (the splitter as the reference applies it when it
+    calls the model on one chunk at a time)"""
+    _need_gpu(x)
+    x2 = x.reshape(x.shape[0], -1).contiguous()
+    B, T = x2.shape
+    ws = torch.zeros(B, device=x.device, dtype=torch.int32)
+    out = torch.empty(B, 2, T, device=x.device, dtype=torch.float32)
+    _lib.call("fqss_splitter2_rows", _p(x2), _p(out), B, T, _p(ws), _stream())
+    return out
+
+
 def frames_conv_fwd(x, w, stride, add=None):
     """x [N,Ci,T] dense, w [Co,Ci,K] -> z [N,Co,M] (+ add [N,Co,M])"""
     _need_gpu(x, w)
@@ -2669,6 +2681,46 @@ def infer_normalize(out, sum_weight):
     assert out.is_contiguous()
     L = out.shape[-1]
     _lib.call("fqss_infer_normalize", _p(out), _p(sum_weight), out.numel() // L, L, L, _stream())
+
+
+def chunk_gather(mix, seg, stride, k0, G):
+    """mix [1, L] or [L] -> [G, 1, seg]: row g = mix[(k0 + g) * stride : ... + seg], zero past L; rows past the last chunk repeat it"""
+    _need_gpu(mix)
+    assert mix.numel() == mix.shape[-1] and mix.is_contiguous(), "chunk_gather: one dense channel"
+    out = torch.empty(G, 1, seg, device=mix.device, dtype=torch.float32)
+    _lib.call("fqss_chunk_gather", _p(mix), _p(out), mix.shape[-1], seg, stride, k0, G, _stream())
+    return out
+
+
+def sisnr_chunks(est, ref, stride, k0, db=None, mp=None):
+    """est [G, S, seg] (chunks k0 .. k0 + G - 1 of the model's output), ref [S, L] (the whole target) -> per-chunk SI-SNR matrices
+    [G, S, S] and swap_channel_order maps [G, S, 2]; `mp`: a dense [G, S, 2] int32 slice to fill (the utterance's map table)"""
+    _need_gpu(est, ref)
+    G, S, seg = est.shape
+    assert est.is_contiguous(), "sisnr_chunks: dense estimates"
+    ref, S2, L, ld_r = as_rowmat(ref)
+    assert S == S2, "sisnr_chunks: source count mismatch"
+    if db is None:
+        db = torch.empty(G, S, S, device=est.device, dtype=torch.float32)
+    if mp is None:
+        mp = torch.empty(G, S, 2, device=est.device, dtype=torch.int32)
+    assert db.is_contiguous() and mp.is_contiguous() and db.numel() == G * S * S and mp.numel() == G * S * 2 and mp.dtype == torch.int32
+    _lib.call("fqss_sisnr_chunks", _p(est), _p(ref), _p(db), _p(mp), G, S, seg, stride, k0, L, ld_r, _stream())
+    return db, mp
+
+
+def infer_ola_chunks(chunks, mp, length, stride):
+    """chunks [N.., S, (C,) seg] (at least ceil(length / stride) chunks), mp [N.., S, 2] int32 or None -> [S, (C,) length]: the
+    triangular overlap-add of infer_ola over every chunk in order and infer_normalize, bit for bit, in one launch"""
+    _need_gpu(chunks)
+    S, seg = chunks.shape[1], chunks.shape[-1]
+    C = chunks.shape[2] if chunks.dim() == 4 else 1
+    n_chunks = -(-length // stride) if stride > 0 else 0
+    assert chunks.is_contiguous() and chunks.shape[0] >= n_chunks, "infer_ola_chunks: dense chunks, one per hop"
+    assert mp is None or (mp.is_contiguous() and mp.dtype == torch.int32 and mp.shape[0] >= n_chunks and tuple(mp.shape[1:]) == (S, 2))
+    out = torch.empty((S, C, length) if chunks.dim() == 4 else (S, length), device=chunks.device, dtype=torch.float32)
+    _lib.call("fqss_infer_ola_chunks", _p(chunks), _p(mp), _p(out), S, C, length, seg, stride, seg, length, _stream())
+    return out
 
 
 # ------------------------------------------------------------------ affine form of the quantizers (csrc/export_q.hip)

@@ -195,6 +195,26 @@ class fast_codes:
         FAST = self.prev
 
 
+SPLIT_PER_ITEM = False  # True (`split_per_item(True)`): the 8-bit splitter normalises every batch item by its own maximum
+
+
+class split_per_item:
+    """split_per_item(True): `process.preprocess(n_splitter=2)` takes one threshold per batch item (fqss_splitter2_rows) instead of one
+    for the whole tensor -- what the reference computes when it calls the model on one chunk at a time; `process.model_infer(chunk_batch=G)`
+    turns it on around its batched forward"""
+
+    def __init__(self, on=True):
+        self.on = on
+
+    def __enter__(self):
+        global SPLIT_PER_ITEM
+        self.prev, SPLIT_PER_ITEM = SPLIT_PER_ITEM, self.on
+
+    def __exit__(self, *a):
+        global SPLIT_PER_ITEM
+        SPLIT_PER_ITEM = self.prev
+
+
 class coded_dataflow:
     """coded_dataflow(False): layer outputs do not carry their u8 codes, so every consumer takes its un-fused fp32 kernels (the
     per-layer path the G1 fixtures pin); used by the tests that pin the fused codes-only step against it"""
@@ -1088,6 +1108,11 @@ class Combine2(Function):
 def splitter2(x):
     with torch.no_grad():
         return K.splitter2(x)
+
+
+def splitter2_rows(x):
+    with torch.no_grad():
+        return K.splitter2_rows(x)
 
 
 class _ForkState:

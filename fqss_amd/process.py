@@ -7,6 +7,7 @@ chunked overlap-add inference with per-chunk source re-ordering, SI-SNR (fqss_si
 """
 import torch
 
+from . import _lib
 from . import kernels as K
 from . import ops
 
@@ -24,7 +25,10 @@ def preprocess(x, n_splitter=1, n_bits=8, sign=True, normalize=True):
     if n_splitter != 2 or n_bits != 8 or not sign:
         raise NotImplementedError("the splitter kernel serves n_splitter=2, 8 bit, signed")
     if normalize and x.shape[1] == 1 and x.dim() == 3:
-        return ops.splitter2(x)
+        return ops.splitter2_rows(x) if ops.SPLIT_PER_ITEM else ops.splitter2(x)
+    if ops.SPLIT_PER_ITEM:
+        raise NotImplementedError("ops.split_per_item serves [B, 1, T] waveforms (fqss_splitter2_rows); the multi-channel / "
+                                  "normalize=False splitter of HTDemucs has one threshold for the whole tensor")
     # multi-channel / multi-dimensional inputs (HTDemucs: [B, A, Fr, T] spectrogram, [B, A, T] waveform): the flattened
     # [B, 2, A*...] result is torch.cat([msb, lsb], dim=1)
     with torch.no_grad():
@@ -68,13 +72,53 @@ def swap_channel_order(sep_tensor, clean_tensor):
     return out.reshape(sep_tensor.shape)
 
 
-def model_infer(model, mix, n_srcs=1, segment=None, overlap=0.25, device="cuda", target=None):
+def _model_infer_batched(model, mix, num_srcs, segment, overlap, target, chunk_batch):
+    """the chunks of one utterance through the model `chunk_batch` at a time: what the chunk-by-chunk loop of `model_infer` computes
+    (per-chunk splitter threshold, per-chunk re-ordering, the same overlap-add in the same order) in ceil(N / G) forwards instead of N;
+    nothing is read back to the host"""
+    G = int(chunk_batch)
+    if G < 1:
+        raise ValueError(f"chunk_batch must be a positive number of chunks, got {chunk_batch!r}")
+    channels, length = mix.shape
+    if channels > 1:
+        raise NotImplementedError("chunk_batch serves one-channel mixtures (the waveform models); multi-channel chunked inference "
+                                  "runs chunk by chunk (chunk_batch=None)")
+    segment = int(segment)
+    stride = int((1 - overlap) * segment)
+    if not 1 <= stride <= segment:
+        raise ValueError(f"chunk_batch needs 1 <= int((1 - overlap) * segment) <= segment, got a hop of {stride}")
+    mix = mix.contiguous()
+    n_chunks = len(range(0, length, stride))
+    n_pad = -(-n_chunks // G) * G
+    want_map = target is not None and num_srcs > 1
+    maps = torch.empty(n_pad, num_srcs, 2, device=mix.device, dtype=torch.int32) if want_map else None
+    db = torch.empty(G, num_srcs, num_srcs, device=mix.device, dtype=torch.float32) if want_map else None
+    buf = None
+    for k0 in range(0, n_chunks, G):
+        chunks = K.chunk_gather(mix, segment, stride, k0, G)
+        with torch.no_grad(), ops.split_per_item(True):
+            y = model(chunks).detach()
+        y = y.reshape(G, num_srcs, y.shape[-1])
+        n = min(y.shape[-1], segment)
+        if buf is None:     # a model that returns fewer than `segment` samples is zero-padded, as the whole-utterance call pads it
+            buf = (torch.zeros if n < segment else torch.empty)(n_pad, num_srcs, segment, device=mix.device, dtype=torch.float32)
+        buf[k0:k0 + G, :, :n].copy_(y[..., :n])
+        if want_map:
+            K.sisnr_chunks(buf[k0:k0 + G], target.reshape(num_srcs, -1), stride, k0, db=db, mp=maps[k0:k0 + G])
+    return K.infer_ola_chunks(buf, maps, length, stride)
+
+
+def model_infer(model, mix, n_srcs=1, segment=None, overlap=0.25, device="cuda", target=None, chunk_batch=None):
     """process.model_infer (process.py:156-194): whole-utterance inference, or chunks of `segment` samples hopped by
     (1 - overlap) * segment, re-ordered per chunk against `target` and blended with the triangular window.  mix [channels, length];
-    returns [n_srcs, (channels,) length] on the device (the reference returns a CPU tensor)."""
-    if str(device) == "cpu":
+    returns [n_srcs, (channels,) length] on the device (the reference returns a CPU tensor).  chunk_batch=G (opt-in) sends the chunks
+    through the model G at a time (`_model_infer_batched`); None runs them one by one."""
+    if str(device) == "cpu" and _lib.BACKEND != "cpu":
         raise RuntimeError("fqss_amd runs on ROCm devices only (oracle/ is the CPU checker)")
     mix = mix.to(device)
+    if segment and chunk_batch is not None:
+        num_srcs = model.n_srcs if hasattr(model, "n_srcs") else n_srcs
+        return _model_infer_batched(model, mix, num_srcs, segment, overlap, None if target is None else target.to(device), chunk_batch)
     if not segment:
         with torch.no_grad():
             out = model(mix.unsqueeze(0)).detach()[0]

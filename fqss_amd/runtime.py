@@ -877,7 +877,7 @@ class InferRunner:
     def __call__(self, x):
         if not self.use_graph:
             return self._forward(x)
-        key = tuple(x.shape)
+        key = tuple(x.shape) + (ops.SPLIT_PER_ITEM,)     # per-item and global splitter: two graphs of one shape, never each other's
         ent = self._graphs.get(key)
         if ent is None:
             sx = x.clone()

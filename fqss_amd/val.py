@@ -82,7 +82,8 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
     for i, (mix, clean) in enumerate(Prefetcher(_Utterances(), [[k] for k in range(n)], device, depth=1)):
         mix_wav, clean_wavs = mix[0], clean[0]
         wavs = model_infer(model, mix_wav, n_srcs=n_srcs, segment=testing_cfg.get("segment_samples", None),
-                           overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs)
+                           overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs,
+                           chunk_batch=testing_cfg.get("chunk_batch"))
         s, d, _ = metric_evaluation(wavs, clean_wavs)
         # val.py:86: the sources as estimates, the mixture as target; only its SI-SNR is used
         base, _, _ = metric_evaluation(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous(), with_sdr=False)

@@ -567,6 +567,9 @@ int fqss_mul_bcast_bwd(const float* gz, const float* mask, const float* feat, fl
 /* x [B][T] -> out [B][2][T]; obs_ws must hold the global min/max of x (fqss_minmax) */
 int fqss_splitter2(const float* x, float* out, int B, int64_t T, const uint32_t* obs_ws,
                    fqss_stream_t stream);
+/* the per-item form: x [B][T] -> out [B][2][T] with one threshold per row, thr_b = max|x[b][:]| (what the reference computes when it
+ * calls the model on one chunk at a time); row_max: B words zeroed by the caller.  A silent row is NaN in that row only.  */
+int fqss_splitter2_rows(const float* x, float* out, int B, int64_t T, uint32_t* row_max, fqss_stream_t stream);
 /* the same with normalize=False (process.py:26-27: threshold = max|x|, x is not divided by it; HTDemucs time branch) */
 int fqss_splitter2_raw(const float* x, float* out, int B, int64_t T, const uint32_t* obs_ws, fqss_stream_t stream);
 /* z[n][co][m] = sum_{ci,k} w[co][ci][k] * x[n][ci][m*stride+k]   (x: [N][Ci][T] dense)        */
@@ -1022,6 +1025,23 @@ int fqss_sisnr_matrix(const float* est, const float* ref, double* mom, float* db
 int fqss_infer_ola(const float* chunk, const int* map, float* out, float* sum_weight, int S, int C, int64_t n, int64_t seg, int64_t start,
                    int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream);
 int fqss_infer_normalize(float* out, const float* sum_weight, int64_t rows, int64_t L, int64_t ld, fqss_stream_t stream);
+
+/* The batched form of the chunked path (process.model_infer(chunk_batch=G)): G chunks of one utterance go through the model as one
+ * batch.  Chunk k covers samples [k * stride, k * stride + seg) of the L-sample utterance, 1 <= stride <= seg; there are
+ * N = ceil(L / stride) chunks and chunk k holds n_k = min(seg, L - k * stride) samples.  No floating-point atomics: every result is
+ * the same bits from run to run.
+ *  fqss_chunk_gather      mix [L] -> out [G][seg]: row g = chunk k0 + g, zero past L; rows past chunk N - 1 repeat chunk N - 1.
+ *  fqss_sisnr_chunks      est [G][S][seg] (dense), ref [S][L] (row stride ld_r) -> db [G][S][S], map [G][S][2]: the matrix and map
+ *                         of fqss_sisnr_matrix between est[g][p][:n_k] and ref[q][k * stride : k * stride + n_k], k = k0 + g
+ *                         (rows past chunk N - 1 are compared as chunk N - 1); S <= 16.
+ *  fqss_infer_ola_chunks  chunks [N][S][C][ld_chunk], map [N][S][2] or NULL -> out [S][C][L] (row stride ld_out) =
+ *                         fqss_infer_ola over k = 0 .. N - 1 followed by fqss_infer_normalize, bit for bit, as a gather: no zeroed
+ *                         output, no weight buffer.                                                                             */
+int fqss_chunk_gather(const float* mix, float* out, int64_t L, int64_t seg, int64_t stride, int64_t k0, int G, fqss_stream_t stream);
+int fqss_sisnr_chunks(const float* est, const float* ref, float* db, int* map, int G, int S, int64_t seg, int64_t stride, int64_t k0,
+                      int64_t L, int64_t ld_r, fqss_stream_t stream);
+int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S, int C, int64_t L, int64_t seg, int64_t stride,
+                          int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream);
 
 /* Signal-to-distortion ratio of the evaluation side (csrc/sdr.hip; process.metric_evaluation, process.py:129-152: torchmetrics'
  * SignalDistortionRatio = fast_bss_eval's sdr, third party, restated from its published definition).  P pairs est[p][:L], ref[p][:L]
