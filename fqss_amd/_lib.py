@@ -1,286 +1,111 @@
-"""ctypes binding of csrc/libfqss_hip.so (C ABI declared in include/fqss.h)."""
+"""ctypes binding of csrc/libfqss_hip.so.  The C ABI is written down once, in include/fqss.h: the argtypes, restypes, descriptor
+structs and integer constants below are read from that header at import."""
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("FQSS_LIB") or os.path.join(_HERE, "csrc", "libfqss_hip.so")   # FQSS_LIB: kernel A/B experiments
-
-P, I64, I32, F32, F64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
-
-# name -> argtypes (restype is always int unless listed in _RESTYPE)
-_PROTOS = {
-    "fqss_version": [],
-    "fqss_last_error": [],
-    "fqss_selftest_div": [P, I64, F32, P, P],
-    "fqss_actq_fwd": [P, P, P, I64, I64, I64, I64, I64, I32, P, I32, P, P, P, P],
-    "fqss_obs_reset": [P, I64, P],
-    "fqss_observer_ema": [P, P, P, F64, P],
-    "fqss_actq_bwd": [P, P, P, I64, I64, I64, I64, I64, I32, P, I32, P, P, P, P, I64, P],
-    "fqss_gluq_fwd": [P, P, I64, I64, I64, I64, I64, I32, P, P, P, P],
-    "fqss_gluq_bwd": [P, P, P, I64, I64, I64, I64, I64, I64, I32, P, P, P, P],
-    "fqss_actq_bwd_colbias": [P, P, P, I64, I32, I64, I64, I64, I32, P, I32, P, P, P, P, P],
-    "fqss_actq2_bwd_colbias": [P, P, P, I64, I32, I64, I64, I64, P, P, P, P, P, P, P, P],
-    "fqss_minmax": [P, I64, I64, I64, P, P],
-    "fqss_wq_observe": [P, I64, I64, I64, P, P, P],
-    "fqss_wq_fwd": [P, P, P, I64, I64, I64, P, P, P],
-    "fqss_wq_bwd": [P, P, P, P, P, I64, I64, I64, P, P, I32, P],
-    "fqss_wq_fwd_bits": [P, P, P, I64, I64, I64, P, P, I32, P],
-    "fqss_wq_bwd_bits": [P, P, P, P, P, I64, I64, I64, P, P, I32, I32, P],
-    "fqss_gacc_flush": [P, P, P, P, P],
-    "fqss_gacc_flush_multi": [P, I32, P],
-    "fqss_wq_table_check": [P, I32],
-    "fqss_wq_multi_fwd": [P, I32, I32, P],
-    "fqss_wq_multi_bwd": [P, I32, I32, P],
-    "fqss_pwconv_fwd": [P, P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_pwconv_fwd_x3": [P, P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_pwconv_fwd_x3s": [P, P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_pwconv_fwd_wq": [P, P, P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_conv1d_s1_fwd": [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_conv1d_s1_bwd_w": [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_halo_pack": [P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I64, I64, P],
-    "fqss_phase_pack": [P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I64, I64, P],
-    "fqss_phase_unpack": [P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I64, I64, I64, I32, P, P],
-    "fqss_conv2_fwd_wq": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_conv2_fwd_x3s": [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_conv2_bwd_x_wq": [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_conv2_bwd_w": [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_pwconv_bwd_x": [P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_pwconv_bwd_w": [P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_wq_codes": [P, P, P, P, P, I32, I32, P, P, P],
-    "fqss_wq_codes_bits": [P, P, P, P, P, I32, I32, P, P, I32, P],
-    "fqss_qpw_fwd": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_qpw_bwd_x": [P, P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_qpw_bwd_x_add": [P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_qpw_bwd_w": [P, P, P, P, P, I32, I32, I32, I32, I64, I64, P],
-    "fqss_qpw_fwdq": [P, P, P, P, P, P, P, P, P, P, I32, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I64, I64, I64, I64, I64, P, P],
-    "fqss_qpw_fwdq_add": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I64, I64, I64, I64, I64, P, P, P],
-    "fqss_add_chain_ok": [I64, I64, I32, I32],
-    "fqss_add_chain_bwd": [P, I32, P, I64, P, I64, P, I64, P, I64, P, P, I64, I64, I32, I64, I64, I64, I64, P],
-    "fqss_qpw_stat_slots": [I32, I32],
-    "fqss_dwq_stat_slots": [I32, I32],
-    "fqss_qpw_fwd2": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_qpw_bwd_x2": [P, P, P, P, P, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_qpw_bwd_w2": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_qpw_bwd_w_group_ws": [P, I32],
-    "fqss_qpw_bwd_w_group": [P, I32, P, I64, P],
-    "fqss_decode": [P, P, I64, I64, I64, I64, P, P, P],
-    "fqss_gnq_fwd": [P, P, P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, F32, P, P, P, P, I32, P],
-    "fqss_gnq_bwd": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, P, P, P, P, P],
-    "fqss_ewq_bwd_p": [P, P, P, P, P, P, F32, P, P, I64, I64, I64, I64, I64, I64, I32, P, P, P, P, I32,
-                       P, I64, I32, P, P, P, P, I64, P, I64, I32, P, P, P, P, I64, P],
-    "fqss_gnq_bwd_p": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, P, P, P, P, P, I64, I32, P, P, P, P],
-    "fqss_dwq_fwd": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P, P, P],
-    "fqss_dwq_bwd_z": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P, P, P, P],
-    "fqss_ewq_fwd": [P, P, P, P, P, P, P, F32, P, P, I64, I64, I64, I64, I64, I64, I64, I32, P, P, P, P],
-    "fqss_ewq_bwd": [P, P, P, P, P, P, P, F32, P, P, I64, I64, I64, I64, I64, I64, I64, I32, P, P, P, P, P],
-    "fqss_dwq_bwd_w": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_mulq_fwd": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I64, P, P, P],
-    "fqss_mulq_bwd": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I64, I64, P, P, P, P, I64, I32, P, P, P, P],
-    "fqss_dwq_bwd": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P, P, P, P],
-    "fqss_dwq_bwd_gn": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, I64, I32, P, P, P, P, P, P, P, P],
-    "fqss_gnq_bwd_rows": [P, P, P, P, P, P, P, I32, I32, I32, I64, I64, P, P, P, P, P],
-    "fqss_gnq_bwd_apply": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, P, P, P, P, I64, I32, P, P, P, P],
-    "fqss_split3_planes": [P, P, I64, P],
-    "fqss_tgemm": [P, P, I32, I32, I32, I32, I64, I32, P, P, P, F32, P, P, I32, P, P, I32, P, P, I64, P, P, I64, P],
-    "fqss_tgemm_tiled": [P, P, I32, I32, I32, I32, I64, I32, P, P, P, F32, P, P, I32, P, P, I32, P, P, I64, P, P, I64, P],
-    "fqss_tgemm_tiled_ok": [I32, I32, I32],
-    "fqss_split3_tiles": [P, P, I32, I32, P],
-    "fqss_bn_moments": [P, P, I32, I32, I32, I64, P],
-    "fqss_bn_apply": [P, P, P, P, I32, I32, I32, I64, I64, P],
-    "fqss_bn_bwd_reduce": [P, P, P, I32, I32, I32, I64, I64, P],
-    "fqss_bn_bwd_apply": [P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, P],
-    "fqss_tdw": [P, P, P, P, F32, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_tstats": [P, I32, I32, I32, I64, P, P],
-    "fqss_dwconv_fwd": [P, P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_dwconv_bwd_x": [P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_dwconv_bwd_w": [P, P, P, I32, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_gn_fwd": [P, P, P, P, P, I32, I32, I32, I64, I64, F32, P, P],
-    "fqss_gn_fwd_tail": [P, P, P, P, I32, I32, I32, I64, I64, F32, P, I32, P, P, I64, P],
-    "fqss_gn_bwd": [P, P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, P, P],
-    "fqss_gnq_fwd_f": [P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, F32, P, P, P, P],
-    "fqss_gnq_bwd_f": [P, P, P, P, P, P, P, P, I32, I32, I32, I64, I64, I64, P, P, P, P, P],
-    "fqss_axpby": [P, P, F32, F32, P, I64, I64, I64, I64, I64, P],
-    "fqss_mul_bcast_fwd": [P, P, P, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_mul_bcast_bwd": [P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I64, I64, P],
-    "fqss_splitter2": [P, P, I32, I64, P, P],
-    "fqss_splitter2_raw": [P, P, I32, I64, P, P],
-    "fqss_splitter2_rows": [P, P, I32, I64, P, P],
-    "fqss_frames_conv_fwd": [P, P, P, I32, I32, I32, I64, I32, I32, I32, I64, P],
-    "fqss_frames_conv_add_fwd": [P, P, P, I64, P, I32, I32, I32, I64, I32, I32, I32, I64, P],
-    "fqss_ola_convtr_fwd": [P, P, P, I32, I32, I32, I64, I32, I32, I64, P],
-    "fqss_frames_wgrad1": [P, P, P, I32, I32, I32, I64, I64, I32, I32, P],
-    "fqss_frames_wgrad1s": [P, P, I64, P, I64, I32, I32, I32, I64, I64, I32, I32, P],
-    "fqss_frames_wgrad1_q": [P, P, P, P, P, I32, I32, I32, I64, I64, I32, I32, P],
-    "fqss_ola_convtr_fwd_q": [P, P, P, P, P, I32, I32, I32, I64, I32, I32, I64, P],
-    "fqss_ola_convtr_mul_fwd": [P, P, P, P, I32, I32, I32, I32, I64, I64, I32, I32, I64, P],
-    "fqss_frames_wgrad": [P, P, P, I32, I32, I32, I32, I64, I64, I32, I32, P],
-    "fqss_kd_loss": [P, P, P, I32, I64, F32, P, P, P, P, P, P],
-    "fqss_kd_moments": [P, P, P, I32, I64, P, P],
-    "fqss_pit_sisdr_loss": [P, P, I32, I64, P, P, P, P, P, P],
-    "fqss_kd_loss_per_sample": [P, P, P, I32, I64, F32, I32, F32, P, P, P, P, P, P],
-    "fqss_sumsq": [P, I64, P, P],
-    "fqss_set_deterministic": [I32, P, I64, P],
-    "fqss_det_finish": [P, I64, P, P],
-    "fqss_adam_clip": [P, P, P, P, I64, P, F32, F32, F32, F32, F32, F32, P, P, P, P],
-    "fqss_rowlin_fwd": [P, P, P, P, I64, I32, I32, I64, I64, I64, P],
-    "fqss_rowlin_fwd_w3": [P, P, P, P, I64, I32, I32, I64, I64, P],
-    "fqss_rowlin_bwd_x": [P, P, P, I64, I32, I32, I64, I64, I64, P],
-    "fqss_rowlin_bwd_w": [P, P, P, I64, I32, I32, I64, I64, I64, P],
-    "fqss_rowlin_bwd_w_batched": [P, P, P, I64, I32, I32, I64, I64, I64, I32, I64, I64, I64, P],
-    "fqss_colsum": [P, P, I64, I32, I64, P],
-    "fqss_layernorm_fwd": [P, P, P, P, P, I64, I32, I64, I64, F64, P],
-    "fqss_layernorm_bwd": [P, P, P, P, P, P, P, I64, I32, I64, I64, I64, P],
-    "fqss_layernormq_fwd": [P, P, P, P, P, P, I64, I32, I64, I64, I64, F64, P, P, P],
-    "fqss_layernormq_bwd": [P, P, P, P, P, P, P, P, I64, I32, I64, I64, I64, P, P, P, P],
-    "fqss_unary_fwd": [P, P, I64, I32, F64, P],
-    "fqss_unary_rows_fwd": [P, P, I64, I32, I64, I64, I32, F64, P],
-    "fqss_unary2_fwd": [P, P, I64, I32, F64, F64, P],
-    "fqss_unary_bwd": [P, P, P, I64, I32, F64, P],
-    "fqss_permute4": [P, P, I64, I64, I64, I32, I64, I64, I64, P],
-    "fqss_permute4_ld": [P, P, I64, I64, I64, I32, I64, I64, I64, I64, P],
-    "fqss_dp_segment_fwd": [P, P, I32, I32, I64, I64, I32, I32, P],
-    "fqss_dp_segment_bwd": [P, P, I32, I32, I64, I64, I32, I32, P],
-    "fqss_dp_merge_fwd": [P, P, P, I32, I32, I32, I32, I32, I64, I64, P],
-    "fqss_dp_merge_bwd": [P, P, P, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_ola2_fwd": [P, P, I64, I64, I64, P],
-    "fqss_ola2_bwd": [P, P, I64, I64, I64, P],
-    "fqss_attn_fwd": [P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I64, P, P, P],
-    "fqss_attn_bwd": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I64, I64, I64, I64, I64, I64, I64, I64, P],
-    "fqss_add_layernorm_fwd": [P, P, P, P, P, P, P, P, I64, I32, I64, I64, I64, I64, I64, F64, P, P, P],
-    "fqss_add_layernorm_bwd": [P, P, P, P, P, P, P, P, P, I64, I32, I64, I64, I64, I64, P, P, P, P],
-    "fqss_addq_layernorm_fwd": [P, P, P, P, P, P, P, P, I64, I32, I64, I64, I64, I64, I64, F64, P, P, P, P, P],
-    "fqss_addq_layernorm_bwd": [P, P, P, P, P, P, P, P, P, I64, I32, I64, I64, I64, I64, P, P, P, P, P, P, P],
-    "fqss_addq_layernorm_fwd_map": [P, P, P, P, P, P, P, P, I64, I32, I64, I64, I64, F64, P, P, P, P, I64, I64, I64, I64, I64, P],
-    "fqss_addq_layernorm_bwd_map": [P, P, P, P, P, P, P, P, I64, I32, I64, I64, P, P, P, P, P, P, I64, I64, I64, I64, I64, P],
-    "fqss_mha_prep_fwd": [P, P, P, P, I64, I32, I64, F64, P, P],
-    "fqss_mha_prep_fwd_c": [P, P, P, P, I64, I32, I64, F64, P, P],
-    "fqss_mha_prep_bwd": [P, P, P, P, P, I64, I32, I64, I64, F64, P, P, P],
-    "fqss_lstm_fwd": [P, P, P, P, P, P, I32, I32, I32, P],
-    "fqss_lstm_bwd": [P, P, P, P, P, I32, I32, I32, P],
-    "fqss_lstm_gate_fn": [P, P, P, I64, P],
-    "fqss_lstm_bwd_b": [P, P, P, P, P, P, I32, I32, I32, P],
-    "fqss_lstm_bwd_b4": [P, P, P, P, P, P, I32, I32, I32, P],
-    "fqss_gnrows_fwd": [P, P, P, P, P, P, I64, I32, I64, I64, I32, I32, I32, F64, P],
-    "fqss_gnrows_bwd": [P, P, P, P, P, P, P, P, I64, I32, I64, I64, I64, I32, I32, I32, P],
-    "fqss_bcast_add": [P, P, P, I64, I64, I32, P],
-    "fqss_bcast_sum": [P, P, I64, I64, I32, P],
-    "fqss_qrow_fwd": [P, P, P, P, P, P, P, P, I64, I32, I32, I64, I64, P],
-    "fqss_qrow_fwdq": [P, P, P, P, P, P, P, P, P, I64, I32, I32, I64, I64, I64, I32, P, P, P, P],
-    "fqss_qrow_fwdq2": [P, P, P, P, P, P, P, P, P, P, I64, I32, I32, I64, I64, I64, I64, P, P, P, P, P],
-    "fqss_qrow_bwd_x": [P, P, P, P, I64, I32, I32, I64, I64, P],
-    "fqss_qrow_bwd_w": [P, P, P, P, P, I64, I32, I32, I64, I64, I64, P],
-    "fqss_qrow_bwd_wb": [P, P, P, P, P, P, I64, I32, I32, I64, I64, I64, P],
-    "fqss_qrow_bwd_w_batched": [P, P, P, P, P, I64, I32, I32, I64, I64, I64, I32, I64, I64, I64, P],
-    "fqss_qrow_bwd_w_group": [P, I32, P],
-    "fqss_glu_fwd": [P, P, I64, I64, I64, I64, I64, P],
-    "fqss_glu_bwd": [P, P, P, I64, I64, I64, I64, I64, I64, P],
-    "fqss_div_fwd": [P, P, P, I64, P],
-    "fqss_div_bwd": [P, P, P, P, P, I64, P],
-    "fqss_embedding_fwd": [P, P, P, I64, I32, I64, P],
-    "fqss_embedding_bwd": [P, P, P, I64, I32, I64, P],
-    "fqss_frames_gather": [P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_frames_ola": [P, P, P, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, I32, I32, I32, I32, I64, I64, I64, P],
-    "fqss_chan_sum": [P, P, I64, I64, I64, I64, P],
-    "fqss_chan_op": [P, P, P, I64, I64, I64, I64, I64, I32, P],
-    "fqss_chan_scale_bwd": [P, P, P, P, P, I64, I64, I64, I64, I64, I64, P],
-    "fqss_col_scale_fwd": [P, P, P, I64, I32, I64, I64, P],
-    "fqss_col_scale_bwd": [P, P, P, P, P, I64, I32, I64, I64, I64, P],
-    "fqss_sample_meanstd": [P, P, P, I64, I64, P],
-    "fqss_sample_norm": [P, P, P, I64, I64, I32, P],
-    "fqss_stft": [P, P, P, P, I64, I64, I64, I32, I32, I32, I32, P],
-    "fqss_istft": [P, P, P, P, P, P, I64, I64, I64, I32, I32, I32, I32, P],
-    "fqss_istft_bwd": [P, P, P, P, P, I64, I64, I64, I32, I32, I32, I32, P],
-    "fqss_transpose2d": [P, P, I64, I64, I64, P],
-    "fqss_hd_kd_loss": [P, P, P, P, P, P, P, P, I32, I32, I64, F32, P],
-    "fqss_sisnr_matrix": [P, P, P, P, P, I32, I64, I64, I64, P],
-    "fqss_infer_ola": [P, P, P, P, I32, I32, I64, I64, I64, I64, I64, P],
-    "fqss_infer_normalize": [P, P, I64, I64, I64, P],
-    "fqss_chunk_gather": [P, P, I64, I64, I64, I64, I32, P],
-    "fqss_sisnr_chunks": [P, P, P, P, I32, I32, I64, I64, I64, I64, I64, P],
-    "fqss_infer_ola_chunks": [P, P, P, I32, I32, I64, I64, I64, I64, I64, P],
-    "fqss_sdr_ws_doubles": [I32, I64, I32],
-    "fqss_sdr": [P, P, P, I64, P, I32, I64, I64, I64, I32, I32, F64, P],
-    "fqss_fq_affine": [P, P, P, I64, I64, I64, P, P, I32, I32, P],
-    "fqss_snr_mix": [P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, I32, P],
-    "fqss_resample_fir": [P, P, P, I64, I64, I64, I64, I64, I32, I32, I32, P],
-    "fqss_attn_long_fwd": [P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P],
-    "fqss_attn_long_bwd": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P],
-    "fqss_attn_long_fwd_c": [P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P],
-    "fqss_attn_long_bwd_c": [P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P],
-    # descriptor-struct forms (csrc/desc_api.hip); the structs are below
-    "fqss_workspace_bytes": [C.c_char_p, P, I32],
-    "fqss_add_fq_fwd": [P, P, P, P, F32, P, P, P, P, C.c_size_t, P],
-    "fqss_add_fq_bwd": [P, P, P, P, F32, P, P, P, P, P, P, C.c_size_t, P],
-    "fqss_pwconv_fq_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, C.c_size_t, P],
-    "fqss_gln_fq_fwd": [P, P, P, P, F32, P, P, P, P, P, C.c_size_t, P, I32, P],
-    "fqss_tgemm_desc": [P, P],
-}
-_RESTYPE = {"fqss_last_error": C.c_char_p, "fqss_workspace_bytes": C.c_int64, "fqss_qpw_bwd_w_group_ws": C.c_int64,
-             "fqss_sdr_ws_doubles": C.c_int64}
-
-DT_F32, DT_U8, DT_I8, DT_F64, DT_U16, DT_I64 = range(6)
-
-
-class FqssTensor(C.Structure):
-    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int), ("shape", C.c_int64 * 4), ("stride", C.c_int64 * 4)]
-
-
-class FqssQParams(C.Structure):
-    _fields_ = [("qmin", C.c_void_p), ("qmax", C.c_void_p), ("act", C.c_int), ("slope", C.c_void_p), ("gacc", C.c_void_p)]
-
-
-class FqssWCodes(C.Structure):
-    _fields_ = [("idx", C.c_void_p), ("idxT", C.c_void_p), ("dw", C.c_void_p), ("rw", C.c_void_p), ("Co", C.c_int), ("Ci", C.c_int)]
-
-
-class FqssAddChainLevel(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("ac", "bc", "bz", "bout", "amin", "amax", "bmin", "bmax", "qmin", "qmax", "gacc", "bgacc", "bgbias")]
-
-
-class FqssAddAfter(C.Structure):
-    _fields_ = [("a", C.c_void_p), ("ld_a", C.c_int64), ("amin", C.c_void_p), ("amax", C.c_void_p), ("qmin", C.c_void_p),
-                ("qmax", C.c_void_p), ("y", C.c_void_p), ("ld_y", C.c_int64)]
-
-
-class FqssGnAfter(C.Structure):
-    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean_rstd", C.c_void_p), ("ws", C.c_void_p), ("qmin", C.c_void_p),
-                ("qmax", C.c_void_p), ("ggamma", C.c_void_p), ("gbeta", C.c_void_p)]
-
-
-class FqssGnBefore(C.Structure):
-    _fields_ = [("xc0", C.c_void_p), ("ld_xc0", C.c_int64), ("qmin0", C.c_void_p), ("qmax0", C.c_void_p), ("gamma", C.c_void_p),
-                ("beta", C.c_void_p), ("mean_rstd", C.c_void_p), ("ws", C.c_void_p), ("gacc", C.c_void_p)]
-
-
-class FqssRowWgradJob(C.Structure):
-    _fields_ = [("gz", C.c_void_p), ("xc", C.c_void_p), ("qmin_x", C.c_void_p), ("qmax_x", C.c_void_p), ("gw", C.c_void_p),
-                ("gbias", C.c_void_p), ("R", C.c_int64), ("Ci", C.c_int32), ("Co", C.c_int32), ("ld_gz", C.c_int64),
-                ("ld_xc", C.c_int64), ("ld_gw", C.c_int64)]
-
-
-class FqssWgradJob(C.Structure):
-    _fields_ = [("gz1", C.c_void_p), ("gz2", C.c_void_p), ("xc", C.c_void_p), ("qmin_x", C.c_void_p), ("qmax_x", C.c_void_p),
-                ("gw", C.c_void_p), ("B", C.c_int32), ("Ci", C.c_int32), ("Co1", C.c_int32), ("Co2", C.c_int32), ("M", C.c_int32),
-                ("ld_gz1", C.c_int64), ("ld_gz2", C.c_int64), ("ld_xc", C.c_int64)]
-
-
-class FqssProducer(C.Structure):
-    _fields_ = [("z", C.POINTER(FqssTensor)), ("act", C.c_int), ("slope", C.c_void_p), ("gacc", C.c_void_p), ("gbias", C.c_void_p),
-                ("out", C.POINTER(FqssTensor))]
-
-
-class FqssTGemmDesc(C.Structure):
-    _fields_ = [("planes", C.POINTER(FqssTensor)), ("x", C.POINTER(FqssTensor)), ("pro", C.c_int), ("pro_stats", C.c_void_p),
-                ("pro_gamma", C.c_void_p), ("pro_beta", C.c_void_p), ("pro_eps", C.c_float), ("pro_slope", C.c_void_p),
-                ("bias", C.c_void_p), ("act", C.c_int), ("slope", C.c_void_p), ("stats_out", C.c_void_p), ("M1", C.c_int),
-                ("c1", C.POINTER(FqssTensor)), ("r1", C.POINTER(FqssTensor)), ("c2", C.POINTER(FqssTensor)),
-                ("r2", C.POINTER(FqssTensor))]
-
-EXPORTS = tuple(_PROTOS)
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "fqss.h"))            # as csrc/Makefile finds it
 
 
 class FqssError(RuntimeError):
     pass
+
+
+_BY_VALUE = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "const char*": C.c_char_p}
+_HANDLE = "fqss_stream_t"
+_DIRECTIVE = re.compile(r"#\s*(?:include\b.*|ifndef\s+\w+_H|ifdef\s+__cplusplus|endif|define\s+(\w+)\s*(.*))$")
+_STRUCT = re.compile(r"typedef\s+struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_FIELD = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*)?\w+(?:\s*\[\d+\])?(?:\s*,\s*(?:\*\s*)?\w+(?:\s*\[\d+\])?)*)")
+_PROTO = re.compile(r"(int|int64_t|const char\s*\*)\s*(\w+)\s*\(([^()]*)\)")
+_POINTER_PARAM = re.compile(r"(?:const\s+)?\w+(?:\s*\*(?:\s*const)?)+\s*\w+")
+_STRING_PARAM = re.compile(r"const char\s*\*\s*\w+")
+_VALUE_PARAM = re.compile(r"(\w+)\s+\w+")
+
+
+def parse_header(text):
+    """The C ABI of a header in the grammar include/fqss.h uses -> (protos {name: argtypes}, restypes {name: restype},
+    structs {name: ctypes.Structure subclass}, constants {name: int}).  Anything outside that grammar raises FqssError naming the
+    declaration: nothing is guessed and nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants, code = {}, []
+    for line in text.splitlines():
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        m = _DIRECTIVE.fullmatch(line.strip())
+        if m is None:
+            raise FqssError(f"fqss.h reader: unsupported preprocessor line {line.strip()!r}")
+        name, value = m.groups()
+        if name is not None and value:            # a #define without a value is the include guard
+            v = re.fullmatch(r"(\d+)|\((-\d+)\)", value.strip())
+            if v is None:
+                raise FqssError(f"fqss.h reader: #define {name} is not an integer constant: {value.strip()!r}")
+            constants[name] = int(v.group(1) or v.group(2))
+    text = "\n".join(code)
+
+    structs = {}
+
+    def struct(m):
+        body, name = m.groups()
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            f = _FIELD.fullmatch(decl)
+            if f is None:
+                raise FqssError(f"fqss.h reader: cannot classify field {decl!r} of struct {name}")
+            base = f.group(1)
+            for d in f.group(2).split(","):
+                field, _, count = d.replace("*", " ").replace("]", "").partition("[")
+                if "*" in d:
+                    ctype = C.POINTER(structs[base]) if base in structs else C.c_void_p
+                elif base in _BY_VALUE:
+                    ctype = _BY_VALUE[base]
+                else:
+                    raise FqssError(f"fqss.h reader: field {decl!r} of struct {name} has the unsupported by-value type {base}")
+                fields.append((field.strip(), ctype * int(count) if count else ctype))
+        structs[name] = type(name, (C.Structure,), {"_fields_": fields})
+        return ""
+
+    text = _STRUCT.sub(struct, text)
+    block = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, flags=re.S)
+    protos, restypes = {}, {}
+    for decl in filter(None, (" ".join(d.split()) for d in (block.group(1) if block else text).split(";"))):
+        if re.fullmatch(r"typedef void\s*\* " + _HANDLE, decl):
+            continue                              # the stream handle: c_void_p wherever a parameter names it
+        m = _PROTO.fullmatch(decl)
+        if m is None:
+            raise FqssError(f"fqss.h reader: cannot classify declaration {decl[:120]!r}")
+        ret, name, params = m.groups()
+        args = []
+        for p in ([] if params.strip() == "void" else (q.strip() for q in params.split(","))):
+            ptr, val = _POINTER_PARAM.fullmatch(p), _VALUE_PARAM.fullmatch(p)
+            if ptr:
+                args.append(C.c_char_p if _STRING_PARAM.fullmatch(p) else C.c_void_p)
+            elif val and val.group(1) == _HANDLE:
+                args.append(C.c_void_p)
+            elif val and val.group(1) in _BY_VALUE:
+                args.append(_BY_VALUE[val.group(1)])
+            else:
+                raise FqssError(f"fqss.h reader: cannot classify parameter {p!r} of {name}")
+        protos[name], restypes[name] = args, _RETURNS["const char*" if "*" in ret else ret]
+    return protos, restypes, structs, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise FqssError(f"{HEADER_PATH} not found: the binding is read from it ({e})") from None
+
+
+# name -> argtypes / name -> restype / struct classes under their header names / every integer #define
+_PROTOS, _RESTYPE, STRUCTS, CONSTANTS = _read_header()
+globals().update(STRUCTS)
+globals().update({k[len("FQSS_"):]: v for k, v in CONSTANTS.items() if k.startswith("FQSS_DT_")})   # DT_F32 .. DT_I64
+EXPORTS = tuple(_PROTOS)
 
 
 _lib = None
@@ -346,7 +171,7 @@ def _bind(name):
                 " (the CPU backend serves the un-fused ConvTasNet QAT step only: cfg 1 of BASELINE.json)" if BACKEND == "cpu" else ""))
         fn = getattr(lib, name)
         fn.argtypes = _PROTOS[name]
-        fn.restype = _RESTYPE.get(name, C.c_int)
+        fn.restype = _RESTYPE[name]
         _bound[name] = fn
     return fn
 

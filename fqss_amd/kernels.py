@@ -6,14 +6,21 @@ import torch
 
 from . import _lib
 
-Q_BYPASS, Q_OBSERVE, Q_QUANT = 0, 1, 2
-ACT_NONE, ACT_PRELU, ACT_RELU = 0, 1, 2
-ACT_GELU = 3          # nn.GELU (erf form) in front of a quantizer: fqss_actq_fwd / fqss_actq_bwd only (qat_layers.fq_node)
-ACT_POST_RELU = 4     # a ReLU BEHIND the quantizer, relu(fq(x)): fqss_actq_fwd / fqss_actq_bwd only (qat_layers.fq_node(post_relu=True))
 
-GACC_DOUBLES = 2048 * 3   # FQSS_GACC_SLOTS x (dmin, dmax, dslope)
-WQ_DESC_WORDS = 18        # FQSS_WQ_DESC_WORDS: int64 words per weight descriptor (word 17 = the weight's width in bits)
-WQ_BITS = (2, 8)          # FQSS_WQ_MIN_BITS, FQSS_WQ_MAX_BITS
+def _h(*names):
+    """values of the header's `#define FQSS_<name>` constants (include/fqss.h, read by _lib)"""
+    return tuple(_lib.CONSTANTS["FQSS_" + n] for n in names)
+
+
+Q_BYPASS, Q_OBSERVE, Q_QUANT = _h("Q_BYPASS", "Q_OBSERVE", "Q_QUANT")
+ACT_NONE, ACT_PRELU, ACT_RELU = _h("ACT_NONE", "ACT_PRELU", "ACT_RELU")
+# ACT_GELU: nn.GELU (erf form) in front of a quantizer (qat_layers.fq_node); ACT_POST_RELU: a ReLU BEHIND the quantizer, relu(fq(x))
+# (qat_layers.fq_node(post_relu=True)) -- fqss_actq_fwd / fqss_actq_bwd only
+ACT_GELU, ACT_POST_RELU = _h("ACT_GELU", "ACT_POST_RELU")
+
+GACC_DOUBLES = _h("GACC_SLOTS")[0] * 3   # FQSS_GACC_SLOTS x (dmin, dmax, dslope)
+WQ_DESC_WORDS, = _h("WQ_DESC_WORDS")     # int64 words per weight descriptor (word 17 = the weight's width in bits)
+WQ_BITS = _h("WQ_MIN_BITS", "WQ_MAX_BITS")
 USE_X3 = True            # route plain fp32 pointwise convs through the bf16 3x3-split GEMM
 LD_ALIGN = 16  # row stride of activation buffers is padded to 16 floats (64 B) -> 16-B/lane path
 
@@ -44,7 +51,7 @@ def _ref(x):
     return _C.byref(x) if x is not None else None
 
 
-def _qparams(qmin, qmax, act=0, slope=None, gacc=None):
+def _qparams(qmin, qmax, act=ACT_NONE, slope=None, gacc=None):
     q = _lib.FqssQParams()
     q.qmin, q.qmax, q.act, q.slope, q.gacc = _p(qmin), _p(qmax), act, _p(slope), _p(gacc)
     return q
@@ -1367,7 +1374,7 @@ def split3_planes(w2d):
 TGEMM_TILED = os.environ.get("FQSS_TGEMM_V1", "0") == "0"     # FQSS_TGEMM_V1=1: the round-3 kernel everywhere (A/B)
 
 
-TSTAT_SLOTS, TSTAT_STRIDE = 32, 16   # FQSS_TSTAT_SLOTS / FQSS_TSTAT_STRIDE (include/fqss.h)
+TSTAT_SLOTS, TSTAT_STRIDE = _h("TSTAT_SLOTS", "TSTAT_STRIDE")
 
 
 def tstat_buffer(n, B, device):
@@ -1423,7 +1430,7 @@ def tstats(x, ws):
 
 
 # ================================================================== dual-path models (cfg 3)
-UNARY_TANH, UNARY_SIGMOID, UNARY_DIVS = 0, 1, 2
+UNARY_TANH, UNARY_SIGMOID, UNARY_DIVS = _h("UNARY_TANH", "UNARY_SIGMOID", "UNARY_DIVS")
 
 
 def _rows(t, C):
@@ -1721,7 +1728,7 @@ def unary_fwd(x, kind, p=1.0):
     return y
 
 
-UNARY_ROUND, UNARY_FLOOR, UNARY_SIGN, UNARY_CLIP = 4, 5, 6, 7
+UNARY_ROUND, UNARY_FLOOR, UNARY_SIGN, UNARY_CLIP = _h("UNARY_ROUND", "UNARY_FLOOR", "UNARY_SIGN", "UNARY_CLIP")
 
 
 def unary2_fwd(x, kind, p=0.0, p2=0.0):
@@ -1957,7 +1964,7 @@ def bcast_sum(g):
 
 
 # ================================================================== first layer kernels of cfg 5 (HTDemucs)
-UNARY_GELU = 3
+UNARY_GELU, = _h("UNARY_GELU")
 
 
 def glu_fwd(x):

@@ -96,8 +96,7 @@ def test_descriptor_table_check_refuses_bad_widths():
     from fqss_amd import _lib, kernels as K
     from fqss_amd.quantization.qat import qat_quant as QQ
     assert _lib.BACKEND == "hip" and K.WQ_DESC_WORDS == 18 and QQ.WEIGHT_BITS == tuple(range(2, 9))
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "fqss.h")).read()
-    assert "#define FQSS_WQ_DESC_WORDS 18" in hdr and "#define FQSS_VERSION 100" in hdr
+    assert _lib.CONSTANTS["FQSS_WQ_DESC_WORDS"] == 18 and _lib.CONSTANTS["FQSS_VERSION"] == 100      # the #defines of include/fqss.h
     row = [0] * 12 + [1, 4, 3, 0, 4]           # words 12-16: outer, C, inner, first block, ldT
     for n in range(2, 9):
         K.wq_table_check([row + [8], row + [n]])
