@@ -1,7 +1,5 @@
 """Thin torch-tensor front end of the C ABI: shape/stride checks on the host, then one ctypes
 call per kernel on torch's current HIP stream.  No arithmetic happens in this file."""
-import os
-
 import torch
 
 from . import _lib
@@ -31,7 +29,6 @@ def _p(t):
 
 import ctypes as _C
 
-DESC_ABI = os.environ.get("FQSS_FLAT_ABI", "0") == "0"   # the long entry points go through their descriptor-struct forms (include/fqss.h)
 _DT = {torch.float32: _lib.DT_F32, torch.uint8: _lib.DT_U8, torch.int8: _lib.DT_I8, torch.float64: _lib.DT_F64, torch.int16: _lib.DT_U16,
        torch.int64: _lib.DT_I64}
 
@@ -143,11 +140,8 @@ def _rowmat_collapsed(t):
 
 def rowmat_collapsed_ok(t):
     """a view the element-wise kernels read in place as a row matrix (as_rowmat): 16-B aligned rows of dense trailing dims"""
-    rm = _rowmat_collapsed(t) if ROWMAT_COLLAPSE else None
+    rm = _rowmat_collapsed(t)
     return rm is not None and rm[2] % 4 == 0 and t.data_ptr() % 16 == 0 and t.dtype == torch.float32
-
-
-ROWMAT_COLLAPSE = os.environ.get("FQSS_ROWMAT_COLLAPSE", "1") != "0"    # element-wise kernels take cropped channel-first views without a dense copy
 
 
 def as_rowmat(t):
@@ -172,7 +166,7 @@ def empty_codes(shape, device):
 def actq_fwd(z, act, slope, qmode, qmin, qmax, obs_ws, want_idx=False, dense_idx=False, write_out=True):
     """write_out=False (QUANT + want_idx only): the fp32 result is an UNINITIALISED carrier, only codes are written"""
     _need_gpu(z, slope, qmin, qmax)
-    rc = _rowmat_collapsed(z) if (ROWMAT_COLLAPSE and z.dim() >= 3 and rowmat(z) is None) else None
+    rc = _rowmat_collapsed(z) if (z.dim() >= 3 and rowmat(z) is None) else None
     skip_out = (not write_out) and want_idx and qmode == Q_QUANT
     if rc is not None:
         # a cropped channel-first view ([B, C, F', T] out of [B, C, F, T]): rows of F' T columns at row stride F T, no dense copy; the
@@ -212,7 +206,7 @@ def actq_bwd(z, g, act, slope, qmode, qmin, qmax, gacc, gbias=None, C=0, out=Non
     """out: optional row-matrix view (e.g. a column block of a wider buffer) that receives gz"""
     _need_gpu(z, g)
     rcz = rcg = None
-    if ROWMAT_COLLAPSE and gbias is None and out is None and z.dim() >= 3 and z.shape == g.shape and (rowmat(z) is None or rowmat(g) is None):
+    if gbias is None and out is None and z.dim() >= 3 and z.shape == g.shape and (rowmat(z) is None or rowmat(g) is None):
         rcz, rcg = _rowmat_collapsed(z), _rowmat_collapsed(g)       # (see actq_fwd: cropped channel-first views, no dense copy)
     if rcz is not None and rcg is not None and rcz[:2] == rcg[:2]:
         (rows, cols, ld_z), ld_g = rcz, rcg[2]
@@ -359,13 +353,12 @@ def pwconv_fwd_wq(x, wc, bias):
     return z
 
 
-CONV_IMPLICIT = os.environ.get("FQSS_CONV_IMPLICIT", "1") != "0"
-CONV_IMPLICIT_MAX_CO = int(os.environ.get("FQSS_CONV_IMPLICIT_MAX_CO", "64"))
+CONV_IMPLICIT_MAX_CO = 64    # widest output of a stride-1 Conv1d that runs as an implicit GEMM; wider ones are faster on the frame image
 
 
 def conv1d_s1_ok(Ci, taps):
     """stride-1 1-D convolutions run without a frame image (fqss_conv1d_s1_*) when the weight rows are 16-B aligned"""
-    return CONV_IMPLICIT and taps > 1 and (Ci * taps) % 4 == 0
+    return taps > 1 and (Ci * taps) % 4 == 0
 
 
 def conv1d_s1_fwd(x, w2, bias, taps, dil, pad):
@@ -517,20 +510,14 @@ def qpw_fwdq(xc, wc, bias1, bias2, qmin_x, qmax_x, Co1, act, slope, r1, r2=None,
                   B, Ci, Co1, Co2, M, rm[2], rowmat(z1)[2], rowmat(z2)[2] if Co2 else 0, rowmat(yc1)[2], rowmat(yc2)[2] if Co2 else 0,
                   _ref(recs[0]) if recs[0] is not None else None, _ref(recs[1]) if recs[1] is not None else None, _stream())
         return ((z1, z2, yc1, yc2) if Co2 else (z1, yc1)) + (tuple(sums),)
-    if DESC_ABI:
-        w = _lib.FqssWCodes()
-        w.idx, w.idxT, w.dw, w.rw, w.Co, w.Ci = _p(wc.idx), _p(wc.idxT), _p(wc.dw), _p(wc.rw), wc.Co, wc.Ci
-        dx, dz1, dz2, dy1, dy2 = _desc(xc), _desc(z1), _desc(z2), _desc(yc1), _desc(yc2)
-        qx, q1 = _qparams(qmin_x, qmax_x), _qparams(r1[0], r1[1], act, slope)
-        q2 = _qparams(r2[0], r2[1], act, slope) if r2 else None
-        ws, nws = (_p(stats.ws), stats.ws.numel() * stats.ws.element_size()) if stats is not None else (None, 0)
-        _lib.call("fqss_pwconv_fq_fwd", _ref(dx), _ref(qx), _ref(w), _p(bias1), _p(bias2), _ref(dz1), _ref(dz2), _ref(dy1), _ref(dy2),
-                  _ref(q1), _ref(q2), ws, nws, _stream())
-        return (z1, z2, yc1, yc2) if Co2 else (z1, yc1)
-    _lib.call("fqss_qpw_fwdq", _p(xc), _p(wc.idx), _p(wc.dw), _p(wc.rw), _p(bias1), _p(bias2), _p(qmin_x), _p(qmax_x), _p(z1), _p(z2),
-              act, _p(slope), _p(r1[0]), _p(r1[1]), _p(r2[0]) if r2 else None, _p(r2[1]) if r2 else None, _p(yc1), _p(yc2),
-              B, Ci, Co1, Co2, M, rm[2], rowmat(z1)[2], rowmat(z2)[2] if Co2 else 0, rowmat(yc1)[2], rowmat(yc2)[2] if Co2 else 0,
-              _p(stats.ws) if stats is not None else None, _stream())
+    w = _lib.FqssWCodes()
+    w.idx, w.idxT, w.dw, w.rw, w.Co, w.Ci = _p(wc.idx), _p(wc.idxT), _p(wc.dw), _p(wc.rw), wc.Co, wc.Ci
+    dx, dz1, dz2, dy1, dy2 = _desc(xc), _desc(z1), _desc(z2), _desc(yc1), _desc(yc2)
+    qx, q1 = _qparams(qmin_x, qmax_x), _qparams(r1[0], r1[1], act, slope)
+    q2 = _qparams(r2[0], r2[1], act, slope) if r2 else None
+    ws, nws = (_p(stats.ws), stats.ws.numel() * stats.ws.element_size()) if stats is not None else (None, 0)
+    _lib.call("fqss_pwconv_fq_fwd", _ref(dx), _ref(qx), _ref(w), _p(bias1), _p(bias2), _ref(dz1), _ref(dz2), _ref(dy1), _ref(dy2),
+              _ref(q1), _ref(q2), ws, nws, _stream())
     return (z1, z2, yc1, yc2) if Co2 else (z1, yc1)
 
 
@@ -821,7 +808,7 @@ def ewq_bwd_p(ac, amin, amax, bc, bmin, bmax, sb, g, act, slope, qmin, qmax, gac
             o = empty_act(tuple(ac.shape), ac.device)
             outs.append(o)
             args += [_p(z), rowmat(z)[2], pact, _p(pslope), _p(pgacc), _p(pgbias), _p(o), rowmat(o)[2]]
-    if DESC_ABI and ac.dim() == 3 and ac.shape[1] == C:
+    if ac.dim() == 3 and ac.shape[1] == C:
         # descriptor form (fqss_add_fq_bwd): tensors / quantizers / producers as structs instead of 38 positional arguments
         keep = [_desc(ac), _desc(bc), _desc(g), _desc(gz)]
         qa, qb, qo = _qparams(amin, amax), (_qparams(bmin, bmax) if bc is not None else None), _qparams(qmin, qmax, act, slope, gacc)
@@ -1174,8 +1161,11 @@ def frames_wgrad(a, x, gw, stride):
     _lib.call("fqss_frames_wgrad", _p(a), _p(x), _p(gw), N, C, Ci, M, ld_a, T, K, stride, _stream())
 
 
+FRAMES_WGRAD1 = True    # False: the general fqss_frames_wgrad kernel also at the two encoder geometries (tests patch it)
+
+
 def _frames_wgrad1_ok(sig, T, K, stride):
-    return (K, stride) in ((16, 8), (32, 16)) and os.environ.get("FQSS_FRAMES_WGRAD1", "1") != "0"
+    return (K, stride) in ((16, 8), (32, 16)) and FRAMES_WGRAD1
 
 
 def frames_wgrad1_q(ac, qmin, qmax, sig, gw, stride):
@@ -1363,15 +1353,12 @@ def split3_planes(w2d):
     planes = torch.empty(3, *w2d.shape, device=w2d.device, dtype=torch.int16)
     _lib.call("fqss_split3_planes", _p(w2d), _p(planes), w2d.numel(), _stream())
     Co, Ci = w2d.shape
-    if Co % 256 == 0 and Ci % 128 == 0 and Ci <= 512 and TGEMM_TILED:
+    if Co % 256 == 0 and Ci % 128 == 0 and Ci <= 512:
         # the image k_tgemm2 streams by LDS-DMA ([Co/256][Ci/32][3][256][32], swizzled); rides on the planes tensor
         tiles = torch.empty(3 * Co * Ci, device=w2d.device, dtype=torch.int16)
         _lib.call("fqss_split3_tiles", _p(w2d), _p(tiles), Co, Ci, _stream())
         planes._fqss_tiles = tiles
     return planes
-
-
-TGEMM_TILED = os.environ.get("FQSS_TGEMM_V1", "0") == "0"     # FQSS_TGEMM_V1=1: the round-3 kernel everywhere (A/B)
 
 
 TSTAT_SLOTS, TSTAT_STRIDE = _h("TSTAT_SLOTS", "TSTAT_STRIDE")
@@ -1396,7 +1383,7 @@ def tgemm(planes, x, bias, act=ACT_NONE, slope=None, pro=0, pro_stats=None, pro_
                   float(pro_eps), _p(pro_slope), _p(bias), act, _p(slope), _p(stats_out), M1, _p(c1), _p(r1), rowmat(c1)[2],
                   _p(c2), _p(r2), rowmat(c2)[2] if c2 is not None else 0, _stream())
         return (c1, c2) if c2 is not None else c1
-    if DESC_ABI and (r1 is None or rowmat(r1)[2] == rowmat(c1)[2]) and (r2 is None or rowmat(r2)[2] == rowmat(c2)[2]):
+    if (r1 is None or rowmat(r1)[2] == rowmat(c1)[2]) and (r2 is None or rowmat(r2)[2] == rowmat(c2)[2]):
         td = _lib.FqssTGemmDesc()
         dpl, dx, dc1, dr1, dc2, dr2 = _desc(planes.view(3, Co, Ci), _lib.DT_U16), _desc(x), _desc(c1), _desc(r1), _desc(c2), _desc(r2)
         td.planes, td.x, td.c1 = _C.pointer(dpl), _C.pointer(dx), _C.pointer(dc1)
@@ -1462,7 +1449,7 @@ def rowlin_fwd(x, w, bias, out=None):
     return z
 
 
-W3_CACHE = os.environ.get("FQSS_W3_CACHE", "0") != "0"    # opt-in: measured neutral (docs/history/DESIGN_rounds_1-5.md 7e (4)), the default stays the on-the-fly split
+W3_CACHE = False    # True: frozen weights keep their bf16 planes across calls (measured neutral, docs/history/DESIGN_rounds_1-5.md 7e (4)); tests patch it
 
 
 def _frozen_weight_planes(w, Ci, x, ld_x):
@@ -1501,7 +1488,7 @@ def rowlin_bwd_w(gz, x, gw):
     _lib.call("fqss_rowlin_bwd_w", _p(gz), _p(x), _p(gw), R, Ci, Co, ld_gz, ld_x, gw.stride(0), _stream())
 
 
-PAIR_WGRAD = os.environ.get("FQSS_PAIR_WGRAD", "1") != "0"    # A/B switch: the two directions' W_hh gradients in one launch
+PAIR_WGRAD = True    # the two directions' W_hh gradients in one launch; False: one launch each (tests patch it)
 
 
 def rowlin_bwd_w_pair(gz0, x0, gw0, gz1, x1, gw1):
@@ -1714,7 +1701,7 @@ def unary_fwd(x, kind, p=1.0):
             y = _like_padded(x, *pd)
             _lib.call("fqss_unary_fwd", _p(x), _p(y), pd[0] * pd[1], kind, float(p), _stream())
             return y
-    if not x.is_contiguous() and _lib.BACKEND != "cpu" and os.environ.get("FQSS_UNARY_INPLACE", "1") != "0":      # (A/B knob)
+    if not x.is_contiguous() and _lib.BACKEND != "cpu":
         # a column block of a wider row matrix (the q third of an attention in-projection): read in place, written dense
         rm = as_rowmat_view(x)
         if rm is not None:
@@ -1846,7 +1833,7 @@ def ola2_bwd(g):
     return gy
 
 
-ATTN_STREAM = os.environ.get("FQSS_ATTN_STREAM", "1") != "0"
+ATTN_STREAM = True    # False: the 250-step sequences stay on the LDS-resident attention kernels of csrc/attn.hip (tests patch it)
 
 
 def _attn_stream_ok(ts, E, nh):
@@ -2213,8 +2200,8 @@ def _sig4(x):
 
 
 # ---- stride-1 convolutions on halo-packed planes (fqss_halo_pack / fqss_conv2_*): no frame image
-CONV_HALO = os.environ.get("FQSS_CONV_HALO", "1") != "0"      # (A/B knob: "0" = every general convolution gathers frames)
-CONV_PHASE = os.environ.get("FQSS_CONV_PHASE", "1") != "0"    # (A/B knob: "0" = the strided convolutions gather frames)
+CONV_HALO = True      # False: every general convolution gathers frames (tests patch it)
+CONV_PHASE = True     # False: the strided convolutions gather frames (tests patch it)
 
 
 class HaloPlan:
@@ -2465,7 +2452,7 @@ def attn_long_bwd(q, k, v, o, go, stats, nh, batch_first):
     return gq, gk, gv
 
 
-ATTN_CODED = os.environ.get("FQSS_ATTN_CODED", "1") != "0"
+ATTN_CODED = True    # False: attention on the float operands instead of the u8 codes of q, k, v (tests patch it)
 
 
 def attn_coded_ok(E, nh):

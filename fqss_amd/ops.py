@@ -95,16 +95,15 @@ class _GnHand:
         self.kind, self.fwd, self.rec = kind, fwd, None
 
 
-FUSE_GN_BWD_DW = os.environ.get("FQSS_FUSE_GN_BWD_DW", "1") != "0"
-_GN_HAND = os.environ.get("FQSS_GN_HAND", "both")          # experiments: "after" / "before" alone
-FUSE_GN = os.environ.get("FQSS_FUSE_GN", "1") != "0"
-FUSE_EW = os.environ.get("FQSS_FUSE_EW", "1") != "0"
+# Test hooks, not user settings: the parity tests patch each of these to False to reach the un-fused reference path.
+FUSE_GN = True          # False: a conv in front of a GroupNormQ runs its own output-quantizer backward (no ops._Producer hand-over)
+FUSE_EW = True          # False: the same for a res | skip pair in front of element-wise layers
 # round 5: the forward of the AddQ behind each output of a res | skip pair runs in the pair GEMM's epilogue (fqss_qpw_fwdq_add)
-FUSE_ADD_FWD = os.environ.get("FQSS_FUSE_ADD_FWD", "1") != "0"
+FUSE_ADD_FWD = True     # False: those AddQ forwards as their own launches
 
 
 # round 5: the backward of a CHAIN of AddQ layers (the skip sum of the TCN stack) as ONE launch (fqss_add_chain_bwd)
-FUSE_ADD_CHAIN = os.environ.get("FQSS_FUSE_ADD_CHAIN", "1") != "0"
+FUSE_ADD_CHAIN = True   # False: one backward launch per AddQ of the chain
 
 
 class _ChainLink:
@@ -126,15 +125,14 @@ class _PreSum:
 
     def __init__(self, codes, a_idx, owner):
         self.codes, self.a_idx, self.owner = codes, a_idx, owner
-FUSE_STATS = os.environ.get("FQSS_FUSE_STATS", "1") != "0"   # gLN statistics from the epilogue of the kernel that makes its input codes
-NEXT_IS_GROUPNORM = False   # set by HipSequential around the forward of a module followed by a GroupNormQ
+NEXT_IS_GROUPNORM = False   # set by HipSequential around the forward of a module followed by a GroupNormQ (its gLN statistics then
+                            # come from the epilogue of the kernel that makes its input codes)
 NEXT_IS_DW3 = False         # ... around the forward of a GroupNormQ followed by a 3-tap depthwise Conv1dNlQ (their backward hand-over)
 # (The two forwards stay two launches: one kernel for both measured SLOWER -- 39.5 us against 34.5 us at the cfg-2 shape, the step
 # unchanged: both passes are bound by vector-ALU issue, so a fusion saves the launch and a 16-MB re-read but not the instructions.)
 
 
 NEXT_TAKES_PRODUCER = False  # set by HipSequential around its last module when the sequence's output has ONE consumer, a coded MulQ
-FUSE_MULQ_PROD = os.environ.get("FQSS_FUSE_MULQ_PROD", "1") != "0"
 
 
 def _producer_args(pr):
@@ -160,7 +158,7 @@ def is_carrier(x):
 # fp32, like the reference's); fqss_amd.runtime.KDTrainStep turns it on around the student forward.
 FAST = False
 CODED = True            # False (tests, `coded_dataflow(False)`): no layer output carries codes -> every layer runs its un-fused fp32 kernels
-DEBUG_POISON = bool(int(__import__("os").environ.get("FQSS_DEBUG_CARRIER", "0")))   # NaN-fill carriers (tests)
+DEBUG_POISON = bool(int(os.environ.get("FQSS_DEBUG_CARRIER", "0")))   # NaN-fill carriers (tests)
 
 
 # ---- deferred per-quantizer work ------------------------------------------------------------------
@@ -329,9 +327,6 @@ def cut(*tensors, late=False):
     return tuple(leaves)
 
 
-FLAT_CM = os.environ.get("FQSS_FLAT_CM", "1") != "0"        # (A/B knob: "0" = reshape(B, C, -1), copying what is not a view)
-
-
 def flat_cm(x):
     """a channel-first tensor [B, C, ...] as [B, C', M] WITHOUT a copy, for maps that pair or walk channels (GLU, per-channel streams):
     [B, C, H W] when the trailing dims are dense; [B, C H, W] when rows of W are `ld` apart with the planes dense in rows -- the
@@ -340,7 +335,7 @@ def flat_cm(x):
     if x.dim() <= 3:
         return x
     B, C = x.shape[0], x.shape[1]
-    if x.dim() == 4 and FLAT_CM:
+    if x.dim() == 4:
         _, _, H, W = x.shape
         st = x.stride()
         if st[3] == 1 and st[2] == W and st[1] >= H * W:
@@ -489,12 +484,9 @@ class _Lin:
         self.w_param, self.b_param, self.slope_param = w_param, b_param, slope_param
 
 
-FRAME_CODES_FWD = os.environ.get("FQSS_FRAME_CODES_FWD", "1") != "0"
-
-
 def _lin_fwd(L, x, w, bias):
     if L.kind == "pw":
-        if L.wc_dgrad is not None and FRAME_CODES_FWD and x.dim() == 3:
+        if L.wc_dgrad is not None and x.dim() == 3:
             # the weight is on its int8 grid (runtime.QuantTables), the input a plain float tensor: three products per k (k_qgemm<4>)
             z = K.pwconv_fwd_wq(x, L.wc_dgrad, bias)
             if z is not None:
@@ -548,10 +540,6 @@ def _lin_bwd_w(L, gz, x, gw):
         raise NotImplementedError(L.kind)
 
 
-FRAME_CODES_DGRAD = os.environ.get("FQSS_FRAME_CODES_DGRAD", "1") != "0"
-PLAIN_BIAS_SUM = os.environ.get("FQSS_PLAIN_BIAS_SUM", "1") != "0"       # (A/B knob: "0" = the bias gradient of a float conv from the epilogue pass)
-
-
 class LinearActQ(Function):
     """out = fq(act(linear(x, w) + bias))  -- Conv1dQ / Conv1dNlQ / Conv1dEncoderQ / decoder convT"""
 
@@ -567,7 +555,7 @@ class LinearActQ(Function):
             # the layer's own non-linearity + fake-quant ride in the GEMM epilogue: z (for the backward) and the
             # output codes come out of one launch
             # ... and, for a GroupNormQ consumer, the integer statistics of those codes (no statistics pass in the gLN)
-            q.stats = K.new_stats("qpw", x.shape[0], ctx.wc.Co, x.shape[-1], x.device) if (FUSE_STATS and NEXT_IS_GROUPNORM) else None
+            q.stats = K.new_stats("qpw", x.shape[0], ctx.wc.Co, x.shape[-1], x.device) if NEXT_IS_GROUPNORM else None
             z, q.idx = K.qpw_fwdq(ctx.xq.idx, ctx.wc, bias, None, ctx.xq.qmin, ctx.xq.qmax, ctx.wc.Co, act, slope, (q.qmin, q.qmax),
                                   stats=q.stats)
             q.carrier = True
@@ -581,7 +569,7 @@ class LinearActQ(Function):
                 z = _lin_fwd(L, x, w, bias)
             out = z if ctx.plain else _epilogue_fwd(z, act, slope, q)
         ctx.prod = None
-        if ((FUSE_GN and NEXT_IS_GROUPNORM) or (FUSE_MULQ_PROD and NEXT_TAKES_PRODUCER and act in (ACT_NONE, ACT_RELU, ACT_PRELU))) \
+        if ((FUSE_GN and NEXT_IS_GROUPNORM) or (NEXT_TAKES_PRODUCER and act in (ACT_NONE, ACT_RELU, ACT_PRELU))) \
                 and DEFER is not None and q.qmode == Q_QUANT and not ctx.plain and q.owner is not None \
                 and getattr(q.owner, "_fqss_deferred", False):
             ctx.prod = q.prod = _Producer(z, act, slope, L.slope_param, q, L.b_param, bias)
@@ -605,7 +593,7 @@ class LinearActQ(Function):
             _touch(L.slope_param if act == ACT_PRELU else None, q.owner.min_range, q.owner.max_range, L.b_param)
         elif ctx.plain and not ctx.has_bias:
             gz, g_slope, g_min, g_max, g_bias = g, None, None, None, None
-        elif ctx.plain and PLAIN_BIAS_SUM and g.dim() == 3 and g.is_cuda and L.kind in ("pw", "conv1") and K.rowmat(g) is not None \
+        elif ctx.plain and g.dim() == 3 and g.is_cuda and L.kind in ("pw", "conv1") and K.rowmat(g) is not None \
                 and K.rowmat(g)[2] % 4 == 0 and g.data_ptr() % 16 == 0:
             # a float (BYPASS) channel-first conv with a bias -- the DConv / frame-path convolutions of HTDemucs: the bias gradient is the
             # channel sum of g (one read-only pass, fqss_chan_sum) and g itself is gz; the epilogue kernel wrote a COPY of g to get it
@@ -626,7 +614,7 @@ class LinearActQ(Function):
                 gx = K.frames_conv_fwd(gz, w.reshape(w.shape[0], 1, w.shape[2]), L.stride, add=other)   # decoder: same, in its dgrad
             elif ctx.wc is not None:
                 gx = K.qpw_bwd_x(gz, ctx.wc)
-            elif L.kind == "pw" and L.wc_dgrad is not None and FRAME_CODES_DGRAD and gz.dim() == 3:
+            elif L.kind == "pw" and L.wc_dgrad is not None and gz.dim() == 3:
                 # round 5 (cfg 5): the frame-path convolutions of HTDemucs read FLOAT inputs, but their weight is fake-quantized: W_q =
                 # dw * Wi with int8 Wi, so the data gradient W_q^T gz is the q-GEMM of the ConvTasNet path (k_qgemm<1>: gz in three exact
                 # bf16 pieces x ONE exact plane of codes = three products per k instead of the six of the float x float form)
@@ -726,7 +714,7 @@ class LinearActQPair(Function):
         return gx, gbias[0], gbias[1], gmin[0], gmax[0], gmin[1], gmax[1], None, None, None, None, None, None, None, None
 
 
-FUSE_GNQ_F = os.environ.get("FQSS_FUSE_GNQ_F", "1") != "0"    # GroupNormQ on a float input: the quantizer inside the GroupNorm's own passes
+FUSE_GNQ_F = True    # GroupNormQ on a float input: the quantizer inside the GroupNorm's own passes; False: GroupNorm, then the quantizer (tests patch it)
 
 
 class GroupNormActQ(Function):
@@ -746,7 +734,7 @@ class GroupNormActQ(Function):
             st = getattr(x, "_fqss_stats", None)
             out, q.idx, mean_rstd = K.gnq_fwd(xq.idx, xq.qmin, xq.qmax, gamma, beta, eps, qmin, qmax, write_out=not q.carrier, stats=st)
             ctx.save_for_backward(gamma, beta, mean_rstd, xq.idx, xq.qmin, xq.qmax, qmin, qmax)
-            if FUSE_GN_BWD_DW and _GN_HAND != "after" and NEXT_IS_DW3 and q.gacc is not None and x.dim() == 3 and x.shape[-1] <= K.DWQ_ROW_MAX:
+            if NEXT_IS_DW3 and q.gacc is not None and x.dim() == 3 and x.shape[-1] <= K.DWQ_ROW_MAX:
                 # the depthwise layer behind this GroupNorm takes our backward's rows pass (ops._GnHand "before")
                 ctx.hand_out = q.hand = _GnHand("before", dict(xc0=xq.idx, qmin0=xq.qmin, qmax0=xq.qmax, gamma=gamma, beta=beta,
                                                                 mean_rstd=mean_rstd, gacc=q.gacc))
@@ -812,16 +800,16 @@ class DwConvQ(Function):
     @staticmethod
     def forward(ctx, x, w, bias, slope, qmin, qmax, L, act, q, xq):
         q.carrier = FAST and not q.keep_out
-        q.stats = K.new_stats("dwq", x.shape[0], x.shape[1], x.shape[2], x.device) if (FUSE_STATS and NEXT_IS_GROUPNORM) else None
+        q.stats = K.new_stats("dwq", x.shape[0], x.shape[1], x.shape[2], x.device) if NEXT_IS_GROUPNORM else None
         out, q.idx = K.dwq_fwd(xq.idx, xq.qmin, xq.qmax, w, bias, L.dil, L.pad, act, slope, qmin, qmax, write_out=not q.carrier,
                                stats=q.stats)
         ctx.save_for_backward(w, bias, slope, xq.idx, xq.qmin, xq.qmax, qmin, qmax)
         ctx.L, ctx.act, ctx.q = L, act, q
         ctx.hand_a = ctx.hand_b = None
-        if FUSE_GN_BWD_DW and w.shape[-1] == 3 and x.shape[-1] <= K.DWQ_ROW_MAX and q.gacc is not None:
+        if w.shape[-1] == 3 and x.shape[-1] <= K.DWQ_ROW_MAX and q.gacc is not None:
             h = getattr(x, "_fqss_hand", None)
             ctx.hand_b = h if (h is not None and h.kind == "before") else None
-            if NEXT_IS_GROUPNORM and q.qmode == Q_QUANT and _GN_HAND != "before":
+            if NEXT_IS_GROUPNORM and q.qmode == Q_QUANT:
                 ctx.hand_a = q.hand = _GnHand("after")       # the GroupNormQ behind this layer may leave its apply pass to our backward
         return _carrier(out) if q.carrier else out
 
@@ -1116,7 +1104,7 @@ def splitter2_rows(x):
 
 
 class _ForkState:
-    """lets the dgrad q-GEMM of ONE branch of a two-way fork add the gradient of the OTHER branch in its epilogue (FUSE_FORK): the other
+    """lets the dgrad q-GEMM of ONE branch of a two-way fork add the gradient of the OTHER branch in its epilogue: the other
     branch's backward (an element-wise LayerQ, created later in the forward => run earlier in the backward) leaves its gradient in
     `other` (tagged with its branch index, ACCUMULATED if that branch has several such consumers); the conv's LinearActQ.backward
     consumes it only if it sits on the opposite branch and records which branch it was -- and WHAT it added (`taken`, a snapshot:
@@ -1144,9 +1132,6 @@ class _ForkState:
             return None
         self.fused_branch, self.taken, self.n_taken = branch, self.other, self.n_other
         return self.other
-
-
-FUSE_FORK = os.environ.get("FQSS_FUSE_FORK", "1") != "0"
 
 
 class Fork2(Function):
@@ -1182,8 +1167,7 @@ def fork2(x):
     if torch.is_grad_enabled() and x.requires_grad:
         fk = _ForkState()
         a, b = Fork2.apply(x, fk)
-        if FUSE_FORK:
-            a._fqss_fork, b._fqss_fork = (fk, 0), (fk, 1)
+        a._fqss_fork, b._fqss_fork = (fk, 0), (fk, 1)
         c = codes_of(x)
         if c is not None:
             a._fqss_q = b._fqss_q = c

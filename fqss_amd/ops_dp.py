@@ -31,18 +31,12 @@ def touch(*ts):
             base._fqss_touched = True
 
 
-QROW_BWD = __import__("os").environ.get("FQSS_QROW_BWD", "1") != "0"    # gradient GEMMs of coded linears on the codes; 0: fp32 x fp32 (A/B, tests)
-
-
 def _rowlinear_dgrad(gz, w):
     """dL/dx of z = x @ w^T: from the weight's int8 codes when it carries them (three bf16 products per k), else fp32 x fp32 (six)"""
     wc = getattr(w, "_fqss_wcodes", None)
-    if QROW_BWD and wc is not None and w.dim() == 2 and wc.idx.is_contiguous() and K.qrow_bwd_ok(wc.Ci, wc.Co):
+    if wc is not None and w.dim() == 2 and wc.idx.is_contiguous() and K.qrow_bwd_ok(wc.Ci, wc.Co):
         return K.qrow_bwd_x(gz, wc)
     return K.rowlin_bwd_x(gz, w)
-
-
-WGRAD_BIAS = __import__("os").environ.get("FQSS_WGRAD_BIAS", "1") != "0"    # the bias gradient out of the coded weight-gradient launch
 
 
 def _rowlinear_wgrad_into(gz, x, xq, buf, gbias=None, defer=False):
@@ -51,9 +45,9 @@ def _rowlinear_wgrad_into(gz, x, xq, buf, gbias=None, defer=False):
     defer: buf (and gbias) are accumulation buffers that outlive this backward node (the step's dL/dW_q arena, a parameter's own
     gradient): with a runtime.QuantTables active the launch is queued and runs with the segment's other weight gradients
     (kernels.RowWgradQueue: one grouped launch instead of one 256-workgroup launch per linear)"""
-    if QROW_BWD and xq is not None and buf.dim() == 2 and buf.is_contiguous() and xq.idx.is_contiguous() \
+    if xq is not None and buf.dim() == 2 and buf.is_contiguous() and xq.idx.is_contiguous() \
             and xq.idx.shape[-1] == buf.shape[1] and K.qrow_bwd_ok(buf.shape[1], buf.shape[0]):
-        with_bias = WGRAD_BIAS and gbias is not None and gbias.is_contiguous() and gbias.numel() == buf.shape[0]
+        with_bias = gbias is not None and gbias.is_contiguous() and gbias.numel() == buf.shape[0]
         rq = getattr(ops.DEFER, "row_wgrad_queue", None) if defer else None
         if rq is not None:
             rq.push(gz, xq.idx, xq.qmin, xq.qmax, buf, gbias if with_bias else None)
@@ -64,14 +58,11 @@ def _rowlinear_wgrad_into(gz, x, xq, buf, gbias=None, defer=False):
     return False
 
 
-LSTM_WIH_GROUP = __import__("os").environ.get("FQSS_LSTM_WIH_GROUP", "1") != "0"
-
-
 def _rowlinear_wgrad_pair_into(gz0, gz1, x, xq, buf0, buf1):
     """both directions' W_ih gradients of a bidirectional LSTM (two column blocks of dG against one input): one launch"""
-    if QROW_BWD and xq is not None and all(b.dim() == 2 and b.is_contiguous() for b in (buf0, buf1)) and xq.idx.is_contiguous() \
+    if xq is not None and all(b.dim() == 2 and b.is_contiguous() for b in (buf0, buf1)) and xq.idx.is_contiguous() \
             and xq.idx.shape[-1] == buf0.shape[1] and K.qrow_bwd_ok(buf0.shape[1], buf0.shape[0]):
-        rq = getattr(ops.DEFER, "row_wgrad_queue", None) if LSTM_WIH_GROUP else None
+        rq = getattr(ops.DEFER, "row_wgrad_queue", None)
         if rq is not None and gz0.data_ptr() % 16 == 0 and gz1.data_ptr() % 16 == 0:
             # (buf0 / buf1 are the step's dL/dW_q arena slots: the two weight gradients join the segment's grouped launch)
             rq.push(gz0, xq.idx, xq.qmin, xq.qmax, buf0)
@@ -136,7 +127,7 @@ class RowLinearActQ(Function):
     @staticmethod
     def forward(ctx, x, w, bias, slope, qmin, qmax, act, q, qops, slope_param, flat):
         touch(w, bias)
-        if qops is not None and FUSE_QROWQ and q.qmode == ops.Q_QUANT and q.no_codes:
+        if qops is not None and q.qmode == ops.Q_QUANT and q.no_codes:
             # the output quantizer rides in the int8 GEMM's epilogue: no pass over z (fqss_qrow_fwdq)
             z, y = K.qrow_fwdq(qops[0].idx, qops[1], bias, qops[0].qmin, qops[0].qmax, act, slope, q.qmin, q.qmax)
             q.carrier = False
@@ -187,8 +178,7 @@ class RowLinearNlQ2(Function):
         return gx, gw, (None if gb_direct else gb), g_min1, g_max1, g_min2, g_max2, None, None, None
 
 
-QROW = __import__("os").environ.get("FQSS_QROW", "1") != "0"    # student linears on codes (csrc/qrow.hip); 0: fp32-equivalent GEMM
-FUSE_QROWQ = __import__("os").environ.get("FQSS_FUSE_QROWQ", "1") != "0"    # their output quantizer in the GEMM epilogue (fqss_qrow_fwdq)
+QROW = True    # student linears on codes (csrc/qrow.hip); False: the fp32-equivalent GEMM (tests patch it)
 
 
 def qrow_operands(x, w):
@@ -350,15 +340,12 @@ class Permute4(Function):
         return (gx if tuple(gx.shape) == ctx.xshape else gx.view(ctx.xshape)), None, None, None, None, None, None, None, None
 
 
-PERMUTE_CODES = __import__("os").environ.get("FQSS_PERMUTE_CODES", "1") != "0"    # the u8 codes of a row tensor travel through the layout change
-
-
 def _codes_along(x, y, dims_out, strides_in):
     """x -> y was a Permute4 of rows of N features; when x carries the u8 codes of the quantizer that made it (`_fqss_rowq`), move them the
     same way (the same kernel on a 4-codes-per-float view: N / 4 floats per row) and tag y -- the linear that follows then runs on codes"""
     xq = getattr(x, "_fqss_rowq", None)
     N = x.shape[-1]
-    if not PERMUTE_CODES or xq is None or N % 4 or xq.idx.shape != x.shape or not xq.idx.is_contiguous():
+    if xq is None or N % 4 or xq.idx.shape != x.shape or not xq.idx.is_contiguous():
         return y
     idx = K.permute4(xq.idx.view(torch.float32), dims_out, tuple(s // 4 for s in strides_in), N // 4)
     y._fqss_rowq = ops.ActCodes(idx.view(torch.uint8).view(y.shape), xq.qmin, xq.qmax)
@@ -437,9 +424,6 @@ class Ola2(Function):
         return K.ola2_bwd(g)
 
 
-FUSE_MHA_PREP = __import__("os").environ.get("FQSS_FUSE_MHA_PREP", "1") != "0"   # q / k / v / div quantizers + the division as one pass each way
-
-
 class MhaCore(Function):
     """Everything of MultiheadAttentionQ.forward between the in-projection X [L, B, 3E] and the (not yet quantized) heads
     [L, B, E] (qat_layers.py:890-911): the q / k / v quantizers (each observes the WHOLE X, each is used on its own third),
@@ -461,7 +445,7 @@ class MhaCore(Function):
             ctx.save_for_backward(X, q, heads, stats)
             return heads
         qs = [a.qctx() for a in aqs[:4]]
-        ctx.fused = FUSE_MHA_PREP and all(c.qmode == ops.Q_QUANT for c in qs) and E % 4 == 0
+        ctx.fused = all(c.qmode == ops.Q_QUANT for c in qs) and E % 4 == 0
         if ctx.fused:
             # quantizing phase: the three quantizers on the thirds, q / sqrt(head_dim) and the div quantizer in ONE pass (fqss_mha_prep_fwd)
             ctx.coded = K.attn_coded_ok(E, nh)
@@ -1011,7 +995,7 @@ class MhaCoreX(Function):
             ctx.save_for_backward(Xq, Xkv, q, heads, stats)
             return heads
         qs = [a.qctx() for a in aqs[:4]]
-        ctx.coded = FUSE_MHA_PREP and all(c.qmode == ops.Q_QUANT for c in qs) and E % 4 == 0 and K.attn_coded_ok(E, nh)
+        ctx.coded = all(c.qmode == ops.Q_QUANT for c in qs) and E % 4 == 0 and K.attn_coded_ok(E, nh)
         if ctx.coded:
             # quantizing phase: the quantizer chain of MhaCore's fused form emits the u8 CODES of q / k / v (for a cross attention the
             # chain runs on both projections: q from the query's, k / v from the key's) and the core runs on them (fqss_attn_long_fwd_c)

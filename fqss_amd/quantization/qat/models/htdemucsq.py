@@ -72,7 +72,7 @@ class _Window(torch.autograd.Function):
         ctx.cfg = (dim, start, length, x.shape[dim])
         if pad_to is None:
             v = x.narrow(dim, start, length)
-            if CROP_VIEWS and dim == x.dim() - 2 and x.dim() == 4 and K.rowmat_collapsed_ok(v):
+            if dim == x.dim() - 2 and x.dim() == 4 and K.rowmat_collapsed_ok(v):
                 # a crop along the frequency axis of [B, C, F, T]: planes of F' * T dense floats at the old plane stride -- the element-wise
                 # kernels behind a decoder layer (the next layer's skip add, the activation quantizer) read such a view in place
                 return v
@@ -106,10 +106,6 @@ class _Window(torch.autograd.Function):
         return out, None, None, None, None
 
 
-CROP_VIEWS = __import__("os").environ.get("FQSS_CROP_VIEWS", "1") != "0"      # (A/B knob: "0" = every crop is a dense copy)
-FOLD_CROP = __import__("os").environ.get("FQSS_FOLD_CROP", "1") != "0"        # (A/B knob: "0" = transposed convolutions write their whole output)
-
-
 def crop(x, dim, start, length):
     x = ops.real(x)
     dim = dim % x.dim()
@@ -135,23 +131,17 @@ class _Transpose(torch.autograd.Function):
         return K.transpose2d(g)
 
 
-SWAP_IN_PLACE = __import__("os").environ.get("FQSS_SWAP_IN_PLACE", "1") != "0"    # swap_mid reads a row-padded view in place (A/B)
-
-
-SWAP_PAD_ROWS = __import__("os").environ.get("FQSS_SWAP_PAD_ROWS", "1") != "0"   # (A/B knob)
-
-
 def swap_mid(x, rows_out=None):
     """[B, P, Q, T] -> [B, Q, P, T] (T-long contiguous chunks move: fqss_permute4).  rows_out True: the result is streamed as rows of T
     floats (DConv over [B F, C, T]): a row-padded activation, rows 16-B aligned, so the element-wise kernels behind it take their 16-B
     forms (T = 431); False: the INPUT was such rows (DConv's output), the result dense planes -- the gradient handed back is row-padded.
     None: dense both ways."""
     x = ops.real(x)
-    if x.stride(-1) != 1 or not SWAP_IN_PLACE:
+    if x.stride(-1) != 1:
         x = x.contiguous()
     B, P, Q, T = x.shape
     sB, sP, sQ, _ = x.stride()          # (a view of a row-padded buffer -- DConv's output reshaped -- is read in place)
-    pad = SWAP_PAD_ROWS and rows_out is not None
+    pad = rows_out is not None
     return ops_dp.Permute4.apply(x, (B, Q, P), (sB, sQ, sP), (B, P, Q), (P * Q * T, T, P * T), False, (0, 2, 1) if pad else None,
                                  pad and rows_out, pad and not rows_out)
 
@@ -177,7 +167,7 @@ class LayerScale(nn.Module):
         return self.mul(x, self.scale if self.channel_last else self.scale[:, None])
 
 
-FUSE_TEACHER_DCONV = __import__("os").environ.get("FQSS_FUSE_TEACHER_DCONV", "1") != "0"
+FUSE_TEACHER_DCONV = True    # False: the float teacher's DConv branches layer by layer, as under autograd (tests patch it)
 
 
 class DConv(nn.Module):
@@ -304,7 +294,7 @@ class HEncLayer(nn.Module):
             le = x.shape[-1]
             if le % self.stride:
                 pad_to = le + self.stride - le % self.stride
-                if not (FOLD_CROP and _takes_pad(self.conv)):
+                if not _takes_pad(self.conv):
                     x, pad_to = pad_right(x, pad_to), None
         y = run(self.conv, x) if pad_to is None else (self.conv(x, pad_to=pad_to) if isinstance(self.conv, QL.LayerQ) else
                                                       QL.conv_frames(self.conv, x, self.conv.weight, pad_to))
@@ -367,12 +357,11 @@ class HDecLayer(nn.Module):
         # the crop behind the transposed convolution (hdemucsq.py:340-345) is handed to it as a window: GELU and the fake-quant in
         # between are element-wise, so cropping first gives the same numbers without the margins ever being written
         window = None
-        if FOLD_CROP:
-            full = (y.shape[-2 if self.freq else -1] - 1) * self.stride + self.kernel_size
-            if self.freq and self.pad:
-                window = (-2, self.pad, full - 2 * self.pad)
-            elif not self.freq:
-                window = (-1, self.pad, length)
+        full = (y.shape[-2 if self.freq else -1] - 1) * self.stride + self.kernel_size
+        if self.freq and self.pad:
+            window = (-2, self.pad, full - 2 * self.pad)
+        elif not self.freq:
+            window = (-1, self.pad, length)
         z = run(self.conv_tr, y, window=window)
         if not self.last:
             z = run(self.gelu, z)

@@ -13,7 +13,6 @@ further down on the kernels of csrc/conv_frames.hip, hd_ops.hip, batchnorm.hip; 
 (see docs/history/DESIGN_rounds_1-5.md 8) raise NotImplementedError at construction -- there is no ATen fallback.
 """
 import math
-import os
 
 import torch
 import torch.nn as nn
@@ -71,14 +70,10 @@ def _mul_any(x1, x2, qmin, qmax, q):
     raise NotImplementedError(f"MulQ broadcast {tuple(x1.shape)} x {getattr(x2, 'shape', x2)} has no HIP kernel yet")
 
 
-FUSE_MULQ = os.environ.get("FQSS_FUSE_MULQ", "1") != "0"
-FUSE_DECQ = os.environ.get("FQSS_FUSE_DECQ", "1") != "0"    # decoder reads its coded input directly
-
-
 def _mul_coded(x1, x2, q):
     """mask[B,S,C,M] * feat[B,1,C,M] (either order) with both operands on codes, in the quantizing phase: the codes -> codes kernel
     (ops.MulQCoded); None when it does not apply"""
-    if not (FUSE_MULQ and torch.is_tensor(x2) and x1.dim() == 4 and x2.dim() == 4 and q.qmode == ops.Q_QUANT):
+    if not (torch.is_tensor(x2) and x1.dim() == 4 and x2.dim() == 4 and q.qmode == ops.Q_QUANT):
         return None
     if q.gacc is None and torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
         return None        # a backward would need the range-gradient slots (inference has none and needs none)
@@ -298,7 +293,7 @@ def conv_frames(conv, x, weight, pad_to=None):
     if K.CONV_HALO and K.CONV_PHASE and K.PhasePlan.serves(H, W, geom):
         # strided along one axis with a kernel of T strides (the k8 s4 p2 encoder layers): a stride-1 T-tap convolution over the phase
         # planes of the input (ops_dp.ConvPhase) -- the signal moves once, the frame image would be T times it
-        wc = getattr(weight, "_fqss_wcodes_dgrad", None) if (ops.FRAME_CODES_FWD and ops.FRAME_CODES_DGRAD) else None
+        wc = getattr(weight, "_fqss_wcodes_dgrad", None)
         pp = K.PhasePlan(H, W, geom, pad_to)
         if pp.ok(C, Co, wc is not None) and (wc is None or (wc.idx.is_contiguous() and wc.Ci == C * pp.k)):
             z = ops_dp.ConvPhase.apply(x4, ops.weight_view(weight, Co, C, geom.kh, geom.kw), conv.bias, pp, wc)
@@ -317,7 +312,7 @@ def conv_frames(conv, x, weight, pad_to=None):
         if geom.sh == 1 and geom.sw == 1:
             # stride-1 convolutions with WIDE outputs (the 3 x 3 / k = 3 `rewrite` convs of the decoder layers, C -> 2C): implicit GEMMs on
             # the halo-packed signal (ops_dp.ConvHalo) -- the frame image would be 9 x / 3 x the activation, written and read back
-            wc = getattr(weight, "_fqss_wcodes_dgrad", None) if (ops.FRAME_CODES_FWD and ops.FRAME_CODES_DGRAD) else None
+            wc = getattr(weight, "_fqss_wcodes_dgrad", None)
             plan = K.HaloPlan(H, W, geom)
             if plan.ok(C, Co, wc is not None) and (wc is None or (wc.idx.is_contiguous() and wc.Ci == C * plan.taps)):
                 z = ops_dp.ConvHalo.apply(x4, ops.weight_view(weight, Co, C, geom.kh, geom.kw), conv.bias, plan, wc)    # (keeps the arena slot)
@@ -686,7 +681,7 @@ def run_convtr1d(convtr, x, weight, aq):
     L = ops._Lin("convtr", stride=convtr.stride[0], w_param=convtr.weight)
     q = aq.qctx() if aq is not None else ops.QCtx()
     q.keep_out = True          # waveform-side outputs are the model's outputs: always real fp32
-    xq = ops.codes_of(x) if (FUSE_DECQ and x.dim() == 3 and K.ola_convtr_ok(weight, convtr.stride[0])) else None
+    xq = ops.codes_of(x) if (x.dim() == 3 and K.ola_convtr_ok(weight, convtr.stride[0])) else None
     if xq is not None and (K.rowmat(xq.idx) is None or K.rowmat(xq.idx)[2] % 16 != 0):
         xq = None
     if xq is None:
@@ -774,7 +769,7 @@ def fq_node(aq, x, nl=None, codes=False, q=None, post_relu=False):
             aq.after_forward(q)
         q.idx = None
         return y if flat is None else y.reshape(x.shape)
-    if FUSE_GLUQ and ops.CODED and isinstance(nl, nn.GLU) and nl.dim == 1 and aq is not None and not codes and torch.is_tensor(x) and x.dim() >= 3:
+    if ops.CODED and isinstance(nl, nn.GLU) and nl.dim == 1 and aq is not None and not codes and torch.is_tensor(x) and x.dim() >= 3:
         # GLU rides in the quantizer's own pass each way (fqss_gluq_fwd / _bwd) in the quantizing and the observer phase
         if q is None:
             q = aq.qctx()
@@ -786,7 +781,7 @@ def fq_node(aq, x, nl=None, codes=False, q=None, post_relu=False):
             aq.after_forward(q)
             q.idx = None
             return y.reshape(xr.shape[0], xr.shape[1] // 2, *xr.shape[2:])
-    gelu = FUSE_GELUQ and ops.CODED and isinstance(nl, nn.GELU) and getattr(nl, "approximate", "none") == "none"
+    gelu = ops.CODED and isinstance(nl, nn.GELU) and getattr(nl, "approximate", "none") == "none"
     if gelu:
         nl = None             # GELU rides in the quantizer's own pass each way (act = ACT_GELU: fqss_actq_fwd / _bwd)
     elif isinstance(nl, (nn.Tanh, nn.Sigmoid, nn.GELU, nn.GLU)):
@@ -816,17 +811,15 @@ def fq_node(aq, x, nl=None, codes=False, q=None, post_relu=False):
     return y
 
 
-FUSE_POSTRELU = __import__("os").environ.get("FQSS_FUSE_POSTRELU", "1") != "0"   # 0: the ReLU behind LSTMQ's quantizer as its own pass
-FUSE_GLUQ = __import__("os").environ.get("FQSS_FUSE_GLUQ", "1") != "0"     # 0: GLU as its own pass in front of the quantizer (A/B, tests)
-FUSE_GELUQ = __import__("os").environ.get("FQSS_FUSE_GELUQ", "1") != "0"   # 0: GELU as its own pass in front of the quantizer (A/B, tests)
-FUSE_ROWQ = __import__("os").environ.get("FQSS_FUSE_ROWQ", "1") != "0"    # 0: row linear, quantizer and bias sums as separate nodes (A/B, tests)
+FUSE_POSTRELU = True   # False: the ReLU behind LSTMQ's quantizer as its own pass (tests patch it)
+FUSE_ROWQ = True       # False: row linear, quantizer and bias sums as separate nodes (tests patch it)
 
 
 def run_linear(lin, x, weight, nl, aq, post_relu=False):
     return linear_fq(x, weight, lin.bias, nl, aq, post_relu)
 
 
-FUSE_NLQ2 = os.environ.get("FQSS_FUSE_NLQ2", "1") != "0"    # LinearQ -> NlQ(ReLU): both quantizers in the int8 GEMM's epilogue
+FUSE_NLQ2 = True    # LinearQ -> NlQ(ReLU): both quantizers in the int8 GEMM's epilogue; False: the two modules one after the other (tests patch it)
 
 
 def _quantizing(aq):
@@ -844,7 +837,7 @@ def linear_then_relu_q(lq, nlq, x):
             and K.colbias_ok(lin.out_features) and _quantizing(aq1) and _quantizing(aq2)):
         weight = lq._wq(lin.weight)
         qops = ops_dp.qrow_operands(x, weight) if weight.dim() == 2 else None
-        if qops is not None and ops_dp.FUSE_QROWQ:
+        if qops is not None:
             q1, q2 = aq1.qctx(), aq2.qctx()
             if q1.qmode != ops.Q_QUANT or q2.qmode != ops.Q_QUANT or q1.gacc is None or q2.gacc is None:
                 raise RuntimeError("linear_then_relu_q: quantizer state changed between the check and qctx()")
@@ -907,7 +900,7 @@ def run_layernorm(ln, x, aq):
 def add_layernorm(norm, a, b):
     """(norm(a + b), a + b) for the float residual add that feeds a pre-norm sub-layer (`x = x + sublayer(...)` followed by `norm(x)`):
     fused into ONE kernel each way (ops_dp.AddLayerNormRows) for an nn.LayerNorm and for a LayerNormQ in the quantizing phase; any
-    other state (observer phase, per-module quantizers without a gacc arena, FQSS_FUSE_ADDLN=0) takes the un-fused pair"""
+    other state (observer phase, per-module quantizers without a gacc arena, FUSE_ADDLN off) takes the un-fused pair"""
     ln = norm.layernorm if isinstance(norm, LayerNormQ) else norm
     a, b = ops.real(a), ops.real(b)
     if FUSE_ADDLN and isinstance(ln, nn.LayerNorm) and len(ln.normalized_shape) == 1 and ln.elementwise_affine:
@@ -932,7 +925,7 @@ def add_layernorm(norm, a, b):
     return norm(s_n), s_res
 
 
-FUSE_LN_LAYOUT = os.environ.get("FQSS_FUSE_LN_LAYOUT", "1") != "0"    # the dual-path layout change inside the AddQ + LayerNormQ kernels
+FUSE_LN_LAYOUT = True    # the dual-path layout change inside the AddQ + LayerNormQ kernels; False: its own pass behind them (tests patch it)
 
 
 def addq_layernorm(add, norm, a, b, then=None):
@@ -966,8 +959,8 @@ def addq_layernorm(add, norm, a, b, then=None):
     return y if then is None else ops_dp.change_layout(y, then[0], then[1])
 
 
-FUSE_ADDLN = __import__("os").environ.get("FQSS_FUSE_ADDLN", "1") != "0"   # residual add + LayerNorm(Q) as one kernel each way
-FUSE_LNQ = __import__("os").environ.get("FQSS_FUSE_LNQ", "1") != "0"     # 0: LayerNorm and its quantizer as separate launches (A/B, tests)
+FUSE_ADDLN = True   # residual add + LayerNorm(Q) as one kernel each way; False: the add, then the norm (tests patch it)
+FUSE_LNQ = True     # False: LayerNorm and its quantizer as separate launches (tests patch it)
 
 
 def _lstm_check(lstm):

@@ -71,12 +71,11 @@ class ParamArena:
                     max_norm, grad_scale, lr, betas[0], betas[1], eps, t0=self.t0)
 
 
-TEACHER_STREAM = os.environ.get("FQSS_TEACHER_STREAM", "1") != "0"
-TEACHER_PRIO = int(os.environ.get("FQSS_TEACHER_PRIO", "0"))        # experiment knob: priority of the teacher stream (0 = default / lowest)
+TEACHER_STREAM = True    # False: the teacher forward on the step's own stream (tests and tools/stress_step.py patch it)
 
 
 def _teacher_stream():
-    return torch.cuda.Stream(priority=TEACHER_PRIO)
+    return torch.cuda.Stream(priority=0)
 
 
 class TeacherRunner:
@@ -148,7 +147,7 @@ class TeacherRunner:
                              pro_eps=sb[5].eps, M1=nfeat, r1=h, r2=acc)
         mask = K.tgemm(pl["mask"], acc, mk.mask_net[1].bias, act=K.ACT_RELU, pro=2, pro_slope=mk.mask_net[0].weight)
         F_ = feats.shape[1]
-        if K.ola_convtr_ok(m.decoder.weight, stride) and os.environ.get("FQSS_FUSE_TMUL", "1") != "0":
+        if K.ola_convtr_ok(m.decoder.weight, stride):
             # the masking product is formed inside the decoder kernel (no [B, S, F, M] intermediate): same values, same sums
             dec = K.ola_convtr_mul_fwd(mask.reshape(B, m.n_srcs, F_, -1), feats, m.decoder.weight, stride)
         else:
@@ -265,7 +264,7 @@ class QuantTables:
             pw = pw or (axis == 0 and w.dim() == 2 and ops_dp.QROW and K.qrow_eligible(shape[1]))
             # convolution weights [Co, Ci, k] / [Co, Ci, kh, kw] of the frame path (HTDemucs): the same code image over Ci * k "channels"
             # serves the DATA gradient alone (ops.LinearActQ: W_q^T gz on k_qgemm<1>); the forward reads float inputs
-            fr = (not pw) and axis == 0 and w.dim() in (3, 4) and shape[0] % 16 == 0 and shape[0] <= 1024 and ops.FRAME_CODES_DGRAD
+            fr = (not pw) and axis == 0 and w.dim() in (3, 4) and shape[0] % 16 == 0 and shape[0] <= 1024
             wc = None
             ldT = C
             if pw and id(w) in partner:
@@ -327,9 +326,10 @@ class QuantTables:
         # grouped, atomics-free weight gradients of the quantized 1x1 convolutions (csrc/qgemm.hip k_qwgrad_group); FQSS_GROUP_WGRAD=0:
         # one k_qwgrad2 launch per layer where autograd reaches it (rounds 2-4)
         self.det = None     # kernels.DetMode of the owning step (FQSS_DETERMINISTIC=1)
-        self.wgrad_queue = K.WgradQueue() if os.environ.get("FQSS_GROUP_WGRAD", "1") != "0" else None
+        grouped = os.environ.get("FQSS_GROUP_WGRAD", "1") != "0"
+        self.wgrad_queue = K.WgradQueue() if grouped else None
         # ... and of the row-major linears of the dual-path / transformer models (csrc/gemm_x3.hip k_gemm_x3_wq_multi)
-        self.row_wgrad_queue = K.RowWgradQueue() if os.environ.get("FQSS_GROUP_WGRAD", "1") != "0" else None
+        self.row_wgrad_queue = K.RowWgradQueue() if grouped else None
         # ---- per-segment views of the two finish tables (descriptor 15 = first block is renumbered per table) -----------------
         self.seg_tables = None
         if segments is not None and len(segments) > 1:
@@ -771,7 +771,7 @@ class KDTrainStep:
         # single rank, one segment: nothing has to happen between the two halves, so the whole step is ALSO captured as one graph
         # (replay() then costs one launch; replay_fwd_bwd / replay_optimize keep serving the trainers that may skip an update)
         self._graph_all = None
-        if not self._exchange() and len(graphs) == 1 and os.environ.get("FQSS_ONE_GRAPH", "1") != "0":
+        if not self._exchange() and len(graphs) == 1:
             ga = torch.cuda.CUDAGraph()
             with torch.cuda.graph(ga, pool=graphs[0].pool()):
                 self.last_all, est, gest, cuts = self._forward_loss(self._sx, self._st, None, fest_cur, False)

@@ -309,11 +309,11 @@ def test_ola_convtr(N, C, M, K_, S):
     # ... and its weight gradient straight from the codes against the generic GEMM on the decoded operand
     gw_q, gw_r = torch.zeros(C, 1, K_, device="cuda"), torch.zeros(C, 1, K_, device="cuda")
     assert K.frames_wgrad1_q(xc, lo, hi, g.cuda(), gw_q, S)
-    os.environ["FQSS_FRAMES_WGRAD1"] = "0"
+    K.FRAMES_WGRAD1 = False
     try:
         K.frames_wgrad(K.decode(xc, lo, hi), g.cuda(), gw_r, S)
     finally:
-        del os.environ["FQSS_FRAMES_WGRAD1"]
+        K.FRAMES_WGRAD1 = True
     close(gw_q, gw_r, rtol=1e-4, atol=1e-5 * float(gw_r.abs().max()) + 1e-5)
     if N % 2 == 0:
         mask, feat = padded(rnd(N // 2, 2, C, M, seed=5)), padded(rnd(N // 2, C, M, seed=6))
