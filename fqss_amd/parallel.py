@@ -41,7 +41,8 @@ class Comm:
     CommError; launch.spawn_ranks / torch.distributed.run see the non-zero exit and end the other ranks.  Either way nothing is retried
     and nothing is restarted in place: a step whose gradients were not averaged must not reach the optimizer, and a process that has initialised the GPU must never
     be replaced by another (no exec on this pool); the rank exits non-zero, torch.distributed.run ends the job, and the job resumes
-    from the last checkpoint (process.py) as a NEW launch."""
+    from the last checkpoint as a NEW launch: every trainer writes the full training state once per epoch (fqss_amd/checkpoint.py,
+    `<work_dir>/checkpoint.pth`) and `python -m fqss_amd.train ... --resume` continues from it."""
 
     def __init__(self, rank=0, world=1, local_rank=0, backend=None, force=False):
         self.rank, self.world, self.local_rank, self.backend = rank, world, local_rank, backend
@@ -92,6 +93,16 @@ class Comm:
         if self.active:
             self._run("broadcast", dist.broadcast, t, src)
         return t
+
+    def all_gather(self, t):
+        """-> [rank 0's t, rank 1's t, ...] as host tensors (small host-side state: the per-rank observer ranges of a checkpoint)"""
+        if not self.active:
+            return [t.cpu()]
+        # RCCL moves device memory only, gloo gathers host memory only
+        src = t.to(torch.device("cuda", torch.cuda.current_device())) if self.backend == "nccl" else t.cpu()
+        out = [torch.empty_like(src) for _ in range(self.world)]
+        self._run("all_gather", dist.all_gather, out, src.contiguous())
+        return [o.cpu() for o in out]
 
     def barrier(self):
         if self.active:

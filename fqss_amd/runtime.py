@@ -51,6 +51,61 @@ class ParamArena:
     def zero_grad(self):
         self.flat_g.zero_()
 
+    # ---- training-state checkpoint (fqss_amd/checkpoint.py) -----------------------------------
+    NEVER = 2 ** 31 - 1         # t0 of an element that has not seen a gradient yet
+
+    def layout(self):
+        """what a stored arena must agree on to be loaded here: parameter names (set by the owning step; positions otherwise), offsets
+        and sizes in the flat buffers"""
+        names = getattr(self, "names", None) or [f"p{i}" for i in range(len(self.params))]
+        return {"names": list(names), "offsets": [int(o) for o in self.offsets], "numel": [int(p.numel()) for p in self.params],
+                "total": int(self.numel)}
+
+    def state_dict(self):
+        """host copies of the parameters, the two Adam moments and both Adam clocks (the device counter step_t, the per-element
+        first-gradient step t0, the host's _host_step), with the layout they belong to.  The gradient buffer is rewritten by every
+        step and is not state."""
+        c = lambda t: t.detach().cpu().clone()
+        return {"layout": self.layout(), "flat_p": c(self.flat_p), "exp_avg": c(self.exp_avg), "exp_avg_sq": c(self.exp_avg_sq),
+                "step_t": c(self.step_t), "t0": c(self.t0), "host_step": int(self._host_step)}
+
+    def load_state_dict(self, sd):
+        """INTO the existing flat buffers: the views that p.data / p.grad hold (and every device table built on their addresses)
+        stay valid.  Parameters are matched BY NAME: the order of the arena follows the gradient buckets (world size, `buckets`), so a
+        file written under another order is copied slice by slice from its offsets to this arena's.  Refused: a file whose set of
+        names or whose size of any parameter differs.  `_inactive` is rebuilt from t0: a parameter is inactive while its elements
+        still sit at INT32_MAX."""
+        mine, theirs = self.layout(), sd["layout"]
+        here, there = dict(zip(mine["names"], mine["numel"])), dict(zip(theirs["names"], theirs["numel"]))
+        if here != there:
+            odd = [n for n in mine["names"] if n not in there] + [n for n in theirs["names"] if n not in here]
+            sized = [f"{n}: {here[n]} here, {there[n]} in the file" for n in mine["names"] if n in there and here[n] != there[n]]
+            raise ValueError(f"ParamArena.load_state_dict: the stored arena layout does not match this model ({len(here)} parameters here, "
+                             f"{len(there)} in the file" + (f"; first differing name: {odd[0]!r}" if odd else "")
+                             + (f"; first differing size: {sized[0]}" if sized else "") + ")")
+        for k in ("flat_p", "exp_avg", "exp_avg_sq", "t0"):
+            if sd[k].dtype != getattr(self, k).dtype or sd[k].numel() != theirs["total"]:
+                raise ValueError(f"ParamArena.load_state_dict: {k} is {tuple(sd[k].shape)} {sd[k].dtype} in the file, expected "
+                                 f"({theirs['total']},) {getattr(self, k).dtype}")
+        with torch.no_grad():
+            if mine == theirs:
+                for k in ("flat_p", "exp_avg", "exp_avg_sq", "t0"):
+                    getattr(self, k).copy_(sd[k])
+            else:
+                # another order: gather on the host into this arena's order (padding: no moments, no clock), one upload per buffer
+                at = dict(zip(theirs["names"], theirs["offsets"]))
+                for k in ("flat_p", "exp_avg", "exp_avg_sq", "t0"):
+                    src = sd[k].cpu()
+                    dst = torch.full((self.numel,), self.NEVER, dtype=src.dtype) if k == "t0" else torch.zeros(self.numel, dtype=src.dtype)
+                    for n, o, m in zip(mine["names"], mine["offsets"], mine["numel"]):
+                        dst[o:o + m] = src[at[n]:at[n] + m]
+                    getattr(self, k).copy_(dst)
+            self.step_t.copy_(sd["step_t"])
+            self.flat_g.zero_()
+        self._host_step = int(sd["host_step"])
+        t0 = self.t0.cpu()
+        self._inactive = [(p, o) for p, o in zip(self.params, self.offsets) if int(t0[o]) == self.NEVER]
+
     def _activate_touched(self):
         if self._inactive:
             still = []
@@ -434,6 +489,7 @@ class KDTrainStep:
         # ---- backward segments = gradient buckets (world > 1 only: a single rank has nothing to overlap) -------------------
         self.segments = None        # [(arena lo, arena hi)] per segment in FORWARD order
         self._seg_ids = None
+        self._sync_ranges = bool(sync_observer_ranges)
         self._ranges_synced = not (sync_observer_ranges and self._exchange())
         params = list(model.parameters())
         # FQSS_FORCE_BUCKETS=1 with a forced one-rank communicator (FQSS_FORCE_DIST=1): the bucketed schedule of world > 1 at world 1
@@ -456,6 +512,8 @@ class KDTrainStep:
                 self._seg_ids[0] |= {id(p) for p in rest}
                 params = rest + ordered
         self.arena = ParamArena(params)
+        name_of = {id(p): n for n, p in model.named_parameters()}
+        self.arena.names = [name_of[id(p)] for p in self.arena.params]       # the layout a stored arena is checked against
         # FQSS_DETERMINISTIC=1: bit-reproducible gradients (kernels.DetMode; no effect on the values beyond fp32 summation order)
         self.det = None
         if os.environ.get("FQSS_DETERMINISTIC", "0") == "1" and not self.cpu:
@@ -493,6 +551,95 @@ class KDTrainStep:
         if getattr(self, "_lr", None) != value:
             self._graphs = None
         self._lr = value
+
+    # ---- training-state checkpoint (fqss_amd/checkpoint.py; DESIGN.md "Resuming a run") ---------------------------------------
+    def _quantizers(self):
+        """(module path, module) of the activation and of the weight quantizers, in module order"""
+        from .quantization.qat.qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize
+        named = list(self.model.named_modules())
+        return ([(n, m) for n, m in named if isinstance(m, GradientActivationFakeQuantize)],
+                [(n, m) for n, m in named if isinstance(m, GradientWeightFakeQuantize)])
+
+    def _ranks_differ(self):
+        """world > 1: the ranks hold different activation ranges -- inside the observer phase until _maybe_sync_ranges has averaged
+        them, and for good where that synchronisation was declined (sync_observer_ranges=False)"""
+        return self._world() > 1 and (not self._sync_ranges or not self._ranges_synced)
+
+    def state_dict(self):
+        """Everything that says where this QAT run stands, as host tensors and plain Python values: the arena (parameters, Adam moments
+        and clocks), the host state of every quantizer by module path (activation: n_iter, observer_mode, sign; weight: observer_mode),
+        _ranges_synced, the learning rate, the student's buffers and the parameters the arena does not hold (requires_grad False).
+        While the ranks' activation ranges differ, every rank's ranges and n_iter travel too (`rank_ranges`, [world, quantizers, 3]
+        int32 words: the bits of min and max, n_iter) -- which makes this a COLLECTIVE call at world > 1: every rank calls it, every rank
+        gets the same `rank_ranges`.  Not stored: QuantTables, graphs and look-ahead results (rebuilt by the next eager quantizing step
+        and maybe_capture), and the integer shadows of FQSS_DETERMINISTIC=1, which are empty between steps."""
+        aqs, wqs = self._quantizers()
+        c = lambda t: t.detach().cpu().clone()
+        held = {id(p) for p in self.arena.params}
+        rank_ranges = None
+        if self._ranks_differ() and aqs:
+            mine = torch.stack([torch.cat([m.min_range.data.reshape(1), m.max_range.data.reshape(1)]).view(torch.int32) for _, m in aqs])
+            mine = torch.cat([mine.cpu(), torch.tensor([[int(m.n_iter)] for _, m in aqs], dtype=torch.int32)], 1)
+            rank_ranges = torch.stack(self.comm.all_gather(mine))
+        return {"arena": self.arena.state_dict(),
+                "act_quantizers": {n: {"n_iter": int(m.n_iter), "observer_mode": bool(m.observer_mode), "sign": bool(m.sign)} for n, m in aqs},
+                "weight_quantizers": {n: {"observer_mode": bool(m.observer_mode)} for n, m in wqs},
+                "ranges_synced": bool(self._ranges_synced), "lr": float(self.lr), "world": int(self._world()),
+                "rank_ranges": rank_ranges,
+                "buffers": {n: c(b) for n, b in self.model.named_buffers()},
+                "frozen": {n: c(p) for n, p in self.model.named_parameters() if id(p) not in held}}
+
+    def load_state_dict(self, sd):
+        """into a step built like the one that was stored (same model structure, any fresh initialisation).  A file written while the
+        ranks' ranges differed resumes at the SAME world size only, each rank taking its own ranges and n_iter; any other file serves
+        any world size and any `buckets` (the arena is loaded by parameter name, whatever order the gradient buckets gave it).  Tables, graphs and look-ahead state are dropped: the next step runs eagerly, rebuilds the QuantTables (and
+        starts no Adam clock again -- t0 is restored), and maybe_capture records the graphs afresh."""
+        aqs, wqs = self._quantizers()
+        for kind, have, want in (("activation", aqs, sd["act_quantizers"]), ("weight", wqs, sd["weight_quantizers"])):
+            if [n for n, _ in have] != list(want):
+                odd = sorted(set(want) ^ {n for n, _ in have})
+                raise ValueError(f"KDTrainStep.load_state_dict: the stored {kind} quantizers are not this model's "
+                                 f"({len(want)} in the file, {len(have)} here; e.g. {odd[:3]})")
+        rr = sd.get("rank_ranges")
+        if rr is not None and int(sd["world"]) != self._world():
+            raise ValueError(f"KDTrainStep.load_state_dict: this state was written at world size {int(sd['world'])} while the ranks still "
+                             f"held their own observer ranges; it resumes at that world size only, not at {self._world()}")
+        buffers, frozen = dict(self.model.named_buffers()), {n: p for n, p in self.model.named_parameters()}
+        for kind, have, want in (("buffers", buffers, sd["buffers"]), ("frozen parameters", frozen, sd["frozen"])):
+            bad = [n for n, t in want.items() if n not in have or have[n].shape != t.shape]
+            if bad or (kind == "buffers" and set(have) != set(want)):
+                raise ValueError(f"KDTrainStep.load_state_dict: the stored {kind} are not this model's (e.g. {(bad or sorted(set(have) ^ set(want)))[:3]})")
+        self.arena.load_state_dict(sd["arena"])
+        with torch.no_grad():
+            for n, t in sd["buffers"].items():
+                buffers[n].copy_(t)
+            for n, t in sd["frozen"].items():
+                frozen[n].data.copy_(t)
+            if rr is not None:
+                own = rr[self.comm.rank]
+                for i, (_, m) in enumerate(aqs):
+                    m.min_range.data.copy_(own[i, 0:1].view(torch.float32))
+                    m.max_range.data.copy_(own[i, 1:2].view(torch.float32))
+        for i, (n, m) in enumerate(aqs):
+            q = sd["act_quantizers"][n]
+            m.n_iter, m.observer_mode, m.sign = int(q["n_iter"] if rr is None else rr[self.comm.rank][i, 2]), bool(q["observer_mode"]), bool(q["sign"])
+            m._fqss_deferred = False        # (a step that had tables: its range gradients are flushed per module until new tables exist)
+        for n, m in wqs:
+            m.observer_mode = bool(sd["weight_quantizers"][n]["observer_mode"])
+        self.lr = float(sd["lr"])
+        # is the one-time averaging of the observer ranges still due?
+        if not (self._sync_ranges and self._exchange()):
+            self._ranges_synced = True              # one rank, or a launch that declined the synchronisation: never
+        elif rr is not None:
+            self._ranges_synced = False             # the file holds per-rank ranges: the ranks differ until the phase ends
+        elif not self.can_capture():
+            self._ranges_synced = False             # one copy written INSIDE the observer phase (a world-1 file): the ranks part ways from here
+        else:
+            # one copy written past the phase: a world-N file says whether its ranks had averaged (True by then); a world-1 file says
+            # True, and every rank starts from its identical ranges -- nothing to average
+            self._ranges_synced = bool(sd["ranges_synced"])
+        self.tables, self._graphs, self._graph_all, self._tgraph, self._ahead, self._ahead_key = None, None, None, None, None, None
+        self._eager_q, self._odd, self.last = 0, 0, None
 
     def can_capture(self):
         from .quantization.qat.qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize

@@ -16,6 +16,9 @@ def argument_handler():
     p.add_argument("--use_cpu", action="store_true", help="Use cpu")
     p.add_argument("--local_rank", type=int, default=0, help="Rank ID")
     p.add_argument("--distributed_launch", action="store_true", help="Multi-GPU training")
+    p.add_argument("--resume", nargs="?", const="auto", default=None, metavar="PATH",
+                   help="Continue from a training-state checkpoint (fqss_amd/checkpoint.py); without PATH: <work_dir>/checkpoint.pth "
+                        "if it exists, a fresh start otherwise.  Sets the environment's `resume` key")
     return p.parse_args()
 
 
@@ -38,14 +41,14 @@ def train():
             return
     if args.env_name == "asteroid":
         from .train_env.asteroid_librimix import asteroid_librimix_trainer
-        asteroid_librimix_trainer.train(args.yml_path, device)
+        asteroid_librimix_trainer.train(args.yml_path, device, resume=args.resume)
     elif args.env_name == "speechbrain":
         from .train_env.speechbrain_librimix import speechbrain_librimix_trainer
-        speechbrain_librimix_trainer.train(args.yml_path, args.local_rank, args.distributed_launch, device)
+        speechbrain_librimix_trainer.train(args.yml_path, args.local_rank, args.distributed_launch, device, resume=args.resume)
     elif args.env_name == "htdemucs":
         from .train_env.htdemucs_musdbhq import train as htdemucs_musdbhq_trainer
         # the reference hands the device to its hydra entry point as an override (train.py:44-46); -y selects the YAML here
-        sys.argv[1:] = ["+device=" + device, "+yml_path=" + args.yml_path]
+        sys.argv[1:] = ["+device=" + device, "+yml_path=" + args.yml_path] + (["+resume=" + args.resume] if args.resume else [])
         htdemucs_musdbhq_trainer.main()
     elif args.env_name == "tasnet":
         raise NotImplementedError("env tasnet (ConvTasNetMusic on MUSDB) is outside SURVEY.md §8")

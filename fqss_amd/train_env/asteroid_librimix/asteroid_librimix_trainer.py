@@ -1,7 +1,8 @@
 """`train(yml_path, device)` of the asteroid env (reference: asteroid_librimix_trainer.py:140-214),
 MI355X edition: same YAML keys (work_dir, model_cfg{,.quantization}, dataset_cfg, training_cfg), same
 outputs (conf.yml, latest_model.pth, best_model.pth = student state_dict), data-parallel over the
-GPUs of one node when launched with torch.distributed.run (one process per GPU, RCCL).
+GPUs of one node when launched with torch.distributed.run (one process per GPU, RCCL).  Every epoch also ends with
+`<work_dir>/checkpoint.pth`, the full training state; `training_cfg.resume: <path> | auto` continues from one (fqss_amd/checkpoint.py).
 
 Data: `dataset_cfg.name: librimix` is the reference's own configuration (configs/convtasnet_2spks_8k.yaml:27-41): `prepare_datasets`
 builds the LibriMix CSV datasets exactly as asteroid_librimix_trainer.py:26-75 does and feeds them through a background reader
@@ -13,6 +14,7 @@ import os
 import torch
 import yaml
 
+from ... import checkpoint
 from ...data import synth_batch
 from ...loader import Prefetcher, epoch_batches, with_lookahead
 from ...parallel import Comm
@@ -80,17 +82,18 @@ class _Data:
         return self._synthetic("val") if self.synthetic else self._files("val", epoch)
 
 
-def train(yml_path, device):
+def train(yml_path, device, resume=None):
+    """resume: a training-state checkpoint to continue from, or "auto" (`--resume` of fqss_amd.train); overrides `training_cfg.resume`"""
     from ... import _lib
     prev = _lib.BACKEND
     try:
-        return _train(yml_path, device)
+        return _train(yml_path, device, resume)
     finally:
         if _lib.BACKEND != prev:          # `--use_cpu` switched the process to the CPU backend: hand it back as it was found
             _lib.set_backend(prev)
 
 
-def _train(yml_path, device):
+def _train(yml_path, device, resume=None):
     cpu = device == "cpu"
     if cpu:
         # `--use_cpu` (reference train.py:31; BASELINE.json configs[0]: "CPU, batch 2, 1 s ... plumbing, no GPU"): the same trainer over
@@ -104,6 +107,14 @@ def _train(yml_path, device):
     training_cfg = conf["training_cfg"]
     set_seed(training_cfg.get("seed", 0))
     comm = Comm.from_env("cpu" if cpu else "cuda")
+    # `training_cfg.resume: <path> | auto`: continue from the full training state an earlier launch left (fqss_amd/checkpoint.py)
+    if resume is not None:
+        training_cfg["resume"] = resume
+    ckpt = checkpoint.resume_path(training_cfg.get("resume"), work_dir)
+    ckpt = checkpoint.load_training_state(ckpt) if ckpt else None
+    if ckpt is not None and ckpt["trainer"]["epoch"] >= training_cfg["epochs"]:
+        comm.barrier()
+        return ckpt["trainer"]["history"]           # the run had finished: nothing is built, nothing is written
     dev = torch.device("cpu") if cpu else torch.device("cuda", comm.local_rank)
     if not cpu:
         torch.cuda.set_device(dev)
@@ -111,6 +122,11 @@ def _train(yml_path, device):
         raise NotImplementedError("--use_cpu: the CPU backend serves the ConvTasNet step (cfg 1 of BASELINE.json) only")
 
     model_cfg.update({"model_path": training_cfg.get("pretrained", None)})
+    pre = model_cfg["model_path"]
+    if ckpt is not None and pre is not None and not str(pre).startswith("https") and not os.path.exists(pre):
+        # the checkpoint holds the student AND the teacher: a pretrained file that has moved since the first launch is not needed
+        print(f"Resuming: pretrained file {pre} is gone; the teacher comes from the checkpoint")
+        model_cfg["model_path"] = None
     model, fmodel = create_pretrained_model(model_cfg)
     model.to(dev).train()
     fmodel.to(dev).eval()
@@ -134,12 +150,22 @@ def _train(yml_path, device):
                     teacher_ahead=ahead)
     global LAST_SYSTEM
     LAST_SYSTEM = system                # tools / tests: the stepper of the run that just finished (its graphs, its model)
-    best, history, since_best = float("inf"), [], 0
+    best, history, since_best, first_epoch = float("inf"), [], 0, 0
     # schedulers of train_setup (asteroid_librimix_trainer.py:96-102): StepLR for `step_lr` (DPTNet config), ReduceLROnPlateau
     # (factor 0.5) for `half_lr`; both act once per epoch on the stepper's learning rate
     step_lr, half_lr = training_cfg.get("step_lr"), training_cfg.get("half_lr", False)
     base_lr, plateau_best, plateau_bad = opt.get("lr", 1e-3), float("inf"), 0
-    for epoch in range(training_cfg["epochs"]):
+    if ckpt is not None:
+        # student, arena, quantizer state (the stored per-quantizer observer flags, not the YAML's `observer`), learning rate, teacher
+        # and random streams from the file; then this loop's own bookkeeping.  StepLR needs nothing stored beyond the epoch number.
+        ts = checkpoint.restore(ckpt, system.stepper, fmodel)
+        best, since_best, first_epoch, history = ts["best"], ts["since_best"], ts["epoch"], list(ts["history"])
+        plateau_best, plateau_bad = ts["plateau_best"], ts["plateau_bad"]
+        if comm.rank == 0:
+            print(f"Resuming after epoch {first_epoch}: best val_loss {best}, lr {system.stepper.lr}", flush=True)
+    for epoch in range(first_epoch, training_cfg["epochs"]):
+        if training_cfg.get("early_stop", False) and since_best >= 30:      # (a resumed run that had stopped early stays stopped)
+            break
         import time
         t_epoch, n_steps = time.perf_counter(), 0
         for i, (x, tgt, x_next) in enumerate(data.train(epoch)):
@@ -172,6 +198,9 @@ def _train(yml_path, device):
         # EarlyStopping(monitor="val_loss", mode="min", patience=30) of train_setup (:117-118); every rank sees the same reduced `val`
         since_best = 0 if val < best else since_best + 1
         best = min(best, val)
+        checkpoint.save_training_state(os.path.join(work_dir, checkpoint.NAME), system.stepper,
+                                       dict(epoch=epoch + 1, best=best, since_best=since_best, plateau_best=plateau_best,
+                                            plateau_bad=plateau_bad, history=history), fmodel)
         if training_cfg.get("early_stop", False) and since_best >= 30:
             if comm.rank == 0:
                 print(f"Early stopping: val_loss has not improved for {since_best} epochs")

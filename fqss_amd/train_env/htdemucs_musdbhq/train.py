@@ -11,7 +11,9 @@ reference always reads configs/htdemucs.yaml through hydra.  Step semantics kept
     optional clip_grad; Adam(lr, betas (momentum, beta2)); global batch divided over the ranks (train.py:200-201), gradients
     averaged over ranks;
   * valid: eval mode on the validation stems, `reco` = source-weighted L1; the best state by `test.metric: loss` is written to
-    `<work_dir>/best.th` as {"state", "kwargs", "history"} (the keys load_model.py:38-45, 76-102 read back).
+    `<work_dir>/best.th` as {"state", "kwargs", "history"} (the keys load_model.py:38-45, 76-102 read back);
+  * every epoch ends with `<work_dir>/checkpoint.pth`, the full training state (the place of the solver's checkpoint.th); `resume=<path>`
+    or `resume=auto` continues from one (fqss_amd/checkpoint.py).
 Data: `dset.name: synthetic` (seeded Gaussian stems); MUSDB readers, demucs' augmentations (shift / flip / scale / remix /
 repitch), EMA copies, `apply_model` split inference and the SDR evaluation are the reference's CPU / third-party data side."""
 import json
@@ -21,6 +23,7 @@ import sys
 import torch
 import yaml
 
+from ... import checkpoint
 from ...parallel import Comm, local_device
 from ...quantization.qat.models.load_model import quantize_model
 from ...quantization.qat.models.htdemucsq import HTDemucsQ
@@ -73,6 +76,15 @@ class Solver:
                                 betas=(float(opt.get("momentum", 0.9)), float(opt.get("beta2", 0.999))))
         self.history = []
         self.best_state, self.best_loss = None, float("inf")
+        self.ckpt_file = os.path.join(conf["work_dir"], checkpoint.NAME)
+
+    def restore(self, ckpt):
+        """student, arena, quantizer state, learning rate, teacher and random streams from a training-state checkpoint; then the
+        solver's own fields.  The next epoch is len(history)."""
+        ts = checkpoint.restore(ckpt, self.step, self.fmodel)
+        self.history, self.best_loss, self.best_state = list(ts["history"]), ts["best_loss"], ts["best_state"]
+        if self.comm.rank == 0:
+            print(f"Resuming after epoch {len(self.history)}: best {self.best_loss}", flush=True)
 
     def _batch(self, epoch, idx, train):
         d = self.conf["dset"]
@@ -104,7 +116,7 @@ class Solver:
         return out
 
     def train(self):
-        for epoch in range(self.conf["epochs"]):
+        for epoch in range(len(self.history), self.conf["epochs"]):
             m = {"train": self._run_one_epoch(epoch), "valid": self._run_one_epoch(epoch, train=False)}
             self.model.train()
             key = self.conf.get("test", {}).get("metric", "loss")
@@ -123,10 +135,13 @@ class Solver:
                            os.path.join(self.conf["work_dir"], "best.th"))
                 with open(os.path.join(self.conf["work_dir"], "history.json"), "w") as f:
                     json.dump(self.history, f)
+            checkpoint.save_training_state(self.ckpt_file, self.step, dict(epoch=epoch + 1, history=self.history, best_loss=self.best_loss,
+                                                                           best_state=self.best_state), self.fmodel)
         return self.history
 
 
-def get_solver(conf):
+def get_solver(conf, ckpt=None):
+    """ckpt: a loaded training-state checkpoint to continue from (main() resolves the `resume` key)"""
     import copy
     device = conf.get("device", "cuda")
     if device != "cuda" or not torch.cuda.is_available():
@@ -150,12 +165,20 @@ def get_solver(conf):
     model = quantize_model(model, mc["quantization"]).to(dev).train()
     model._init_kwargs = kwargs
     assert conf["batch_size"] % comm.world == 0
-    return Solver(conf, model, fmodel, comm, dev)
+    solver = Solver(conf, model, fmodel, comm, dev)
+    if ckpt is not None:
+        solver.restore(ckpt)
+    return solver
 
 
 def main():
     conf = load_config(sys.argv[1:])
-    solver = get_solver(conf)
+    # `resume=<path> | auto`: a run that had finished returns its stored history -- nothing is built, nothing is written
+    ckpt = checkpoint.resume_path(conf.get("resume"), conf["work_dir"])
+    ckpt = checkpoint.load_training_state(ckpt) if ckpt else None
+    if ckpt is not None and ckpt["trainer"]["epoch"] >= conf["epochs"]:
+        return ckpt["trainer"]["history"]
+    solver = get_solver(conf, ckpt)
     hist = solver.train()
     solver.comm.close()
     return hist

@@ -17,7 +17,9 @@ plain mappings and ignored.  Step semantics kept:
     from speechbrain 0.5.14's published behaviour: third-party, parity unpinned).
 Data: `dataset_cfg.name: librimix` is the reference's configuration (configs/sepformer_2spks_8k.yaml:27-39): `prepare_librimix` writes
 the CSVs into `save_folder`, `SbLibriMix` (prepare_data.py) serves whole utterances with the train-time speed perturbation / re-mix /
-random cut of `compute_forward` on the device, a batch ahead of the step (fqss_amd/loader.py); `synthetic`: seeded 2-speaker mixtures."""
+random cut of `compute_forward` on the device, a batch ahead of the step (fqss_amd/loader.py); `synthetic`: seeded 2-speaker mixtures.
+Every epoch ends with `<work_dir>/checkpoint.pth`, the full training state (what speechbrain's Checkpointer keeps); the top-level
+key `resume: <path> | auto` continues from one (fqss_amd/checkpoint.py)."""
 import json
 import os
 import re
@@ -25,6 +27,7 @@ import re
 import torch
 import yaml
 
+from ... import checkpoint
 from ...data import synth_batch
 from ...loader import Prefetcher, epoch_batches
 from ...parallel import Comm
@@ -158,10 +161,13 @@ class _Data:
         self.loader_wait_s += pf.wait_s
 
 
-def train(yml_path, local_rank=0, distributed_launch=False, device="cuda"):
+def train(yml_path, local_rank=0, distributed_launch=False, device="cuda", resume=None):
+    """resume: a training-state checkpoint to continue from, or "auto" (`--resume` of fqss_amd.train); overrides the YAML's `resume`"""
     if device == "cpu":
         raise RuntimeError("fqss_amd is MI355X-only (no CPU fallback); the CPU checker lives in oracle/")
     hp = load_hparams(yml_path)
+    if resume is not None:
+        hp["resume"] = resume
     if int(hp.get("batch_size", 1)) not in (1, 2):
         raise ValueError("speechbrain env: per-GPU batch_size must be 1 or n_src = 2 (the reference's KD weights broadcast "
                          "[1, n_src, n_src] * [1, B] and raise for any other batch)")
@@ -169,6 +175,13 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda"):
     comm = Comm.from_env("cuda")
     dev = torch.device("cuda", comm.local_rank)
     torch.cuda.set_device(dev)
+    work_dir = hp["work_dir"]
+    ckpt_file = os.path.join(work_dir, checkpoint.NAME)       # beside train_log.txt: `save/` keeps exactly the files it always held
+    ckpt = checkpoint.resume_path(hp.get("resume"), work_dir)
+    ckpt = checkpoint.load_training_state(ckpt) if ckpt else None
+    if ckpt is not None and ckpt["trainer"]["epoch"] >= int(hp["N_epochs"]):
+        comm.barrier()
+        return ckpt["trainer"]["history"]           # the run had finished: nothing is built, nothing is written
     model_cfg = hp["model_cfg"]
     model = create_model(model_cfg)
     kd_lambda = float(hp.get("kd_lambda", 0))
@@ -177,7 +190,6 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda"):
     import copy
     fmodel = copy.deepcopy(model).to(dev).eval()            # float teacher BEFORE quantization (:625-629)
     model = quantize_model(model, model_cfg["quantization"]).to(dev).train()
-    work_dir = hp["work_dir"]
     if comm.rank == 0:
         os.makedirs(os.path.join(work_dir, "save"), exist_ok=True)
     lr = float(hp.get("lr", 1.5e-4))
@@ -188,10 +200,17 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda"):
                        loss="sisdr_pit_per_sample", loss_threshold=threshold)
     sch = hp.get("lr_scheduler") or {}
     sched = ReduceLROnPlateau(sch.get("factor", 0.5), sch.get("patience", 2), sch.get("dont_halve_until_epoch", 65))
-    history, best, nonfinite = [], float("inf"), 0
+    history, best, nonfinite, done = [], float("inf"), 0, 0
     flag = torch.zeros(1, device=dev)
     data = _Data(hp, comm, dev)
-    for epoch in range(1, int(hp["N_epochs"]) + 1):
+    if ckpt is not None:
+        # student, arena, quantizer state, learning rate, teacher and random streams from the file; then the loop's own bookkeeping
+        ts = checkpoint.restore(ckpt, step, fmodel)
+        history, best, nonfinite, done = list(ts["history"]), ts["best"], ts["nonfinite"], ts["epoch"]
+        sched.patience_counter, sched.losses, sched.anchor = ts["sched"]["patience_counter"], list(ts["sched"]["losses"]), ts["sched"]["anchor"]
+        if comm.rank == 0:
+            print(f"Resuming after epoch {done}: best valid_si-snr {best}, lr {step.lr}", flush=True)
+    for epoch in range(done + 1, int(hp["N_epochs"]) + 1):
         losses = []
         for x, tgt in data.batches("train", epoch):
             step.maybe_capture(x, tgt)        # quantizing phase: both halves of the step replay as hipGraphs
@@ -230,7 +249,10 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda"):
             sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
             torch.save(sd, os.path.join(work_dir, "save", "latest_model.pth"))
             if val < best:
-                best = val
                 torch.save(sd, os.path.join(work_dir, "save", "best_model.pth"))
+        best = min(best, val)                       # (every rank: the reduced `val` is the same everywhere)
+        checkpoint.save_training_state(ckpt_file, step, dict(
+            epoch=epoch, best=best, nonfinite=nonfinite, history=history,
+            sched=dict(patience_counter=sched.patience_counter, losses=list(sched.losses), anchor=sched.anchor)), fmodel)
     comm.barrier()
     return history
