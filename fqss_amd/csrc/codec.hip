@@ -9,8 +9,6 @@
 // Reference replaced: process.preprocess (process.py:16-37); F.conv1d(k=16,s=8) of Conv1dEncoderQ /
 // ResidualErrorBlock (qat_layers.py:1028-1039, 1189-1192); F.conv_transpose1d of ConvTr1dDecoderQ /
 // ResidualErrorBlock (qat_layers.py:1330-1341, 1194-1202) and their autograd.
-#include <cstdlib>
-
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
 #include "fqss_dev.h"
 
@@ -147,15 +145,12 @@ __global__ __launch_bounds__(256) void k_frames_conv4(const float* __restrict__ 
         }
     }
     constexpr int PF = 8;      // output channels per group: the addend rows of a group are requested before its FMAs start
-    const int ct = co_tile < 0 ? Co : co_tile;
     const int co_lo = (int)blockIdx.z * co_per, co_hi = min(Co, co_lo + co_per);
-    for (int cb = co_lo; cb < co_hi; cb += ct) {
-        const int ce = min(co_hi, cb + ct);
-        if (co_tile > 0) {
+    for (int cb = co_lo; cb < co_hi; cb += co_tile) {
+        const int ce = min(co_hi, cb + co_tile);
         if (cb > co_lo) __syncthreads();   // every wave is done with the previous tile's taps
         for (int i = threadIdx.x; i < (ce - cb) * CK; i += 256) Wl[i] = w[(int64_t)cb * CK + i];
         __syncthreads();
-        }
         for (int cg = cb + wave; cg < ce; cg += 4 * PF) {
             float4 a4[PF];
             if (add != nullptr) {
@@ -170,16 +165,10 @@ __global__ __launch_bounds__(256) void k_frames_conv4(const float* __restrict__ 
                 const int co = cg + 4 * i;
                 if (co >= ce) break;       // wave-uniform
                 float wk[CK];
-                if (co_tile < 0) {           // taps straight from memory (wave-uniform): the A/B form
-                    const float* wr = w + (int64_t)co * CK;
-#pragma unroll
-                    for (int j = 0; j < CK; ++j) wk[j] = wr[j];
-                } else {
 #pragma unroll
                 for (int j4 = 0; j4 < CK / 4; ++j4) {
                     const float4 t = *reinterpret_cast<const float4*>(&Wl[(co - cb) * CK + 4 * j4]);
                     wk[4 * j4] = t.x; wk[4 * j4 + 1] = t.y; wk[4 * j4 + 2] = t.z; wk[4 * j4 + 3] = t.w;
-                }
                 }
                 float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -499,8 +488,6 @@ static int frames_conv_impl(const char* who, const float* x, const float* w, flo
         int co_tile = (int)((48 * 1024) / ((size_t)Ci * K * sizeof(float))) & ~3;      // output channels whose taps fit 48 KB of LDS
         if (co_tile > Co) co_tile = (Co + 3) & ~3;
         size_t lds = (size_t)co_tile * Ci * K * sizeof(float);
-        static const int taps_lds = [] { const char* e = getenv("FQSS_TAPS_LDS"); return e ? atoi(e) : 1; }();   // A/B switch
-        if (!taps_lds) { co_tile = -1; lds = 0; }       // taps by wave-uniform loads from memory
         if ((k16 || k32) && (Ci == 1 || Ci == 2) && aligned16(x) && T % 4 == 0 && T >= 4 && aligned16(z) && ld_z % 4 == 0 &&
             ld_z >= m4 && (!add || (aligned16(add) && ld_add % 4 == 0 && ld_add >= m4))) {
             // slices of the output channels in grid.z until ~512 workgroups are in flight (>= 32 channels per slice)

@@ -44,11 +44,6 @@ static inline dim3 grid_rows(int64_t rows, int64_t cols, int vec, int64_t max_bl
 constexpr int kXcds = 8;
 static inline unsigned xcd_grid(int64_t groups, int64_t per_group) { return (unsigned)(cdiv(groups, kXcds) * kXcds * per_group); }
 
-// the data-gradient q-GEMM on the LDS ring (csrc/qgemm_ring.hip), dispatched from csrc/qgemm.hip where its shape rules hold
-bool qdgrad_ring_ok(int Ci, int Co1, int Co2);
-int qdgrad_ring(const char* who, const float* gz1, const float* gz2, const int8_t* wiT, const float* dw, const float* addend, float* gx, int B,
-                int Ci, int Co1, int Co2, int M, int64_t ld_gz1, int64_t ld_gz2, int64_t ld_add, int64_t ld_gx, fqss_stream_t stream);
-
 // ---------------------------------------------------------------- device side
 #if defined(__HIPCC__)
 __device__ __forceinline__ bool xcd_tile(int groups, int per_group, int& group, int& idx) {
@@ -91,11 +86,6 @@ __device__ __forceinline__ T dpp_get(T v) {
 }
 template <typename T>
 __device__ __forceinline__ T wave_sum63(T v) {
-#ifdef FQSS_NO_DPP_SUMS
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-#else
     v += dpp_get<0xB1>(v);          // quad_perm:[1,0,3,2]
     v += dpp_get<0x4E>(v);          // quad_perm:[2,3,0,1]
     v += dpp_get<0x141>(v);         // row_half_mirror
@@ -103,7 +93,6 @@ __device__ __forceinline__ T wave_sum63(T v) {
     v += dpp_get<0x142, 0xa>(v);    // row_bcast:15 into rows 1 and 3
     v += dpp_get<0x143, 0xc>(v);    // row_bcast:31 into rows 2 and 3
     return v;
-#endif
 }
 
 // lane 63's value in every lane (v_readlane_b32: through a scalar register)

@@ -386,7 +386,6 @@ struct GemmArgs3 {          // keep in sync with csrc/gemm_x3.hip
     int imp_kw, imp_rowshift;
     const unsigned short* Bp;
     int64_t ldp;
-    int scalar_stores;
     float* rowsum_out;
 };
 int launch_gemm_x3_imp(const GemmArgs3& g, bool wgrad, hipStream_t s, const char* what);
@@ -403,7 +402,7 @@ static int try_x3(const GemmArgs& g, bool a_kc, bool b_kc, bool atomic, hipStrea
     *used = false;
     if (batch > 1 && (g.sAb % 4 != 0 || g.sBb % 4 != 0)) return FQSS_OK;      // every batch's operand 16-B aligned
     GemmArgs3 h{g.A, g.B, g.C, g.bias, g.bias_col, g.M, g.N, g.K, g.sAi, g.sAk, g.sBk, g.sBj, g.sCi, g.ksplit, g.kchunk, nullptr, nullptr, nullptr, nullptr,
-                batch, g.sAb, g.sBb, g.sCb, 0, 0, 0, 0, 0, 0, nullptr, 0, 0};
+                batch, g.sAb, g.sBb, g.sCb, 0, 0, 0, 0, 0, 0, nullptr, 0};
     return launch_gemm_x3(h, a_kc, b_kc, atomic, s, what, used);
 }
 

@@ -14,7 +14,6 @@
 // coalesced float4 loads along the contiguous dimension, then one 8-B LDS write per row and plane.
 // Measured dead end: k-tiles of 16 with two LDS buffers and one barrier per tile (split + store of tile kt+1 under the MFMAs of
 // tile kt) -- 5-12 % SLOWER than this single-buffered k-tile of 32 at the dual-path shapes (60 -> 66 us for 8500 x 256 x 1024).
-#include <stdlib.h>
 #include <type_traits>
 
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
@@ -57,7 +56,6 @@ struct GemmArgs3 {
     // weight that does not change between launches: the frozen teacher's linears) -- the tile is copied, not split
     const unsigned short* Bp;
     int64_t ldp;
-    int scalar_stores;       // 1: the lane-per-column epilogue (FQSS_X3_STAGED=0, A/B measurements)
     float* rowsum_out;       // BQ = 1, optional: sum_k A(i, k) is ADDED here ([M]: the bias gradient of the linear whose weight gradient this is)
 };
 
@@ -437,7 +435,7 @@ __device__ __forceinline__ void x3_body(GemmArgs3 g, const int bx, const int by,
         // (the lane-per-column layout needs 16 strided 4-B stores per tile: that store-issue-bound tail was most of this kernel's time at
         // the skinny reductions of the dual-path linears, K = 256: 8 k-tiles of MFMAs against 64 scalar stores per thread).  Needs
         // 16-B aligned output rows; the scalar path below serves everything else.
-        if (!g.scalar_stores && (g.sCi & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15u) == 0) {
+        if ((g.sCi & 3) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15u) == 0) {
             constexpr int TLD = 36;                                    // floats per staged row (16-B aligned, conflict-light)
             static_assert(4 * 32 * TLD * 4 <= kBytesLds, "staging tiles fit the operand planes");
             float(*Tt)[TLD] = reinterpret_cast<float(*)[TLD]>(reinterpret_cast<float*>(lds_raw) + wave * 32 * TLD);
@@ -556,14 +554,7 @@ static bool x3_ok(const GemmArgs3& g, bool a_kc, bool b_kc, bool atomic) {
     return ok;
 }
 
-static int x3_scalar_stores() {
-    static const int v = [] { const char* e = getenv("FQSS_X3_STAGED"); return (e && e[0] == '0') ? 1 : 0; }();
-    return v;
-}
-
-int launch_gemm_x3(const GemmArgs3& g_in, bool a_kc, bool b_kc, bool atomic, hipStream_t s, const char* what, bool* used) {
-    GemmArgs3 g = g_in;
-    g.scalar_stores = x3_scalar_stores();
+int launch_gemm_x3(const GemmArgs3& g, bool a_kc, bool b_kc, bool atomic, hipStream_t s, const char* what, bool* used) {
     *used = false;
     if (g.M <= 0 || g.N <= 0) return FQSS_OK;
     if (!x3_ok(g, a_kc, b_kc, atomic)) return FQSS_OK;     // caller falls back to k_gemm_f32
@@ -608,9 +599,7 @@ int launch_gemm_x3(const GemmArgs3& g_in, bool a_kc, bool b_kc, bool atomic, hip
 
 // implicit stride-1 convolution forms: forward / data gradient (A = weight [Co][Ci * taps], k contiguous; B implicit, positions
 // contiguous) and weight gradient (A = gz [Co][positions]; B implicit with (channel, tap) rows; split-K + atomics, batches added)
-int launch_gemm_x3_imp(const GemmArgs3& g_in, bool wgrad, hipStream_t s, const char* what) {
-    GemmArgs3 g = g_in;
-    g.scalar_stores = x3_scalar_stores();
+int launch_gemm_x3_imp(const GemmArgs3& g, bool wgrad, hipStream_t s, const char* what) {
     if (g.M <= 0 || g.N <= 0) return FQSS_OK;
     const int64_t zdim = (int64_t)(g.batch > 0 ? g.batch : 1) * (wgrad ? g.ksplit : 1);
     if (zdim > 65535) { set_error("%s: too many batches x k-slices", what); return FQSS_EINVAL; }
@@ -636,7 +625,6 @@ int launch_gemm_x3_imp(const GemmArgs3& g_in, bool wgrad, hipStream_t s, const c
 // coded-B forms (BQ = 1 wgrad, 2 dgrad); the caller has checked shapes and alignment
 int launch_gemm_x3q(const GemmArgs3& g_in, int bq, hipStream_t s, const char* what) {
     GemmArgs3 g = g_in;
-    g.scalar_stores = x3_scalar_stores();
     if (g.M <= 0 || g.N <= 0) return FQSS_OK;
     const bool atomic = bq == 1;
     if (g.batch < 1) g.batch = 1;

@@ -24,7 +24,6 @@
 // wgrad (k_qwgrad2): LDS-tiled 64 x 128 x 64 stages, a ring of four hand-scheduled register stages, float atomics.
 //
 // Reference replaced: F.conv1d(k=1) of Conv1dQ / Conv1dNlQ (qat_layers.py:137-146, 202-212) and its autograd.
-#include <cstdlib>
 #include <type_traits>
 
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
@@ -48,11 +47,6 @@ constexpr int WGRAD_BLOCKS = 256;   // one workgroup per CU: the fp32 atomics of
 
 __device__ __forceinline__ unsigned short f2bf_trunc(float f) { return (unsigned short)(__float_as_uint(f) >> 16); }
 __device__ __forceinline__ float bf_trunc(float f) { return __uint_as_float(__float_as_uint(f) & 0xFFFF0000u); }
-// the fp32 word whose HIGH half is f rounded to nearest-even bf16 (finite f): the second piece of the two-piece gradient split
-__device__ __forceinline__ unsigned int bf_rne_word(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return u + 0x7FFFu + ((u >> 16) & 1u);
-}
 
 // exact 3-way split g = b1 + b2 + b3 (each bf16-representable)
 __device__ __forceinline__ void split3(float g, unsigned short& b1, unsigned short& b2, unsigned short& b3) {
@@ -142,12 +136,9 @@ struct QGemmArgs {
 
 // MODE 0 fwd (int8 A codes, u8 B codes)            1 dgrad (int8 A codes, fp32 B split3)
 //      3 plain fp32 x fp32 (A split3 x B split3 = 9 exact products; GP = 2: the six above 2^-24)   (wgrad: k_qwgrad2 below)
-// GP (dgrad only): bf16 pieces of the fp32 gradient operand.  3 = exact products (a = h1 + h2 + h3, truncations): the default.  2 = an
-// OPT-IN fast form (FQSS_GRAD_PIECES=2): a ~ h1 + RNE_bf16(a - h1), 16-17 significant bits, |error| <= 2^-16 |a|, unbiased; one third
-// fewer MFMAs and LDS bytes: -1.7 / -5.5 us (dgrad), -4 / -6 us (wgrad) = -0.4 ms per cfg-2 step.  Measured against fp64
-// (tests/test_gpu_kernels.py::test_gradient_gemms_two_piece_split): the exact form sits at 1.6e-7 .. 3.3e-7 of the result's norm, the
-// two-piece form at 4.9e-6 (dgrad) / 8.1e-6 (wgrad) -- 25x the exact form's error, which is why it is not the default and why
-// bench.py never sets it.
+// The fp32 gradient operand of MODE 1 always goes in three exact bf16 pieces (a = h1 + h2 + h3, truncations): against fp64 the result
+// sits at 1.6e-7 .. 4.4e-7 of its norm (tests/test_gpu_kernels.py::test_gradient_gemms_exact_split).
+// GP is 3 except for MODE 3's six-product form; it stays a parameter because profiles and the benchmark key on the kernels' printed names.
 template <int MODE, int GP = 3, bool IMP = false>
 __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
     static_assert(!IMP || MODE == 1 || MODE == 3 || MODE == 4, "implicit convolution: float B operands");
@@ -155,12 +146,12 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
     // convolutions of HTDemucs): A = int8 weight codes, B = fp32 x in three exact bf16 pieces -- the loop of MODE 1 without its
     // delta_w scaling of the reduction rows -- and z = dw[co] * S + b[co] in the epilogue: three products per k instead of six
     static_assert(MODE == 0 || MODE == 1 || MODE == 3 || MODE == 4, "unknown q-GEMM mode");
-    static_assert(GP == 3 || (GP == 2 && MODE != 0 && MODE != 4), "two gradient pieces: dgrad only");
+    static_assert(GP == 3 || MODE == 3, "GP = 2: the six-product form of MODE 3 only");
     constexpr bool ACODES = MODE < 2 || MODE == 4;          // A arrives as int8 codes
     constexpr int WMODE = MODE == 4 ? 1 : MODE;             // register image / wait form of the load stages
     constexpr bool SIX = MODE == 3 && GP == 2;              // fp32 x fp32 with the six products above 2^-24 instead of all nine
     constexpr int NA = (MODE == 3) ? 3 : 1;                 // A images
-    constexpr int NB = (MODE == 1) ? GP : (MODE == 3 || MODE == 4) ? 3 : 1;    // B images
+    constexpr int NB = (MODE == 0) ? 1 : 3;                 // B images
     constexpr int BROWS = QBK, BLD = LDN;
     constexpr int A_BYTES = NA * QBM * LDK * 2, B_BYTES = NB * BROWS * BLD * 2;
     constexpr int T_BYTES = 4 * 32 * LDT * 4;   // epilogue staging: one 32x32 fp32 tile per wave
@@ -309,30 +300,6 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
         }
     };
 
-    // two-piece form of store_split3 for the gradient operand: truncated head + round-to-nearest remainder
-    auto store_split2 = [&](unsigned short* d1, unsigned short* d2, const f32x4* v, float scale, bool zero) {
-        unsigned int o1[4], o2[4];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            float h0[4];
-            unsigned int r1[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = scale * v[q][e];
-                if (zero) t = 0.0f;
-                h0[e] = t;
-                r1[e] = bf_rne_word(t - bf_trunc(t));
-            }
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                o1[2 * q + e] = __builtin_amdgcn_perm(__float_as_uint(h0[2 * e + 1]), __float_as_uint(h0[2 * e]), 0x07060302u);
-                o2[2 * q + e] = __builtin_amdgcn_perm(r1[2 * e + 1], r1[2 * e], 0x07060302u);
-            }
-        }
-        *reinterpret_cast<uint4*>(d1) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
-        *reinterpret_cast<uint4*>(d2) = make_uint4(o2[0], o2[1], o2[2], o2[3]);
-    };
-
     auto store_tiles = [&](QStage& st, int k0) {
         q_wait<WMODE, NLOADS>(st);   // this stage has landed; the NLOADS younger requests of the other stage stay in flight
         const bool kz = (k0 + bk_row) >= g.K;   // reduction rows past K contribute zeros (B side)
@@ -349,11 +316,8 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
             store_codes(&Bs[0][bk_row][bk_n], w, std::integral_constant<int, 2>{}, false, kz);
         } else {
             const float sc = (MODE == 1) ? dws[IMP ? st.kch : min(k0 + bk_row, g.K - 1)] : 1.0f;
-            if constexpr (NB == 2)
-                store_split2(&Bs[0][bk_row][bk_n], &Bs[1][bk_row][bk_n], st.b, sc, kz);
-            else
-                store_split3(&Bs[0][bk_row][bk_n], &Bs[1][bk_row][bk_n], &Bs[2][bk_row][bk_n], st.b, sc, MODE == 1, kz,
-                             std::integral_constant<int, 2>{});
+            store_split3(&Bs[0][bk_row][bk_n], &Bs[1][bk_row][bk_n], &Bs[2][bk_row][bk_n], st.b, sc, MODE == 1, kz,
+                         std::integral_constant<int, 2>{});
         }
     };
 
@@ -627,8 +591,9 @@ __device__ __forceinline__ void w2_wait(W2Stage& st) {
 
 // 512 threads = 8 waves as 2 (co) x 4 (ci), each a 32 x 32 output tile: two waves per SIMD, so one wave's conversion (VALU) runs
 // beside the other's MFMAs (a 4-wave form, one wave per SIMD, serialised the two phases: 34 us instead of the 39 us it replaced)
-template <int GP>   // bf16 pieces of gz: 3 exact (default), 2 = head + round-to-nearest remainder (opt-in, see k_qgemm)
+template <int GP>   // bf16 pieces of gz: always the 3 exact ones; still a parameter because profiles and the benchmark key on the printed name
 __global__ __launch_bounds__(512, 1) void k_qwgrad2(QGemmArgs g) {
+    static_assert(GP == 3, "gz goes in three exact bf16 pieces");
     // two LDS stage buffers: a wave converts stage s+1 into one while it (and its SIMD partner) multiply stage s out of the other,
     // ONE barrier per stage.  (Single-buffered, two barriers per stage put all eight waves into the same phase at the same time:
     // VALU and matrix pipe took turns -- PMC: 49 % of the wave time waiting -- and the kernel ran at 30 / 45 us.)
@@ -683,18 +648,14 @@ __global__ __launch_bounds__(512, 1) void k_qwgrad2(QGemmArgs g) {
                 const float a0 = x[2 * e], a1 = x[2 * e + 1];
                 const float r0 = a0 - bf_trunc(a0), r1 = a1 - bf_trunc(a1);
                 o1[e] = __builtin_amdgcn_perm(__float_as_uint(a1), __float_as_uint(a0), 0x07060302u);
-                if constexpr (GP == 3) {
-                    const float s0 = r0 - bf_trunc(r0), s1 = r1 - bf_trunc(r1);
-                    o2[e] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
-                    o3[e] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-                } else {
-                    o2[e] = __builtin_amdgcn_perm(bf_rne_word(r1), bf_rne_word(r0), 0x07060302u);
-                }
+                const float s0 = r0 - bf_trunc(r0), s1 = r1 - bf_trunc(r1);
+                o2[e] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
+                o3[e] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
             }
             const int row = ar + 32 * i;
             *reinterpret_cast<uint2*>(&As[buf][0][row][ac]) = make_uint2(o1[0], o1[1]);
             *reinterpret_cast<uint2*>(&As[buf][1][row][ac]) = make_uint2(o2[0], o2[1]);
-            if constexpr (GP == 3) *reinterpret_cast<uint2*>(&As[buf][2][row][ac]) = make_uint2(o3[0], o3[1]);
+            *reinterpret_cast<uint2*>(&As[buf][2][row][ac]) = make_uint2(o3[0], o3[1]);
         }
         {   // codes need no mask: finite, and beyond kend they only ever meet a zero
             uint32_t o[8];
@@ -829,6 +790,7 @@ __device__ __forceinline__ void ld16_sc1(f32x4& d, const float* p) { asm volatil
 template <int GP, bool WIDE>
 __device__ __forceinline__ void wgr_segment(const WGroupArgs& ga, const WJob& J, const int tile, const int s0, const int n, const int nparts,
                                             const int part, unsigned short* As_raw, unsigned short* Bs_raw, float* rsum, unsigned* ticket_s) {
+    static_assert(GP == 3, "gz goes in three exact bf16 pieces");
     constexpr int TN = WIDE ? 256 : 128, NBF = WIDE ? 2 : 1;      // tile width, B fragments (and code loads) per wave (thread)
     typedef unsigned short (*AsT)[GP][W2_TM][W2_LD];
     typedef unsigned short (*BsT)[TN][W2_LD];
@@ -903,18 +865,14 @@ __device__ __forceinline__ void wgr_segment(const WGroupArgs& ga, const WJob& J,
                 const float a0 = x[2 * e], a1 = x[2 * e + 1];
                 const float r0 = a0 - bf_trunc(a0), r1 = a1 - bf_trunc(a1);
                 o1[e] = __builtin_amdgcn_perm(__float_as_uint(a1), __float_as_uint(a0), 0x07060302u);
-                if constexpr (GP == 3) {
-                    const float q0 = r0 - bf_trunc(r0), q1 = r1 - bf_trunc(r1);
-                    o2[e] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
-                    o3[e] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-                } else {
-                    o2[e] = __builtin_amdgcn_perm(bf_rne_word(r1), bf_rne_word(r0), 0x07060302u);
-                }
+                const float q0 = r0 - bf_trunc(r0), q1 = r1 - bf_trunc(r1);
+                o2[e] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
+                o3[e] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
             }
             const int row = ar + 32 * i;
             *reinterpret_cast<uint2*>(&As[buf][0][row][ac]) = make_uint2(o1[0], o1[1]);
             *reinterpret_cast<uint2*>(&As[buf][1][row][ac]) = make_uint2(o2[0], o2[1]);
-            if constexpr (GP == 3) *reinterpret_cast<uint2*>(&As[buf][2][row][ac]) = make_uint2(o3[0], o3[1]);
+            *reinterpret_cast<uint2*>(&As[buf][2][row][ac]) = make_uint2(o3[0], o3[1]);
         }
 #pragma unroll
         for (int f = 0; f < NBF; ++f) {   // codes need no mask: finite, and where gz is masked they only ever meet a zero
@@ -1050,8 +1008,9 @@ __device__ __forceinline__ void wgr_segment(const WGroupArgs& ga, const WJob& J,
     __syncthreads();     // rsum / ticket_s / the LDS stages are reused by the next segment
 }
 
-template <int GP>
+template <int GP>   // (see k_qwgrad2)
 __global__ __launch_bounds__(512, 1) void k_qwgrad_group(WGroupArgs ga) {
+    static_assert(GP == 3, "gz goes in three exact bf16 pieces");
     // two stage buffers of the WIDE tile (the narrow one uses the front of each): gz pieces 2 x GP x 9,216 B, codes 2 x 36,864 B
     __shared__ __attribute__((aligned(16))) unsigned short As_raw[2 * GP * W2_TM * W2_LD];
     __shared__ __attribute__((aligned(16))) unsigned short Bs_raw[2 * 256 * W2_LD];
@@ -1105,13 +1064,6 @@ __global__ __launch_bounds__(256) void k_wq_codes(const float* __restrict__ w, s
 }  // namespace fqss
 
 using namespace fqss;
-
-// bf16 pieces of the fp32 gradient operand in the dgrad / wgrad q-GEMMs: 3 = exact products (default: what every parity gate and the
-// benchmark run on) or, opt-in with FQSS_GRAD_PIECES=2, the two-piece form (read on every call: the test flips it inside one process)
-static int grad_pieces() {
-    const char* e = getenv("FQSS_GRAD_PIECES");
-    return (e != nullptr && e[0] == '2') ? 2 : 3;
-}
 
 extern "C" int fqss_wq_codes_bits(const float* w, int8_t* idx, int8_t* idxT, float* dw, float* rw, int Co, int Ci,
                                   const float* qmin, const float* qmax, int n_bits, fqss_stream_t stream) {
@@ -1245,10 +1197,7 @@ static int qpw_bwd_x_impl(const char* who, const float* gz1, const float* gz2, c
         g.C2 = const_cast<float*>(addend); g.ldc2 = ld_add; g.sC2b = (int64_t)Ci * ld_add;
     }
     g.tiles_n = (int)cdiv(M, QBN); g.tiles_m = (int)cdiv(Ci, QBM); g.batches = B;
-    if (grad_pieces() == 3)
-        hipLaunchKernelGGL((k_qgemm<1, 3>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
-    else
-        hipLaunchKernelGGL((k_qgemm<1, 2>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
+    hipLaunchKernelGGL((k_qgemm<1, 3>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
     return launch_status(who);
 }
 
@@ -1296,10 +1245,7 @@ static int qpw_bwd_w_impl(const char* who, const float* gz1, const float* gz2, c
     const int kchunk = (int)cdiv(cdiv(M, want), W2_RING * W2_TK) * W2_RING * W2_TK;   // whole rounds of the stage ring
     g.kchunk = kchunk;
     g.ksplit = (int)cdiv(M, kchunk);
-    if (grad_pieces() == 3)
-        hipLaunchKernelGGL(k_qwgrad2<3>, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(512), 0, (hipStream_t)stream, g);
-    else
-        hipLaunchKernelGGL(k_qwgrad2<2>, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(512), 0, (hipStream_t)stream, g);
+    hipLaunchKernelGGL(k_qwgrad2<3>, dim3(xcd_grid((int64_t)B * g.ksplit, (int64_t)g.tiles_m * g.tiles_n)), dim3(512), 0, (hipStream_t)stream, g);
     return launch_status(who);
 }
 
@@ -1328,8 +1274,7 @@ static int wgr_plan(const FqssWgradJob* jobs, int n0, int n, WGroupArgs& ga, int
         J.lda = f.ld_gz1; J.lda2 = f.ld_gz2; J.ldb = f.ld_xc;
         J.sAb = (int64_t)f.Co1 * f.ld_gz1; J.sA2b = (int64_t)f.Co2 * f.ld_gz2; J.sBb = (int64_t)f.Ci * f.ld_xc;
         J.M = Co; J.M1 = f.Co1; J.N = f.Ci; J.K = f.M;
-        static const bool no_wide = getenv("FQSS_WGRAD_WIDE") != nullptr && getenv("FQSS_WGRAD_WIDE")[0] == '0';      // A/B knob
-        J.wide = (f.Ci >= 256 && !no_wide) ? 1 : 0;
+        J.wide = f.Ci >= 256;
         J.tiles_n = (int)cdiv(f.Ci, J.wide ? 256 : W2_TN);
         J.ntiles = (int)cdiv(Co, W2_TM) * J.tiles_n;
         J.spb = (int)cdiv(f.M, W2_TK);
@@ -1386,10 +1331,7 @@ extern "C" int fqss_qpw_bwd_w_group(const FqssWgradJob* jobs, int njobs, void* w
         FQSS_REQUIRE((int64_t)t * 4 <= WGR_TICKET_BYTES && WGR_TICKET_BYTES + sb <= ws_bytes, "workspace too small (fqss_qpw_bwd_w_group_ws)");
         ga.tickets = (unsigned*)ws;
         ga.slabs = (float*)((char*)ws + WGR_TICKET_BYTES);
-        if (grad_pieces() == 3)
-            hipLaunchKernelGGL(k_qwgrad_group<3>, dim3(WGR_TEAMS * WGR_TEAM), dim3(512), 0, (hipStream_t)stream, ga);
-        else
-            hipLaunchKernelGGL(k_qwgrad_group<2>, dim3(WGR_TEAMS * WGR_TEAM), dim3(512), 0, (hipStream_t)stream, ga);
+        hipLaunchKernelGGL(k_qwgrad_group<3>, dim3(WGR_TEAMS * WGR_TEAM), dim3(512), 0, (hipStream_t)stream, ga);
         if (int rc = launch_status("fqss_qpw_bwd_w_group")) return rc;
     }
     return FQSS_OK;

@@ -10,8 +10,6 @@
 // adjoint: crop / envelope / window, one forward FFT per frame, (2 - [k = 0]) / sqrt(N) scaling.
 // Spectra are exchanged as separate real / imaginary planes [rows][2][T][N/2] (bins contiguous: coalesced); fqss_transpose2d turns
 // them into the model's [.., 2, Fr, T] "complex as channels" layout and back.
-#include <stdlib.h>
-
 #include "fqss_dev.h"
 
 namespace fqss {
@@ -19,13 +17,7 @@ namespace fqss {
 // in-place DIT FFT of N = 2^logn points in LDS (radix-2 butterflies, fused three stages at a time); data must have been stored in
 // bit-reversed order.
 // tw[k] = exp(-2 pi i k / N), k < N/2; inverse: conjugated twiddles (no 1/N).
-// tws (nullable): the twiddle table staged in LDS behind the data (N/2 entries) -- every butterfly then reads its twiddle from LDS
-// instead of a (cached, but ~a microsecond per dependent round trip) global load
-__device__ __forceinline__ void fft_lds(float2* s, const float2* __restrict__ tw, int N, int logn, bool inverse, float2* tws = nullptr) {
-    if (tws != nullptr) {
-        for (int k = threadIdx.x; k < N / 2; k += blockDim.x) tws[k] = tw[k];
-        tw = tws;           // (generic address space: LDS reads from here on; the first stage's barrier orders the stores)
-    }
+__device__ __forceinline__ void fft_lds(float2* s, const float2* __restrict__ tw, int N, int logn, bool inverse) {
     // one radix-2 butterfly, written once: the fused passes below apply it in the SAME order as the stage-by-stage form (the results
     // are bit-identical to it); w = tw[pos * tstep] of the butterfly's stage
     auto bfly = [&](float2& a, float2& c, float2 w) {
@@ -103,7 +95,7 @@ __device__ __forceinline__ int bitrev(int v, int logn) { return (int)(__brev((un
 
 // z[row][0/1][f][k] = (1/sqrt(N)) * FFT_k( w[n] * x2[f*hop + n] ),  k < N/2,  x2 = reflect-pad(x, pad) (`_spec`)
 __global__ __launch_bounds__(1024) void k_stft(const float* __restrict__ x, float* __restrict__ z, const float* __restrict__ win,
-                                               const float2* __restrict__ tw, int N, int logn, int hop, int T, int pad, int64_t L, int64_t ld_x, int twl) {
+                                               const float2* __restrict__ tw, int N, int logn, int hop, int T, int pad, int64_t L, int64_t ld_x) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     const int f = blockIdx.x;
     const int64_t row = blockIdx.y;
@@ -113,7 +105,7 @@ __global__ __launch_bounds__(1024) void k_stft(const float* __restrict__ x, floa
         if (i >= L) i = 2 * (L - 1) - i;
         sm[bitrev(n, logn)] = make_float2(win[n] * x[row * ld_x + i], 0.f);
     }
-    fft_lds(sm, tw, N, logn, false, twl ? sm + N : nullptr);
+    fft_lds(sm, tw, N, logn, false);
     const float sc = 1.0f / sqrtf((float)N);
     float* zr = z + ((row * 2 + 0) * T + f) * (int64_t)(N / 2);
     float* zi = z + ((row * 2 + 1) * T + f) * (int64_t)(N / 2);
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(1024) void k_stft(const float* __restrict__ x, floa
 
 // fr[row][t][n] = w[n] * sqrt(N) * irfft(Z_t)[n],  Z_t = bins 0 .. N/2-1 of z[row][0/1][t][:], Nyquist bin = 0
 __global__ __launch_bounds__(1024) void k_istft_frames(const float* __restrict__ z, float* __restrict__ fr, const float* __restrict__ win,
-                                                       const float2* __restrict__ tw, int N, int logn, int T, int twl) {
+                                                       const float2* __restrict__ tw, int N, int logn, int T) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     const int t = blockIdx.x;
     const int64_t row = blockIdx.y;
@@ -137,7 +129,7 @@ __global__ __launch_bounds__(1024) void k_istft_frames(const float* __restrict__
         if (k > 0) sm[bitrev(N - k, logn)] = make_float2(re, -im);
         else sm[bitrev(N / 2, logn)] = make_float2(0.f, 0.f);
     }
-    fft_lds(sm, tw, N, logn, true, twl ? sm + N : nullptr);
+    fft_lds(sm, tw, N, logn, true);
     const float sc = sqrtf((float)N) / (float)N;
     float* o = fr + (row * T + t) * (int64_t)N;
     for (int n = threadIdx.x; n < N; n += blockDim.x) o[n] = win[n] * (sm[n].x * sc);
@@ -164,7 +156,7 @@ __global__ __launch_bounds__(256) void k_istft_ola(const float* __restrict__ fr,
 // c_0 = 1/sqrt(N) (imaginary part 0), c_k = 2/sqrt(N)
 __global__ __launch_bounds__(1024) void k_istft_bwd(const float* __restrict__ g, float* __restrict__ gz, const float* __restrict__ win,
                                                     const float* __restrict__ env, const float2* __restrict__ tw, int N, int logn, int hop, int T,
-                                                    int pad, int64_t length, int64_t ld_g, int twl) {
+                                                    int pad, int64_t length, int64_t ld_g) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     const int t = blockIdx.x;
     const int64_t row = blockIdx.y;
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(1024) void k_istft_bwd(const float* __restrict__ g,
         if (j >= 0 && j < length) v = win[m] * (g[row * ld_g + j] / env[n % hop]);
         sm[bitrev(m, logn)] = make_float2(v, 0.f);
     }
-    fft_lds(sm, tw, N, logn, false, twl ? sm + N : nullptr);
+    fft_lds(sm, tw, N, logn, false);
     const float sc = 1.0f / sqrtf((float)N);
     float* zr = gz + ((row * 2 + 0) * T + t) * (int64_t)(N / 2);
     float* zi = gz + ((row * 2 + 1) * T + t) * (int64_t)(N / 2);
@@ -212,12 +204,7 @@ static int check_fft(int N, int hop, int* logn) {
 using namespace fqss;
 
 constexpr int kFftThreads = 512;     // threads per frame
-// whether the twiddles are staged in LDS (A/B knob FQSS_FFT_TW_LDS, see fft_lds)
-static int fft_tw_lds() {
-    static const int v = [] { const char* e = getenv("FQSS_FFT_TW_LDS"); return e ? atoi(e) : 0; }();
-    return v;
-}
-static size_t fft_lds_bytes(int N) { return (size_t)N * sizeof(float2) + (fft_tw_lds() ? (size_t)(N / 2) * sizeof(float2) : 0); }
+static size_t fft_lds_bytes(int N) { return (size_t)N * sizeof(float2); }
 
 // x [rows][L] (row stride ld_x) -> z [rows][2][T][N/2];  T frames, reflect padding `pad` on the left (must be < L, as must the right one)
 extern "C" int fqss_stft(const float* x, float* z, const float* win, const float* tw, int64_t rows, int64_t L, int64_t ld_x, int N, int hop,
@@ -229,7 +216,7 @@ extern "C" int fqss_stft(const float* x, float* z, const float* win, const float
     const int64_t last = (int64_t)(T - 1) * hop + N - 1 - pad;       // right-most sample index touched
     FQSS_REQUIRE(pad >= 0 && pad < L && last - (L - 1) < L, "reflect padding longer than the signal");
     hipLaunchKernelGGL(k_stft, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, x, z, win,
-                       reinterpret_cast<const float2*>(tw), N, logn, hop, T, pad, L, ld_x, fft_tw_lds());
+                       reinterpret_cast<const float2*>(tw), N, logn, hop, T, pad, L, ld_x);
     return launch_status("fqss_stft");
 }
 
@@ -241,7 +228,7 @@ extern "C" int fqss_istft(const float* z, float* frames, float* y, const float* 
     if (int rc = check_fft(N, hop, &logn)) return rc;
     FQSS_REQUIRE(rows > 0 && rows <= 65535 && T > 0 && length > 0 && ld_y >= length && pad >= 0, "bad shape");
     hipLaunchKernelGGL(k_istft_frames, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, z, frames, win,
-                       reinterpret_cast<const float2*>(tw), N, logn, T, fft_tw_lds());
+                       reinterpret_cast<const float2*>(tw), N, logn, T);
     int64_t gx = cdiv(length, 1024);
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(k_istft_ola, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, frames, y, env, N, hop, T, pad, length, ld_y);
@@ -256,7 +243,7 @@ extern "C" int fqss_istft_bwd(const float* g, float* gz, const float* win, const
     if (int rc = check_fft(N, hop, &logn)) return rc;
     FQSS_REQUIRE(rows > 0 && rows <= 65535 && T > 0 && length > 0 && ld_g >= length && pad >= 0, "bad shape");
     hipLaunchKernelGGL(k_istft_bwd, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, g, gz, win, env,
-                       reinterpret_cast<const float2*>(tw), N, logn, hop, T, pad, length, ld_g, fft_tw_lds());
+                       reinterpret_cast<const float2*>(tw), N, logn, hop, T, pad, length, ld_g);
     return launch_status("fqss_istft_bwd");
 }
 

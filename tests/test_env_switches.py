@@ -1,5 +1,6 @@
 """The environment does not pick kernels: the only FQSS_* variables the package reads are process-level settings (they cross into child
-processes or belong to the test harness) and the library's own six; every other flag is a module constant that tests patch."""
+processes or belong to the test harness); the library reads one, the selector of a test's reference kernel; every other flag is a
+module constant that tests patch."""
 import glob
 import os
 import re
@@ -9,7 +10,7 @@ PKG = os.path.join(ROOT, "fqss_amd")
 
 PYTHON_ENV = {"FQSS_LIB", "FQSS_DEBUG_CARRIER", "FQSS_DETERMINISTIC", "FQSS_DIST_BACKEND", "FQSS_FORCE_DIST", "FQSS_FORCE_BUCKETS",
               "FQSS_DIST_TIMEOUT_S", "FQSS_NPROC", "FQSS_GROUP_WGRAD"}
-C_ENV = {"FQSS_X3_STAGED", "FQSS_TAPS_LDS", "FQSS_FFT_TW_LDS", "FQSS_GNQ_APPLY_V1", "FQSS_GRAD_PIECES", "FQSS_WGRAD_WIDE"}
+C_ENV = {"FQSS_GNQ_APPLY_V1"}
 
 
 def _files(*patterns):

@@ -388,11 +388,9 @@ def test_kd_loss_per_sample_speechbrain_objective():
         K.kd_loss(e_all.cuda(), f_all.cuda(), s.cuda(), 0.1, per_sample=True)
 
 
-def test_gradient_gemms_two_piece_split(monkeypatch):
-    """The dgrad / wgrad q-GEMMs form EXACT products by default (the fp32 gradient operand in three bf16 pieces): 1.6e-7 .. 3.3e-7 of the
-    result's norm against fp64 at the cfg-2 layer shapes.  FQSS_GRAD_PIECES=2 opts into a two-piece operand (truncated head +
-    round-to-nearest remainder, 16-17 significant bits, -0.4 ms per cfg-2 step): 5e-6 .. 8e-6 -- bounded here so the option stays honest;
-    nothing else in the suite, and never the benchmark, runs on it."""
+def test_gradient_gemms_exact_split():
+    """The dgrad / wgrad q-GEMMs form EXACT products (the fp32 gradient operand in three bf16 pieces): 1.6e-7 .. 4.4e-7 of the
+    result's norm against fp64 at the cfg-2 layer shapes."""
     torch.manual_seed(0)
     B, M = 2, 3999
     for Ci, Co in ((128, 512), (512, 256)):
@@ -402,26 +400,18 @@ def test_gradient_gemms_two_piece_split(monkeypatch):
         gz.copy_(torch.randn(B, Co, M, device="cuda") * torch.exp(torch.randn(B, Co, M, device="cuda")) * 1e-4)      # heavy-tailed, like real gradients
         xc = K.empty_codes((B, Ci, M), "cuda").random_(0, 256)
         lo, hi = torch.tensor([-1.0], device="cuda"), torch.tensor([2.0], device="cuda")
-        out = {}
-        for pieces in ("3", "2"):
-            monkeypatch.setenv("FQSS_GRAD_PIECES", pieces)         # (the default, unset, is 3)
-            gw = torch.zeros(Co, Ci, device="cuda")
-            K.qpw_bwd_w(gz, xc, lo, hi, gw)
-            out[pieces] = (K.qpw_bwd_x(gz, wc)[..., :M].clone(), gw)
-        monkeypatch.delenv("FQSS_GRAD_PIECES")
+        gw = torch.zeros(Co, Ci, device="cuda")
+        K.qpw_bwd_w(gz, xc, lo, hi, gw)
+        out = (K.qpw_bwd_x(gz, wc)[..., :M].clone(), gw)
         # fp64 references
         w64 = (wc.idx.double() * wc.dw.double()[:, None])                              # [Co, Ci]
         gx64 = torch.einsum("oc,bom->bcm", w64, gz[..., :M].double())
         x64 = xc[..., :M].double() * ((hi - lo).double() / 255.0) + lo.double()
         gw64 = torch.einsum("bom,bcm->oc", gz[..., :M].double(), x64)
         for k, ref in ((0, gx64), (1, gw64)):
-            a3, a2 = out["3"][k].double(), out["2"][k].double()
-            nrm, rms = float(ref.norm()), float(ref.pow(2).mean().sqrt())
-            e3, e2 = float((a3 - ref).norm()) / nrm, float((a2 - ref).norm()) / nrm
-            print(f"Ci {Ci} Co {Co} {'dgrad' if k == 0 else 'wgrad'}: |2p-3p|/|ref| {float((a2 - a3).norm()) / nrm:.2e}  max/rms "
-                  f"{float((a2 - a3).abs().max()) / rms:.2e}  vs fp64: 3 pieces {e3:.2e}, 2 pieces {e2:.2e}")
-            assert e3 <= 1e-6 and e2 <= 1.5e-5, (Ci, Co, k, e3, e2)
-            assert float((a2 - a3).abs().max()) <= 5e-4 * rms, (Ci, Co, k, float((a2 - a3).abs().max()) / rms)
+            e3 = float((out[k].double() - ref).norm()) / float(ref.norm())
+            print(f"Ci {Ci} Co {Co} {'dgrad' if k == 0 else 'wgrad'} vs fp64: {e3:.2e}")
+            assert e3 <= 1e-6, (Ci, Co, k, e3)
 
 
 @pytest.mark.parametrize("case", ["block", "segment", "ragged", "many"])
@@ -499,8 +489,7 @@ def test_grouped_weight_gradients_beside_a_memory_hog():
     landed in the slab in place of data whenever the memory pipe was slow to fetch the store data (profiles/r05_store_hazard.txt).
     Here the grouped launch of a three-block backward segment (cfg-2 shapes) runs 30 times while
     two other streams keep HBM saturated with 1 GB copies; the kernel uses no atomics, so every run must reproduce the bits of a run
-    on an idle GPU -- not a tolerance.  tools/r06_store_hazard.sh runs this very test against a library built WITHOUT the wait states (wide and narrow tiles: FQSS_WGRAD_WIDE
-    is read once per process)."""
+    on an idle GPU -- not a tolerance.  tools/r06_store_hazard.sh runs this very test against a library built WITHOUT the wait states."""
     dev = "cuda"
     g = torch.Generator().manual_seed(2)
     shapes = [(8, 128, 512, 0, 3999), (8, 512, 128, 128, 3999)] * 3

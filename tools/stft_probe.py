@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The spectrogram pair of HTDemucs at the cfg 5 shapes (32 rows x 441000 samples, n_fft 4096, hop 1024) in isolation:
-python tools/stft_probe.py   (knob: FQSS_FFT_TW_LDS=0|1)"""
+python tools/stft_probe.py"""
 import os
 import sys
 
