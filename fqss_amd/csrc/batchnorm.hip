@@ -51,9 +51,9 @@ __global__ __launch_bounds__(256) void k_bn_affine(const float* __restrict__ p, 
     const float* qr = q ? q + (int64_t)row * ld_q : nullptr;
     float* yr = y + (int64_t)row * ld_y;
     for (int m = blockIdx.x * 256 + threadIdx.x; m < M; m += gridDim.x * 256) {
-        float t = pr[m] * ca;
-        if (qr) t = t + qr[m] * cb;
-        yr[m] = t + cd;
+        // one rounding per term (as k_gn_apply / k_gn_bwd_apply): with |mean| >> std the product p * a is ~|mean| / std times the result
+        const float t = qr ? fmaf(qr[m], cb, cd) : cd;
+        yr[m] = fmaf(pr[m], ca, t);
     }
 }
 

@@ -1175,8 +1175,9 @@ class BatchNormFn(Function):
         invstd = 1.0 / torch.sqrt(var + bn.eps)
         w = weight.double() if weight is not None else torch.ones(C, device=dev, dtype=torch.float64)
         b = bias.double() if bias is not None else torch.zeros(C, device=dev, dtype=torch.float64)
-        a = invstd * w
-        y = K.bn_apply(x, a.float(), (b - mean * a).float())
+        a = (invstd * w).float()
+        # the shift from the ROUNDED scale (k_gn_apply's form): x * a + shift then cancels mean * a whatever the rounding of a was
+        y = K.bn_apply(x, a, (b - mean * a.double()).float())
         ctx.save_for_backward(x, mean, invstd, w)
         ctx.batch_stats, ctx.n, ctx.has_w, ctx.has_b = bool(training or bn.running_mean is None), n, weight is not None, bias is not None
         return y
