@@ -85,6 +85,73 @@ __global__ __launch_bounds__(256) void k_resample_fir(const float* __restrict__ 
     }
 }
 
+// Stems of the htdemucs env (train_env/htdemucs_musdbhq/wav_dataset.py; reference: demucs' wav reader + the augmentation chain of
+// solver.py:60-69, 314-318 -- Shift, FlipChannels, FlipSign, Scale, Remix -- folded by the host into one table row per output (b, s)):
+//   b' = src_b[b,s];  c' = (C == 2 && flip[b,s]) ? 1 - c : c
+//   v = float(pcm[b'][s][t + off[b,s]][c']) * 2^-15;   normalise: v = (v - mean[b']) / std[b'];   sources[b][s][c][t] = v * gain[b,s]
+//   mix[b][c][t] = ((sources[b][0][c][t] + sources[b][1][c][t]) + ...)   left to right on the rounded values
+// One rounding per written operation.  A pure stream: a lane takes V consecutive frames (both channels of a frame: the interleaved
+// input is read once, for the stem and for the mix), walks the S stems with the mix in registers and writes V consecutive floats per
+// output row -- V = 4 (16-byte stores) when T_out is a multiple of 4, which keeps every output row 16-byte aligned; V = 1 otherwise.
+// `off` leaves the input frame-aligned only (4 bytes for stereo): the V frames are one load of that alignment.  The table rows are
+// indexed by (blockIdx.y, s) alone, so they are scalar loads.  Every index of the table was range-checked by the host wrapper.
+template <int C, int V>
+__global__ __launch_bounds__(256) void k_hd_augment_mix(const int16_t* __restrict__ pcm, const float* __restrict__ mean,
+                                                         const float* __restrict__ stdv, const int* __restrict__ src_b,
+                                                         const int* __restrict__ off, const int* __restrict__ flip,
+                                                         const float* __restrict__ gain, float* __restrict__ sources, float* __restrict__ mix,
+                                                         int S, int64_t T_in, int64_t T_out, int normalise) {
+    typedef float vec_t __attribute__((ext_vector_type(V)));
+    struct __attribute__((packed, aligned(2 * C))) Frames { int16_t x[V * C]; };
+    const int64_t b = blockIdx.y;
+    const int64_t n = T_out / V;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t t = i * V;
+        float acc[C][V];
+        for (int s = 0; s < S; ++s) {
+            const int64_t k = b * S + s;
+            const int64_t bs = src_b[k];
+            const bool fl = C == 2 && flip[k] != 0;
+            const float g = gain[k];
+            float m = 0.0f, sd = 1.0f;
+            if (normalise) { m = mean[bs]; sd = stdv[bs]; }
+            const Frames f = *reinterpret_cast<const Frames*>(pcm + ((bs * S + s) * T_in + t + off[k]) * C);
+            float o[C][V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                int16_t raw[C];
+                raw[0] = f.x[j * C];
+                if (C == 2) {
+                    raw[1] = f.x[j * C + 1];
+                    if (fl) { const int16_t x0 = raw[0]; raw[0] = raw[1]; raw[1] = x0; }
+                }
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    float v = (float)raw[c] * 0x1p-15f;
+                    if (normalise) v = (v - m) / sd;
+                    v = v * g;
+                    o[c][j] = v;
+                    acc[c][j] = s == 0 ? v : acc[c][j] + v;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                vec_t w;
+#pragma unroll
+                for (int j = 0; j < V; ++j) w[j] = o[c][j];
+                *reinterpret_cast<vec_t*>(sources + ((b * S + s) * C + c) * T_out + t) = w;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            vec_t w;
+#pragma unroll
+            for (int j = 0; j < V; ++j) w[j] = acc[c][j];
+            *reinterpret_cast<vec_t*>(mix + (b * C + c) * T_out + t) = w;
+        }
+    }
+}
+
 }  // namespace fqss
 
 using namespace fqss;
@@ -115,4 +182,28 @@ extern "C" int fqss_snr_mix(const float* a, const float* b, const float* snr, do
     hipLaunchKernelGGL(k_snr_mix, grid, dim3(256), 0, s, a, b, snr, ws, out, peak, T, ld_a, ld_b, ld_o, mode);
     if (clip) hipLaunchKernelGGL(k_max_clip, grid, dim3(256), 0, s, out, peak, T, ld_o, 0.9f, 0.9f);
     return launch_status("fqss_snr_mix");
+}
+
+// pcm int16 [B][S][T_in][C] (frames interleaved, as the WAV files hold them); mean / std [B] (ignored unless normalise); src_b / off /
+// flip / gain [B * S]; sources fp32 [B][S][C][T_out], mix fp32 [B][C][T_out].  The table is device memory: its ranges (src_b in [0, B),
+// off in [0, T_in - T_out], flip in {0, 1}, finite gain, std > 0) are the caller's to check before the upload.
+extern "C" int fqss_hd_augment_mix(const int16_t* pcm, const float* mean, const float* stdv, const int* src_b, const int* off, const int* flip,
+                                   const float* gain, float* sources, float* mix, int B, int S, int C, int64_t T_in, int64_t T_out,
+                                   int normalise, fqss_stream_t stream) {
+    FQSS_REQUIRE(pcm && src_b && off && flip && gain && sources && mix && (!normalise || (mean && stdv)), "null pointer");
+    FQSS_REQUIRE(B > 0 && B <= 65535 && S >= 1 && S <= 8 && (C == 1 || C == 2) && T_out > 0 && T_in >= T_out, "bad shape");
+    FQSS_REQUIRE((int64_t)B * S * T_in <= (INT64_MAX >> 3) && (uintptr_t)pcm % (2 * C) == 0 && (uintptr_t)sources % 4 == 0 && (uintptr_t)mix % 4 == 0,
+                 "size or alignment");
+    const bool wide = T_out % 4 == 0 && (uintptr_t)sources % 16 == 0 && (uintptr_t)mix % 16 == 0;
+    int64_t gx = cdiv(wide ? T_out / 4 : T_out, 256);
+    if (gx > 512) gx = 512;
+    const dim3 grid((unsigned)gx, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+#define FQSS_HD_AUG(CC, VV)                                                                                                                  \
+    hipLaunchKernelGGL((k_hd_augment_mix<CC, VV>), grid, dim3(256), 0, st, pcm, mean, stdv, src_b, off, flip, gain, sources, mix, S, T_in, \
+                       T_out, normalise)
+    if (C == 2) { if (wide) FQSS_HD_AUG(2, 4); else FQSS_HD_AUG(2, 1); }
+    else        { if (wide) FQSS_HD_AUG(1, 4); else FQSS_HD_AUG(1, 1); }
+#undef FQSS_HD_AUG
+    return launch_status("fqss_hd_augment_mix");
 }

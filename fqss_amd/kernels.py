@@ -2791,3 +2791,79 @@ def resample(x, orig_freq, new_freq):
     y = torch.empty(rows, Lout, device=x.device, dtype=torch.float32)
     _lib.call("fqss_resample_fir", _p(xs), _p(h), _p(y), rows, L, Lout, L, Lout, orig, new, width, _stream())
     return y.reshape(*x.shape[:-1], Lout)
+
+
+# ------------------------------------------------------------------ data side: stems of the htdemucs env (csrc/data_ops.hip)
+def check_augment_table(B, S, C, T_in, T_out, src_b, off, flip, gain, mean=None, std=None):
+    """Host-side gate of `hd_augment_mix`: the table never reaches the device unless every row is in range.  src_b / off / flip /
+    gain: CPU tensors of B * S elements; mean / std: CPU tensors of B elements or both None (normalise off).  ValueError otherwise."""
+    if not 1 <= S <= 8:
+        raise ValueError(f"hd_augment_mix: S = {S} sources (1 to 8 are built)")
+    if C not in (1, 2) or B < 1 or T_out < 1 or T_in < T_out:
+        raise ValueError(f"hd_augment_mix: bad shape B={B} C={C} T_in={T_in} T_out={T_out}")
+    if B >= 1 << 31 or T_in >= 1 << 31:
+        raise ValueError(f"hd_augment_mix: B={B}, T_in={T_in}: src_b and off travel as int32")
+    for name, t in (("src_b", src_b), ("off", off), ("flip", flip), ("gain", gain), ("mean", mean), ("std", std)):
+        if t is None:
+            if name in ("mean", "std"):
+                continue
+            raise ValueError(f"hd_augment_mix: {name} is missing")
+        if not isinstance(t, torch.Tensor) or t.is_cuda:
+            raise ValueError(f"hd_augment_mix: {name} must be a CPU tensor (its ranges are checked on the host before the upload)")
+        want = B if name in ("mean", "std") else B * S
+        if t.numel() != want:
+            raise ValueError(f"hd_augment_mix: {name} has {t.numel()} elements, {want} expected")
+    for name, t in (("src_b", src_b), ("off", off), ("flip", flip)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"hd_augment_mix: {name} must be an integer tensor, got {t.dtype}")
+    if (mean is None) != (std is None):
+        raise ValueError("hd_augment_mix: mean and std come together")
+    if int(src_b.min()) < 0 or int(src_b.max()) >= B:
+        raise ValueError(f"hd_augment_mix: src_b outside [0, {B})")
+    if int(off.min()) < 0 or int(off.max()) + T_out > T_in:
+        raise ValueError(f"hd_augment_mix: off outside [0, T_in - T_out = {T_in - T_out}]")
+    if int(flip.min()) < 0 or int(flip.max()) > 1:
+        raise ValueError("hd_augment_mix: flip outside {0, 1}")
+    if gain.dtype != torch.float32 or not bool(torch.isfinite(gain).all()):
+        raise ValueError("hd_augment_mix: gain must be finite fp32")
+    if mean is not None:
+        if mean.dtype != torch.float32 or std.dtype != torch.float32 or not bool(torch.isfinite(mean).all()):
+            raise ValueError("hd_augment_mix: mean / std must be finite fp32")
+        if not bool((torch.isfinite(std) & (std > 0)).all()):
+            raise ValueError("hd_augment_mix: std must be finite and > 0")
+
+
+def hd_augment_mix(pcm, T_out, src_b, off, flip, gain, mean=None, std=None, sources=None, mix=None):
+    """pcm int16 [B, S, T_in, C] on the device (frames interleaved as the WAV files hold them) -> (mix [B, C, T_out], sources
+    [B, S, C, T_out]) fp32: decode (x 2^-15), per-track (v - mean) / std when mean / std are given, the row's shift / channel swap /
+    signed gain / source item, and the left-to-right sum of the stems, in one pass (include/fqss.h: fqss_hd_augment_mix).
+    The table (src_b, off, flip, gain [B, S]; mean, std [B]) is taken as CPU tensors: every range is checked here, then one upload."""
+    if pcm.dim() != 4 or pcm.dtype != torch.int16:
+        raise ValueError(f"hd_augment_mix: pcm must be int16 [B, S, T_in, C], got {pcm.dtype} {tuple(pcm.shape)}")
+    B, S, T_in, C = pcm.shape
+    T_out = int(T_out)
+    check_augment_table(B, S, C, T_in, T_out, src_b, off, flip, gain, mean, std)
+    if not pcm.is_cuda or _lib.BACKEND == "cpu":
+        raise _lib.FqssError("hd_augment_mix runs on the HIP backend with pcm in ROCm device memory (no CPU fallback)")
+    pcm = pcm.contiguous()
+    n = B * S
+    tab = torch.empty(4 * n + 2 * B, dtype=torch.int32)
+    tab[:n] = src_b.reshape(-1)
+    tab[n:2 * n] = off.reshape(-1)
+    tab[2 * n:3 * n] = flip.reshape(-1)
+    tab[3 * n:4 * n] = gain.reshape(-1).contiguous().view(torch.int32)
+    if mean is not None:
+        tab[4 * n:4 * n + B] = mean.reshape(-1).contiguous().view(torch.int32)
+        tab[4 * n + B:] = std.reshape(-1).contiguous().view(torch.int32)
+    d = tab.to(pcm.device, non_blocking=True)          # one small upload; freed into the current stream's pool, behind the launch that reads it
+    e = d.element_size()
+    if sources is None:
+        sources = torch.empty(B, S, C, T_out, device=pcm.device, dtype=torch.float32)
+    if mix is None:
+        mix = torch.empty(B, C, T_out, device=pcm.device, dtype=torch.float32)
+    assert sources.shape == (B, S, C, T_out) and mix.shape == (B, C, T_out) and sources.is_contiguous() and mix.is_contiguous()
+    assert sources.dtype == mix.dtype == torch.float32 and sources.device == mix.device == pcm.device
+    base = d.data_ptr()
+    _lib.call("fqss_hd_augment_mix", _p(pcm), base + 4 * n * e if mean is not None else None, base + (4 * n + B) * e if mean is not None else None,
+              base, base + n * e, base + 2 * n * e, base + 3 * n * e, _p(sources), _p(mix), B, S, C, T_in, T_out, 0 if mean is None else 1, _stream())
+    return mix, sources

@@ -24,10 +24,11 @@ import torch
 DEVICE_WORK_LOCK = threading.RLock()
 
 
-def epoch_batches(n_items, batch_size, shuffle, drop_last=True, rank=0, world=1, seed=0, epoch=0):
+def epoch_batches(n_items, batch_size, shuffle, drop_last=True, rank=0, world=1, seed=0, epoch=0, generator=None):
     """list of index lists for one epoch.  world == 1: torch.utils.data.RandomSampler draws its permutation seed from the global torch
     RNG when iteration starts (sampler.py: `int(torch.empty((), dtype=torch.int64).random_().item())`) -- done the same way here, so
-    `torch.manual_seed(s)` fixes the order as it does in the reference; world > 1: DistributedSampler (`seed + epoch`)."""
+    `torch.manual_seed(s)` fixes the order as it does in the reference; with `generator` (RandomSampler's own argument) the seed is
+    drawn from it instead and the global RNG is left alone; world > 1: DistributedSampler (`seed + epoch`)."""
     if world > 1:
         if shuffle:
             g = torch.Generator().manual_seed(int(seed) + int(epoch))
@@ -39,7 +40,7 @@ def epoch_batches(n_items, batch_size, shuffle, drop_last=True, rank=0, world=1,
             idx = (idx * (total // max(1, len(idx)) + 1))[:total]
         idx = idx[rank:total:world]
     elif shuffle:
-        g = torch.Generator().manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+        g = torch.Generator().manual_seed(int(torch.empty((), dtype=torch.int64).random_(generator=generator).item()))
         idx = torch.randperm(n_items, generator=g).tolist()
     else:
         idx = list(range(n_items))

@@ -14,8 +14,10 @@ reference always reads configs/htdemucs.yaml through hydra.  Step semantics kept
     `<work_dir>/best.th` as {"state", "kwargs", "history"} (the keys load_model.py:38-45, 76-102 read back);
   * every epoch ends with `<work_dir>/checkpoint.pth`, the full training state (the place of the solver's checkpoint.th); `resume=<path>`
     or `resume=auto` continues from one (fqss_amd/checkpoint.py).
-Data: `dset.name: synthetic` (seeded Gaussian stems); MUSDB readers, demucs' augmentations (shift / flip / scale / remix /
-repitch), EMA copies, `apply_model` split inference and the SDR evaluation are the reference's CPU / third-party data side."""
+Data: `dset.name: synthetic` (seeded Gaussian stems), or folders of WAV stems (`dset.wav` / `dset.musdb` + `use_musdb`, wav_dataset.py):
+a prefetching reader a batch ahead of the step, int16 samples to the device, demucs' augmentations (shift / flip / scale / remix, restated)
+and the mixture in one fused kernel; validation is un-augmented windows of the training length.  demucs' repitch, EMA copies,
+`apply_model` split inference and the SDR evaluation are the reference's CPU / third-party data side."""
 import json
 import os
 import sys
@@ -30,6 +32,8 @@ from ...quantization.qat.models.htdemucsq import HTDemucsQ
 from ...runtime import KDTrainStep
 from ...utils import set_seed
 from ... import kernels as K
+from ...loader import Prefetcher, epoch_batches
+from . import wav_dataset
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
@@ -77,6 +81,14 @@ class Solver:
         self.history = []
         self.best_state, self.best_loss = None, float("inf")
         self.ckpt_file = os.path.join(conf["work_dir"], checkpoint.NAME)
+        self.sets = None
+        if wav_dataset.configured(conf["dset"]):
+            # refusals first (repitch, a per-GPU batch the remix groups do not divide): nothing is read before them
+            wav_dataset.check_augment_cfg(conf.get("augment"), conf["batch_size"] // comm.world)
+            train_set, valid_set = wav_dataset.build_datasets(conf, device)
+            if len(train_set.sources) != model.n_srcs:
+                raise ValueError(f"dset.sources names {len(train_set.sources)} stems, the model separates {model.n_srcs}")
+            self.sets = {True: train_set, False: valid_set}
 
     def restore(self, ckpt):
         """student, arena, quantizer state, learning rate, teacher and random streams from a training-state checkpoint; then the
@@ -93,14 +105,44 @@ class Solver:
         seed = self.conf.get("seed", 42) * 1000003 + (epoch * 4096 + idx) * self.comm.world + self.comm.rank + (0 if train else 1 << 30)
         return synth_stems(B, self.model.n_srcs, d["channels"], T, seed, self.device)
 
-    def _run_one_epoch(self, epoch, train=True):
-        d = self.conf["dset"]
-        n = d["steps_per_epoch"] if train else d["valid_steps"]
-        tot = torch.zeros(1, device=self.device, dtype=torch.float64)
-        self.model.train(train)
+    def _wav_batches(self, epoch, train):
+        """this rank's batches of the epoch: torch's sampler order (loader.epoch_batches), the single-process permutation drawn from a
+        generator of (seed, epoch) instead of the global RNG, so which examples land in a batch depends on the epoch number alone; a
+        training batch carries the seed of its position, so the reader draws the same augmentation for it in any run that gets there"""
+        conf, comm, ds = self.conf, self.comm, self.sets[train]
+        B = conf["batch_size"] // comm.world if train else 1
+        seed = conf.get("seed", 42)
+        order = torch.Generator().manual_seed(int(seed) * 1000003 + int(epoch))
+        batches = epoch_batches(len(ds), B, shuffle=train, drop_last=True, rank=comm.rank, world=comm.world, seed=seed, epoch=epoch,
+                                generator=order)
+        caps = [conf.get("max_batches")] + ([] if train else [conf["dset"].get("valid_steps")])
+        for cap in caps:
+            if cap is not None:
+                batches = batches[:int(cap)]
+        if not batches:
+            raise ValueError(f"htdemucs env: the {'training' if train else 'validation'} set of {len(ds)} examples gives no batch of {B}")
+        if train:
+            batches = [wav_dataset.SeededBatch(b, wav_dataset.batch_seed(seed, epoch, i, comm.rank, comm.world)) for i, b in enumerate(batches)]
+        return batches
+
+    def _synthetic_batches(self, epoch, n, train):
         for idx in range(n):
             sources = self._batch(epoch, idx, train)
-            mix = sources.sum(dim=1)
+            yield sources.sum(dim=1), sources
+
+    def _run_one_epoch(self, epoch, train=True):
+        pf = None
+        if self.sets is not None:
+            batches = self._wav_batches(epoch, train)
+            n = len(batches)
+            it = pf = Prefetcher(self.sets[train], batches, self.device, depth=int(self.conf.get("prefetch_depth", 2)))
+        else:
+            d = self.conf["dset"]
+            n = d["steps_per_epoch"] if train else d["valid_steps"]
+            it = self._synthetic_batches(epoch, n, train)
+        tot = torch.zeros(1, device=self.device, dtype=torch.float64)
+        self.model.train(train)
+        for mix, sources in it:
             if train:
                 self.step.maybe_capture(mix, sources)
                 tot += self.step(mix, sources)["loss"].double()
@@ -113,6 +155,8 @@ class Solver:
         out = {"loss": tot.item() / (n * self.comm.world), "reco": tot.item() / (n * self.comm.world)}
         if train:
             out["launch"] = "hipGraph replay" if self.step._graphs is not None else "eager"
+        if pf is not None:
+            out["loader_wait_s"] = pf.wait_s      # host time this loop spent blocked on the reader (a loader that keeps up: ~0)
         return out
 
     def train(self):

@@ -1075,6 +1075,17 @@ int fqss_snr_mix(const float* a, const float* b, const float* snr, double* ws, u
  * h [new][2 * width + orig] fp32 taps.                                                                                           */
 int fqss_resample_fir(const float* x, const float* h, float* y, int64_t rows, int64_t L, int64_t Lout, int64_t ld_x, int64_t ld_y,
                       int orig, int newf, int width, fqss_stream_t stream);
+/* Stems of the htdemucs env (train_env/htdemucs_musdbhq/wav_dataset.py): PCM decode, per-track normalisation, demucs' augmentation
+ * chain (Shift, FlipChannels, FlipSign, Scale, Remix of the reference's solver.py:60-69, folded by the host into one table row per output
+ * (b, s)) and the mixture, in one pass.  pcm int16 [B][S][T_in][C], frames interleaved as in the WAV files, C = 1 | 2; S = 1..8.
+ *   b' = src_b[b,s];  c' = (C == 2 && flip[b,s]) ? 1 - c : c;  v = float(pcm[b'][s][t + off[b,s]][c']) * 2^-15;
+ *   normalise != 0: v = (v - mean[b']) / std[b'];   sources[b][s][c][t] = v * gain[b,s];   mix[b][c][t] = sum over s, left to right,
+ * every operation one fp32 rounding.  sources fp32 [B][S][C][T_out], mix fp32 [B][C][T_out]; mean / std [B] (may be NULL when normalise
+ * is 0); src_b / off / flip (int32) and gain (fp32) [B * S], all on the device.  The library cannot read the table: the caller has
+ * checked src_b in [0, B), 0 <= off <= T_in - T_out, flip in {0, 1}, gain finite and std > 0 BEFORE uploading it.                  */
+int fqss_hd_augment_mix(const int16_t* pcm, const float* mean, const float* stdv, const int* src_b, const int* off, const int* flip,
+                        const float* gain, float* sources, float* mix, int B, int S, int C, int64_t T_in, int64_t T_out, int normalise,
+                        fqss_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Descriptor-struct forms of the long entry points ("fqss_<op>_{fwd,bwd}(const FqssTensor* in..,
