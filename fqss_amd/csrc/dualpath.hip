@@ -586,7 +586,7 @@ __global__ __launch_bounds__(256) void k_ola2_bwd(const float* __restrict__ g, f
 // ------------------------------------------------------------------------------------------------ gLN on row matrices
 // GroupNorm(1, C) of the Sepformer dual-path blocks (sepformerq.py:141-142, 159, 175) on the row layouts: the statistics run
 // over ALL rows of a sample; the sample of row r is b = (r % RB) / X  (intra-chunk rows [K][B*S][C]: RB = B*S, X = S;
-// inter-chunk rows [S][B*K][C]: RB = B*K, X = K).  Pass 1 reduces per-sample (sum, sum^2) in fp64 (one wavefront per row,
+// inter-chunk rows [S][B*K][C]: RB = B*K, X = K).  Pass 1 reduces per-sample (sum, sum of squares) in fp64 (one wavefront per row,
 // per-workgroup LDS slots, one fp64 atomic per sample and workgroup); pass 2 applies.  kMaxB samples per launch.
 constexpr int kMaxB = 16;
 
@@ -598,13 +598,15 @@ __global__ __launch_bounds__(256) void k_gnrows_stats(const float* __restrict__ 
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
     for (int64_t r = wave; r < R; r += nw) {
-        float s = 0.f, q = 0.f;
+        // squares and sums in fp64 from the first operation: an fp32 v * v loses |mean|^2 2^-24 per element, which E[x^2] - mean^2
+        // turns into an error of the variance (|mean| / std = 1000: rstd off by 1e-3 relative at 900 elements per sample)
+        double s = 0.0, q = 0.0;
         for (int c = lane; c < C; c += 64) {
-            const float v = x[r * ld + c];
+            const double v = (double)x[r * ld + c];
             s += v;
             q += v * v;
         }
-        double sd = wave_sum((double)s), qd = wave_sum((double)q);
+        double sd = wave_sum(s), qd = wave_sum(q);
         if (lane == 0) {
             const int b = (int)((r % RB) / X);
             atomicAdd(&acc[b][0], sd);

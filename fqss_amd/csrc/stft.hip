@@ -220,13 +220,16 @@ extern "C" int fqss_stft(const float* x, float* z, const float* win, const float
     return launch_status("fqss_stft");
 }
 
-// z [rows][2][T][N/2] -> y [rows][length] (row stride ld_y); frames: workspace of rows*T*N floats; env [hop] = window envelope
+// z [rows][2][T][N/2] -> y [rows][length] (row stride ld_y); frames: workspace of rows*T*N floats; env [hop] = window envelope.
+// hop <= N/2 (N/4 is the model's): with the periodic Hann window the envelope of hop = N is w^2, zero at n = 0, and the division by it
+// could only give non-finite samples -- refused here and in the adjoint
 extern "C" int fqss_istft(const float* z, float* frames, float* y, const float* win, const float* env, const float* tw, int64_t rows,
                           int64_t length, int64_t ld_y, int N, int hop, int T, int pad, fqss_stream_t stream) {
     FQSS_REQUIRE(z && frames && y && win && env && tw, "null pointer");
     int logn;
     if (int rc = check_fft(N, hop, &logn)) return rc;
     FQSS_REQUIRE(rows > 0 && rows <= 65535 && T > 0 && length > 0 && ld_y >= length && pad >= 0, "bad shape");
+    FQSS_REQUIRE(2 * hop <= N, "hop must be at most n_fft / 2: the periodic Hann envelope has a zero at hop = n_fft");
     hipLaunchKernelGGL(k_istft_frames, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, z, frames, win,
                        reinterpret_cast<const float2*>(tw), N, logn, T);
     int64_t gx = cdiv(length, 1024);
@@ -242,6 +245,7 @@ extern "C" int fqss_istft_bwd(const float* g, float* gz, const float* win, const
     int logn;
     if (int rc = check_fft(N, hop, &logn)) return rc;
     FQSS_REQUIRE(rows > 0 && rows <= 65535 && T > 0 && length > 0 && ld_g >= length && pad >= 0, "bad shape");
+    FQSS_REQUIRE(2 * hop <= N, "hop must be at most n_fft / 2: the periodic Hann envelope has a zero at hop = n_fft");
     hipLaunchKernelGGL(k_istft_bwd, dim3((unsigned)T, (unsigned)rows), dim3(kFftThreads), fft_lds_bytes(N), (hipStream_t)stream, g, gz, win, env,
                        reinterpret_cast<const float2*>(tw), N, logn, hop, T, pad, length, ld_g);
     return launch_status("fqss_istft_bwd");

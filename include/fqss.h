@@ -1001,6 +1001,7 @@ int fqss_sample_norm(const float* x, const float* ms, float* y, int64_t B, int64
  * fqss_stft: frames f = 0 .. T-1 of the signal reflect-padded by `pad` on the left (and as needed on the right), scaled by
  *   1/sqrt(N).  fqss_istft: y[j], j < length, of the inverse with 2 zero frames either side, window-envelope division and the
  *   crop by N/2 + pad; `frames` is a workspace of rows*T*N floats.  fqss_istft_bwd: its adjoint (gradient wrt the spectrum).
+ *   Both need hop <= N/2 (hop = N: the envelope win^2 has a zero; FQSS_EINVAL).
  * fqss_transpose2d: y[b][c][r] = x[b][r][c] (dense), the layout change between [.., T, Fr] and the model's [.., Fr, T].         */
 int fqss_stft(const float* x, float* z, const float* win, const float* tw, int64_t rows, int64_t L, int64_t ld_x, int N, int hop, int T,
               int pad, fqss_stream_t stream);
