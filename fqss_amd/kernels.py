@@ -1905,6 +1905,65 @@ def lstm_bwd(gout, whh, gsav, csav, S, B, H, gbias=None, gb4=None):
     return dG
 
 
+LSTMQ_SITES = ("ih", "hh", "add0", "sig0", "sig1", "sig2", "tanh0", "tanh1", "mul0", "mul1", "add1", "mul2")   # order of fqss_lstmq_*'s tables
+LSTMQ_GENERIC_FWD = False   # True: lstmq_fwd on the generic kernel at H = 128 too (fqss_lstmq_fwd_generic; tests patch it)
+
+
+def lstm_gate_fn(x):
+    """(sigmoid(x), tanh(x)) by the gate functions of the LSTM recurrence kernels (csrc/lstm.hip gate_fn)"""
+    _need_gpu(x)
+    x = x.contiguous()
+    sg, th = torch.empty_like(x), torch.empty_like(x)
+    _lib.call("fqss_lstm_gate_fn", _p(x), _p(sg), _p(th), x.numel(), _stream())
+    return sg, th
+
+
+def lstmq_fwd(pre, whh, bhh, ranges, S, B, H, k0=0, k1=None, h0=None, c0=None, save=True, out=None, want_last=False):
+    """recurrence of LSTMQ_static over the steps [k0, k1) (csrc/lstmq.hip).  ranges: 24 (min, max) pairs of device scalars in the order
+    forward direction x LSTMQ_SITES, reverse direction x LSTMQ_SITES (the reverse mul2 pair may be (None, None): never read).
+    out = (hout, hsav, csav) of an earlier launch over other steps of the same sequence (chaining); -> hout, hc_last, hsav, csav"""
+    _need_gpu(pre, whh, bhh)
+    k1 = S if k1 is None else k1
+    assert pre.is_contiguous() and whh.is_contiguous() and bhh.is_contiguous() and len(ranges) == 2 * len(LSTMQ_SITES)
+    assert pre.numel() == S * B * 8 * H and (h0 is None) == (c0 is None)
+    assert all(t is None or (t.is_contiguous() and t.numel() == 2 * B * H) for t in (h0, c0))
+    dev = pre.device
+    if out is not None:
+        hout, hsav, csav = out
+    else:
+        full = k0 == 0 and k1 == S          # (a partial launch leaves the other steps' rows at zero)
+        new = torch.empty if full else torch.zeros
+        hout = new(S, B, 2 * H, device=dev, dtype=torch.float32)
+        hsav = new(S, B, 8 * H, device=dev, dtype=torch.float32) if save else None
+        csav = new(S, B, 2, H, device=dev, dtype=torch.float32) if save else None
+    hc_last = torch.empty(2, 2, B, H, device=dev, dtype=torch.float32) if want_last else None
+    _lib.call("fqss_lstmq_fwd_generic" if LSTMQ_GENERIC_FWD else "fqss_lstmq_fwd", _p(pre), _p(whh), _p(bhh), _p(h0), _p(c0), _ptr_array([t for r in ranges for t in r]), _p(hout), _p(hc_last),
+              _p(hsav), _p(csav), S, B, H, k0, k1, _stream())
+    return hout, hc_last, hsav, csav
+
+
+def lstmq_bwd(gout, whh, pre, hsav, csav, ranges, gaccs, S, B, H, k0=0, k1=None, c0=None, g_hc_last=None, want_state=False, out=None):
+    """-> d_pre, d_hh [S, B, 8H] (gradients at the inputs of fq_ih / fq_hh), d_h0, d_c0 [2, B, H] (want_state); the range partials go to
+    gaccs (24 fp64 slot arrays in the order of `ranges`; the reverse mul2 entry may be None).  out = (d_pre, d_hh) of an earlier launch"""
+    _need_gpu(gout, whh, pre)
+    k1 = S if k1 is None else k1
+    gout = gout.contiguous()
+    assert len(ranges) == 2 * len(LSTMQ_SITES) == len(gaccs) and hsav.is_contiguous() and csav.is_contiguous() and pre.is_contiguous()
+    assert gout.numel() == S * B * 2 * H and all(t is None or (t.is_contiguous() and t.numel() == n * B * H) for t, n in ((c0, 2), (g_hc_last, 4)))
+    dev = gout.device
+    if out is not None:
+        d_pre, d_hh = out
+    else:
+        new = torch.empty if (k0 == 0 and k1 == S) else torch.zeros
+        d_pre = new(S, B, 8 * H, device=dev, dtype=torch.float32)
+        d_hh = new(S, B, 8 * H, device=dev, dtype=torch.float32)
+    d_h0 = torch.empty(2, B, H, device=dev, dtype=torch.float32) if want_state else None
+    d_c0 = torch.empty(2, B, H, device=dev, dtype=torch.float32) if want_state else None
+    _lib.call("fqss_lstmq_bwd", _p(gout), _p(g_hc_last), _p(whh), _p(pre), _p(hsav), _p(csav), _p(c0), _ptr_array([t for r in ranges for t in r]),
+              _ptr_array(list(gaccs)), _p(d_pre), _p(d_hh), _p(d_h0), _p(d_c0), S, B, H, k0, k1, _stream())
+    return d_pre, d_hh, d_h0, d_c0
+
+
 # ================================================================== Sepformer (cfg 4, SURVEY §8 row a14)
 def gnrows_fwd(x, gamma, beta, eps, RB, X, B):
     """gLN over all rows of a sample of a row matrix [..., C]; sample of row r = (r % RB) // X"""

@@ -622,6 +622,109 @@ class LstmBi(Function):
         return gx, gws[0], gws[1], gbs[0], gbs[1], gws[2], gws[3], gbs[2], gbs[3], None, None, None
 
 
+class LstmGate(Function):
+    """sigmoid (th=False) / tanh (th=True) by the recurrence kernels' own gate functions (fqss_lstm_gate_fn): the step-by-step path of
+    LSTMQ_static evaluates the same function as the fused kernel it hands over to"""
+
+    @staticmethod
+    def forward(ctx, x, th):
+        y = K.lstm_gate_fn(x)[1 if th else 0]
+        ctx.save_for_backward(y)
+        ctx.kind = K.UNARY_TANH if th else K.UNARY_SIGMOID
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (y,) = ctx.saved_tensors
+        return K.unary_bwd(g, y, ctx.kind), None
+
+
+LSTMQ_LAUNCHES = 0      # fused launches of LstmBiQ.forward so far (the tests' launch counter)
+
+
+class LstmBiQ(Function):
+    """The steps [k0, S) of LSTMQ_static's bidirectional recurrence (qat_layers.py:741-862 of the reference) on sequence-first input
+    [S, B, I], all 23 used step quantizers in their quantizing phase, from the carried state h0 / c0 [2, B, H] of the step-by-step
+    prefix (k0 = 0: None, zeros): ONE launch of the quantized recurrence kernel each way (csrc/lstmq.hip).  Rows of the result that
+    belong to steps before k0 are zero.  aqs: the 24 quantizer modules, forward direction x K.LSTMQ_SITES then reverse; their 48 range
+    tensors follow as inputs so that autograd carries the range gradients of un-deferred quantizers."""
+
+    @staticmethod
+    def forward(ctx, x, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, h0, c0, k0, xq, wc_f, wc_r, aqs, *ranges):
+        global LSTMQ_LAUNCHES
+        S, B, I = x.shape
+        H = whh_f.shape[1]
+        x = x.contiguous()
+        on_codes = QROW and xq is not None and wc_f is not None and wc_r is not None and K.qrow_eligible(I) \
+            and xq.idx.shape == x.shape and xq.idx.is_contiguous()
+        wih, whh, bih, bhh = _lstm_pack(wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, on_codes)
+        if on_codes:
+            pre = torch.empty(S, B, 8 * H, device=x.device, dtype=torch.float32)
+            K.qrow_fwd(xq.idx, wc_f, bih_f, xq.qmin, xq.qmax, out=pre[..., :4 * H])
+            K.qrow_fwd(xq.idx, wc_r, bih_r, xq.qmin, xq.qmax, out=pre[..., 4 * H:])
+        else:
+            pre = K.rowlin_fwd(x, wih, bih)
+        used = list(range(len(aqs) - 1))                    # the reverse direction's mul2 (the last one) is never called: not even counted
+        qs = [aqs[i].qctx() for i in used] + [None]
+        if any(qs[i].qmode != ops.Q_QUANT for i in used):
+            raise RuntimeError("LstmBiQ: a step quantizer is still observing (the step-by-step prefix serves those steps)")
+        pairs = [(qs[i].qmin, qs[i].qmax) for i in used] + [(None, None)]
+        if h0 is not None:
+            h0, c0 = h0.contiguous(), c0.contiguous()
+        save = any(ctx.needs_input_grad)
+        hout, _, hsav, csav = K.lstmq_fwd(pre, whh, bhh, pairs, S, B, H, k0=k0, h0=h0, c0=c0, save=save)
+        LSTMQ_LAUNCHES += 1
+        ctx.save_for_backward(x, wih, whh, hout, pre, hsav, csav, h0, c0)
+        ctx.params = (bih_f, bhh_f, bih_r, bhh_r)
+        ctx.weights = (wih_f, whh_f, wih_r, whh_r)
+        ctx.xq = xq if on_codes else None
+        ctx.qs, ctx.used, ctx.k0, ctx.pairs = qs, used, k0, pairs
+        touch(wih_f, whh_f, wih_r, whh_r)
+        return hout
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, wih, whh, hout, pre, hsav, csav, h0, c0 = ctx.saved_tensors
+        S, B, I = x.shape
+        H = whh.shape[2]
+        qs, used, k0 = ctx.qs, ctx.used, ctx.k0
+        gaccs = [qs[i].gacc if qs[i].gacc is not None else torch.zeros(K.GACC_DOUBLES, dtype=torch.float64, device=x.device) for i in used] + [None]
+        d_pre, d_hh, d_h0, d_c0 = K.lstmq_bwd(gout, whh, pre, hsav, csav, ctx.pairs, gaccs, S, B, H, k0=k0, c0=c0, want_state=h0 is not None)
+        gx = K.rowlin_bwd_x(d_pre, wih) if ctx.needs_input_grad[0] else None
+        # the two clip masks differ, so b_ih takes the column sums of d_pre and b_hh those of d_hh
+        gbufs = [_param_grad(p, p) for p in ctx.params]
+        for (buf, _), img, lo in zip(gbufs, (d_pre, d_hh, d_pre, d_hh), (0, 0, 4 * H, 4 * H)):
+            K.colsum(img[..., lo:lo + 4 * H], buf)
+        slots = [getattr(w, "_fqss_gwq", None) for w in ctx.weights]      # wih_f, whh_f, wih_r, whh_r (see LstmBi.backward)
+        if slots[0] is not None and slots[2] is not None:
+            _rowlinear_wgrad_pair_into(d_pre[..., :4 * H], d_pre[..., 4 * H:], x, ctx.xq, slots[0], slots[2])
+            gws = [None, None, None, None]
+        else:
+            gwih = torch.zeros_like(wih)
+            K.rowlin_bwd_w(d_pre, x, gwih)
+            gws = [gwih[:4 * H], None, gwih[4 * H:], None]
+        ghh = [slots[1] if slots[1] is not None else torch.zeros_like(whh[0]), slots[3] if slots[3] is not None else torch.zeros_like(whh[1])]
+        if S - k0 > 1:
+            # step k of the forward direction is time k, of the reverse direction time S-1-k: d_hh of step k with h of step k-1
+            K.rowlin_bwd_w_pair(d_hh[k0 + 1:, :, :4 * H], hout[k0:S - 1, :, :H], ghh[0], d_hh[:S - 1 - k0, :, 4 * H:], hout[1:S - k0, :, H:], ghh[1])
+        if h0 is not None:                  # step k0 pairs with the carried state
+            K.rowlin_bwd_w(d_hh[k0, :, :4 * H], h0[0], ghh[0])
+            K.rowlin_bwd_w(d_hh[S - 1 - k0, :, 4 * H:], h0[1], ghh[1])
+        gws[1] = None if slots[1] is not None else ghh[0]
+        gws[3] = None if slots[3] is not None else ghh[1]
+        if (slots[0] is None) != (slots[2] is None):
+            for i in (0, 2):
+                if slots[i] is not None:
+                    K.axpby_(slots[i], gws[i], 1.0)
+                    gws[i] = None
+        gbs = [None if direct else buf for buf, direct in gbufs]
+        grads = []
+        for i in used:
+            grads += list(ops._ranges_after(qs[i], gaccs[i]))
+        grads += [None, None]
+        return (gx, gws[0], gws[1], gbs[0], gbs[1], gws[2], gws[3], gbs[2], gbs[3], d_h0, d_c0, None, None, None, None, None, *grads)
+
+
 class GroupNormRows(Function):
     """GroupNorm(1, C) of a dual-path block on a row layout (sepformerq.py:159, 175): statistics over all rows of a sample;
     geom = (RB, X, B): sample of row r = (r % RB) // X"""

@@ -21,7 +21,7 @@ from ....process import postprocess, preprocess
 from .. import qat_layers as QL
 from ..float_exec import HipSequential, apply_module
 from ..qat_layers import Add, Mul
-from ..qat_utils import quantize_modules, replace_decoderq, replace_encoderq
+from ..qat_utils import check_lstm_quant, quantize_modules, replace_decoderq, replace_encoderq
 
 
 def overlap_and_add(signal, frame_step):
@@ -319,9 +319,10 @@ class DPTNetQ(nn.Module):
         self.n_combiner = n_combiner
 
     def quantize_model(self, gradient_based=True, weight_quant=True, weight_n_bits=8, act_quant=True, act_n_bits=8,
-                       inout_nl_quant=False, in_quant=False, in_act_n_bits=8, out_quant=True, out_act_n_bits=8):
+                       inout_nl_quant=False, in_quant=False, in_act_n_bits=8, out_quant=True, out_act_n_bits=8, lstm_quant="weights"):
+        """lstm_quant: "weights" (LSTMQ) or "static" (LSTMQ_static: the recurrence's twelve step quantizers per direction as well)"""
         p = {"gradient_based": gradient_based, "act_quant": act_quant, "weight_quant": weight_quant,
-             "weight_n_bits": weight_n_bits, "act_n_bits": act_n_bits}
+             "weight_n_bits": weight_n_bits, "act_n_bits": act_n_bits, "lstm_quant": check_lstm_quant(lstm_quant)}
         io = {"gradient_based": gradient_based, "act_quant": act_quant, "inout_nl_quant": inout_nl_quant,
               "weight_quant": weight_quant, "weight_n_bits": weight_n_bits}
         for _, m in list(self.named_modules()):

@@ -3,6 +3,7 @@ import torch
 
 from ..qat_layers import LayerQ
 from ..qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize
+from ..qat_utils import check_lstm_quant
 from .convtasnetq import ConvTasNetQ
 from .dptnetq import DPTNetQ
 from .htdemucsq import HTDemucsQ
@@ -46,11 +47,16 @@ def quantize_model(model, quant_cfg):
     if quant_cfg.get("qat", False):
         g = quant_cfg.get
         model.set_splitter_combiner(g("n_splitter", 1), g("n_combiner", 1))
+        extra = {}
+        if check_lstm_quant(g("lstm_quant", "weights")) != "weights":       # absent: LSTMQ, as every existing config has it
+            if not isinstance(model, DPTNetQ):
+                raise NotImplementedError("lstm_quant: static quantizes the recurrence of DPTNet's LSTMs; this model has none")
+            extra["lstm_quant"] = g("lstm_quant")
         model.quantize_model(gradient_based=g("gradient_based", True), weight_quant=g("weight_quant", True),
                              weight_n_bits=g("weight_n_bits", 8), act_quant=g("act_quant", True),
                              act_n_bits=g("act_n_bits", 8), inout_nl_quant=g("inout_nl_quant", False),
                              in_quant=g("in_quant", False), in_act_n_bits=g("in_act_n_bits", 8),
-                             out_quant=g("out_quant", False), out_act_n_bits=g("out_act_n_bits", 8))
+                             out_quant=g("out_quant", False), out_act_n_bits=g("out_act_n_bits", 8), **extra)
         enable_observer(model, g("observer", False))
     return model
 

@@ -7,7 +7,8 @@ LayerQ (:49-59), AddQ/SubQ/MulQ (:62-101), Conv1dQ (:124-153), Conv1dNlQ (:188-2
 GroupNormQ (:438-452), NlQ (:511-518), Conv1dEncoderQ (:993-1046), ResidualErrorBlock (:1105-1202),
 ConvTr1dDecoderQ (:1305-1361); and, for the dual-path models (DPTNet): LayerNormQ (:455-465),
 LinearQ (:521-536), LSTMQ (:571-600), MultiheadAttentionQ (:865-950), Conv2dQ (1x1), LinearDecoderQ (:1256-1296) with the
-nn.Linear branch of ResidualErrorBlock (:1178-1187), over the kernels of csrc/dualpath.hip, attn.hip, lstm.hip.
+nn.Linear branch of ResidualErrorBlock (:1178-1187), over the kernels of csrc/dualpath.hip, attn.hip, lstm.hip; LSTMQ_static (:741-862,
+the recurrence's own twelve step quantizers per direction) over csrc/lstmq.hip.
 The Sepformer / HTDemucs classes (LinearNlQ, Conv2dNlQ, ConvTranspose*Q, Conv1dGnNlQ, ConvTr2dDecoderQ, ...) and BatchNormQ follow
 further down on the kernels of csrc/conv_frames.hip, hd_ops.hip, batchnorm.hip; variants of these layers that no FQSS configuration takes
 (see docs/history/DESIGN_rounds_1-5.md 8) raise NotImplementedError at construction -- there is no ATen fallback.
@@ -655,7 +656,8 @@ class ResidualErrorBlock(LayerQ):
 
 
 def _observing(aq):
-    return bool(getattr(aq, "observer_mode", False)) and aq.n_iter < aq.max_observations
+    """a learned-range quantizer inside its observer phase (GradientActivationFakeQuantize.observing); False for a bypass"""
+    return hasattr(aq, "observing") and aq.observing()
 
 
 def _decoder_window(layer, window, convtr):
@@ -1087,6 +1089,94 @@ class LSTMQ(LayerQ):
         """post_relu (not in the reference's signature): the caller's F.relu on the output, folded into the output quantizer's pass"""
         weights = {n: q(getattr(self.lstm, n)) for n, q in self.weight_quantizers_dict.items()}
         return [run_lstm(self.lstm, x, weights, self.activation_fake_quantize, post_relu)]
+
+
+FUSE_LSTMQ = True   # False: the whole sequence of LSTMQ_static step by step, no fused recurrence launch (tests patch it)
+
+
+def _lstmq_step(xt, h, c, wih, whh, bih, bhh, q, aq_mul2):
+    """one time step of one direction of LSTMQ_static (qat_layers.py:811-821 of the reference) as separate nodes: row linears, each
+    quantizer module through fq_node (so each dispatches on its own observer count), the recurrence kernels' own gate functions"""
+    gate = ops_dp.LstmGate.apply
+    add = lambda a, b: ops.AddActQ.apply(a, b, None, None, 1.0, ops.BYPASS)
+    mul = lambda a, b: _mul_any(a, b, None, None, ops.BYPASS)
+    ih = fq_node(q["ih"], ops_dp.RowLinear.apply(xt, wih, bih))
+    hh = fq_node(q["hh"], ops_dp.RowLinear.apply(h, whh, bhh))
+    gates = fq_node(q["add0"], add(ih, hh))
+    gi, gf, gg, go = (t.contiguous() for t in gates.chunk(4, 1))
+    gi = fq_node(q["sig0"], gate(gi, False))
+    gf = fq_node(q["sig1"], gate(gf, False))
+    gg = fq_node(q["tanh0"], gate(gg, True))
+    go = fq_node(q["sig2"], gate(go, False))
+    c = fq_node(q["add1"], add(fq_node(q["mul0"], mul(gf, c)), fq_node(q["mul1"], mul(gi, gg))))
+    h = fq_node(aq_mul2, mul(go, fq_node(q["tanh1"], gate(c, True))))
+    return h, c
+
+
+def run_lstmq(layer, x, weights, post_relu=False):
+    """LSTMQ_static.forward: the observing prefix -- the steps until every used step quantizer has left its observer, at most 50 time
+    steps in the life of a run -- step by step, the rest of the sequence as one launch of the quantized recurrence (ops_dp.LstmBiQ)
+    from the prefix's carried state"""
+    lstm = layer.lstm
+    _lstm_check(lstm)
+    xq = getattr(x, "_fqss_rowq", None)
+    x = ops.real(x)
+    S, B, _ = x.shape
+    H = lstm.hidden_size
+    aq_f = [getattr(layer, f"activation_fake_quantize_{s}") for s in K.LSTMQ_SITES]
+    aq_r = [getattr(layer, f"activation_fake_quantize_{s}_r") for s in K.LSTMQ_SITES]
+    used = aq_f + aq_r[:-1]             # the reverse direction's h goes through the FORWARD direction's mul2 (the reference's :835)
+    q_f, q_r = dict(zip(K.LSTMQ_SITES, aq_f)), dict(zip(K.LSTMQ_SITES, aq_r))
+    w_f = (weights["weight_ih_l0"], weights["weight_hh_l0"], lstm.bias_ih_l0, lstm.bias_hh_l0)
+    w_r = (weights["weight_ih_l0_reverse"], weights["weight_hh_l0_reverse"], lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse)
+    k0, outs_f, outs_r = 0, [], []
+    hf = cf = hr = cr = None
+    while k0 < S and (not FUSE_LSTMQ or any(a.observing() for a in used)):
+        if k0 == 0:
+            hf, cf, hr, cr = (torch.zeros(B, H, device=x.device, dtype=torch.float32) for _ in range(4))
+        hf, cf = _lstmq_step(x[k0], hf, cf, *w_f, q_f, aq_f[-1])              # (forward direction first: mul2's call order)
+        hr, cr = _lstmq_step(x[S - 1 - k0], hr, cr, *w_r, q_r, aq_f[-1])
+        outs_f.append(hf)
+        outs_r.append(hr)
+        k0 += 1
+    if k0 < S:
+        state = (torch.stack([hf, hr]), torch.stack([cf, cr])) if k0 else (None, None)
+        ranges = [r for a in aq_f + aq_r for r in (a.min_range, a.max_range)]
+        hout = ops_dp.LstmBiQ.apply(x, *w_f, *w_r, *state, k0, xq, getattr(w_f[0], "_fqss_wcodes", None), getattr(w_r[0], "_fqss_wcodes", None),
+                                    aq_f + aq_r, *ranges)
+        if k0 == 0:
+            y = hout
+        else:
+            y = torch.cat([torch.cat([torch.stack(outs_f), hout[k0:, :, :H]], 0), torch.cat([hout[:S - k0, :, H:], torch.stack(outs_r[::-1])], 0)], -1)
+    else:
+        y = torch.cat([torch.stack(outs_f), torch.stack(outs_r[::-1])], -1)
+    aq = layer.activation_fake_quantize
+    return fq_node(aq, y, post_relu=True) if post_relu else fq_node(aq, y)
+
+
+class LSTMQ_static(LSTMQ):
+    """LSTMQ with the reference's twelve learned-range activation quantizers per direction inside the recurrence, applied at every time
+    step (qat_layers.py:741-862 of the reference; `model_cfg.quantization.lstm_quant: static`).  Same constructor and state_dict keys.
+    The step quantizers count TIME STEPS while observing: the first 50 processed steps of the first forward are un-quantized and update
+    the ranges by EMA, later steps quantize.  Kept from the reference for checkpoint compatibility: the reverse direction's h goes through
+    the forward direction's `activation_fake_quantize_mul2` (two calls per step, observer left after 25 steps);
+    `activation_fake_quantize_mul2_r` is never called."""
+
+    def __init__(self, lstm, gradient_based=True, weight_quant=True, act_quant=True, act_n_bits=8, weight_n_bits=8):
+        super().__init__(lstm, gradient_based=gradient_based, weight_quant=weight_quant, act_quant=act_quant, act_n_bits=act_n_bits,
+                         weight_n_bits=weight_n_bits)
+        for sfx in ("", "_r"):          # the reference's attribute names in its registration order (:755-779)
+            for site in ("ih", "hh", "add0", "add1", "mul0", "mul1", "mul2", "sig0", "sig1", "sig2", "tanh0", "tanh1"):
+                setattr(self, f"activation_fake_quantize_{site}{sfx}",
+                        get_activation_quantizer(gradient_based, n_bits=act_n_bits) if act_quant else _BypassQuantizer())
+        if act_quant:
+            self.activation_fake_quantize_mul2_r.never_called = True     # keeps (-0.5, 0.5) and n_iter 0: the training step does not wait for it
+
+    def forward(self, x, post_relu=False):
+        weights = {n: q(getattr(self.lstm, n)) for n, q in self.weight_quantizers_dict.items()}
+        if not self.act_quant:          # (identity step quantizers: the plain recurrence)
+            return [run_lstm(self.lstm, x, weights, self.activation_fake_quantize, post_relu)]
+        return [run_lstmq(self, x, weights, post_relu)]
 
 
 class MultiheadAttentionQ(LayerQ):

@@ -131,6 +131,12 @@ class GradientActivationFakeQuantize(nn.Module):
     def enable_observer(self, observer_mode):
         self.observer_mode = observer_mode
 
+    never_called = False    # set by a layer on a quantizer its forward never reaches (LSTMQ_static's mul2_r): nobody waits for its observer
+
+    def observing(self):
+        """still inside the observer phase (what the training step waits for before it builds tables and captures graphs)"""
+        return bool(self.observer_mode and self.n_iter < self.max_observations and not self.never_called)
+
     # -- fused entry points used by the LayerQ modules ---------------------------------------
     def next_mode(self):
         """advance the host-side observer counter exactly like qat_quant.py:228-229"""

@@ -49,7 +49,23 @@ quant_conv1d_nl, quant_conv2d_nl = _wa(QL.Conv1dNlQ), _wa(QL.Conv2dNlQ)
 quant_conv1d_gn_nl = _wa(QL.Conv1dGnNlQ)
 quant_convtr1d_nl, quant_convtr2d_nl = _wa(QL.ConvTranspose1dNlQ), _wa(QL.ConvTranspose2dNlQ)
 quant_groupnorm, quant_layernorm, quant_batchnorm = _a(QL.GroupNormQ), _a(QL.LayerNormQ), _a(QL.BatchNormQ)
-quant_embedding, quant_lstm, quant_mha = _wa(QL.EmbeddingQ), _wa(QL.LSTMQ), _wa(QL.MultiheadAttentionQ)
+quant_embedding, quant_mha = _wa(QL.EmbeddingQ), _wa(QL.MultiheadAttentionQ)
+LSTM_QUANT = ("weights", "static")      # model_cfg.quantization.lstm_quant
+
+
+def check_lstm_quant(value):
+    if value not in LSTM_QUANT:
+        raise ValueError(f"lstm_quant must be one of {LSTM_QUANT[0]!r} (weights and layer output: LSTMQ) or {LSTM_QUANT[1]!r} (also the twelve "
+                         f"step quantizers per direction: LSTMQ_static), got {value!r}")
+    return value
+
+
+def quant_lstm(lstm, params_dict):
+    """LSTMQ, or LSTMQ_static with `lstm_quant: static` in params_dict (absent: weights)"""
+    kind = check_lstm_quant(params_dict.get("lstm_quant", "weights"))
+    return (QL.LSTMQ_static if kind == "static" else QL.LSTMQ)(lstm, **_pick(params_dict, *_WA))
+
+
 quant_linear, quant_linear_nl = _wa(QL.LinearQ), _wa(QL.LinearNlQ)
 quant_nl, quant_add, quant_sub, quant_mul, quant_div, quant_const = (_a(QL.NlQ), _a(QL.AddQ), _a(QL.SubQ), _a(QL.MulQ),
                                                                     _a(QL.DivQ), _a(QL.ConstQ))

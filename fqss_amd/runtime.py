@@ -644,7 +644,7 @@ class KDTrainStep:
     def can_capture(self):
         from .quantization.qat.qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize
         for m in self.model.modules():
-            if isinstance(m, GradientActivationFakeQuantize) and m.observer_mode and m.n_iter < m.max_observations:
+            if isinstance(m, GradientActivationFakeQuantize) and m.observing():
                 return False
             if isinstance(m, GradientWeightFakeQuantize) and m.observer_mode:
                 return False
@@ -803,7 +803,7 @@ class KDTrainStep:
         if self.tables is None:
             from .quantization.qat.qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize
             for m in self.model.modules():
-                if isinstance(m, GradientActivationFakeQuantize) and m.observer_mode and m.n_iter < m.max_observations:
+                if isinstance(m, GradientActivationFakeQuantize) and m.observing():
                     return None
                 if isinstance(m, GradientWeightFakeQuantize) and m.observer_mode:
                     return None
@@ -866,7 +866,7 @@ class KDTrainStep:
         from .quantization.qat.qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize
         for m in self.model.modules():
             if isinstance(m, GradientActivationFakeQuantize):
-                assert not (m.observer_mode and m.n_iter < m.max_observations), "capture() needs the observer phase to be over"
+                assert not m.observing(), "capture() needs the observer phase to be over"
             if isinstance(m, GradientWeightFakeQuantize):
                 assert not m.observer_mode, "capture() needs the weight observers to have run"
         self._maybe_sync_ranges()

@@ -863,6 +863,33 @@ int fqss_lstm_bwd_b(const float* gout, const float* whh, const float* gsav, cons
  * direction, b_ih, b_hh of the reverse direction ([4H] each, "+=") */
 int fqss_lstm_bwd_b4(const float* gout, const float* whh, const float* gsav, const float* csav, float* dG, float* const* gb, int S,
                      int B, int H, fqss_stream_t stream);
+/* Recurrence of LSTMQ_static (qat_layers.py:741-862): the same LSTM with twelve learned-range 8-bit activation quantizers per
+ * direction at every time step (csrc/lstmq.hip has the op sequence).  Quantizer order within a direction:
+ *   ih, hh, add0, sig0, sig1, sig2, tanh0, tanh1, mul0, mul1, add1, mul2.
+ *   ranges: host array of 2 x 12 x {min, max} device scalars, forward direction first; gaccs: host array of 2 x 12 device pointers
+ *           (FQSS_GACC_SLOTS x 3 doubles each, "+=" into one slot per workgroup as fqss_actq_bwd; past 2 ceil(B / 2) = FQSS_GACC_SLOTS
+ *           workgroups the slots are shared through fp64 atomics).
+ *           Both directions' h use the FORWARD direction's mul2 (the reference's forward, :835); the reverse direction's mul2 entries
+ *           are never dereferenced and may be NULL.
+ *   pre  [S][B][2][4H] = x W_ih^T + b_ih, un-quantized (fq_ih is applied inside);  whh [2][4H][H], bhh [2][4H]
+ *   The call processes the steps [k0, k1) of the S-step sequence in processing order: step k is time k in the forward direction and
+ *   time S-1-k in the reverse direction.  h0 / c0 [2][B][H]: the state after step k0-1 (both NULL: zeros); hc_last [2][2][B][H]
+ *   (nullable): h | c after step k1-1.  hout [S][B][2H] is written at the times of those steps only.
+ *   hsav [S][B][2][4H] (W_hh h + b_hh in front of fq_hh) and csav [S][B][2][H] (cell state) are what the backward needs besides
+ *   pre and c0: 20 H bytes per (step, sequence, direction); both NULL: inference, nothing saved.
+ * bwd: gout [S][B][2H], g_hc_last [2][2][B][H] (gradient of hc_last, nullable) -> d_pre / d_hh [S][B][2][4H], the gradients at the
+ *   inputs of fq_ih / fq_hh (written at the times of the steps [k0, k1) only), d_h0 / d_c0 [2][B][H] (nullable).  The caller
+ *   finishes with row GEMMs: gx = d_pre W_ih, gW_ih += d_pre^T x, gb_ih += colsum(d_pre), gb_hh += colsum(d_hh),
+ *   gW_hh[d] += d_hh_d[step k]^T h_d[step k-1] (h0 at k = k0).  Chaining [0, k) and [k, S) gives the bits of [0, S). */
+int fqss_lstmq_fwd(const float* pre, const float* whh, const float* bhh, const float* h0, const float* c0, const float* const* ranges,
+                   float* hout, float* hc_last, float* hsav, float* csav, int S, int B, int H, int k0, int k1, fqss_stream_t stream);
+/* Test hook: fqss_lstmq_fwd on the generic kernel at every H (fqss_lstmq_fwd itself takes the register-resident form at H = 128) */
+int fqss_lstmq_fwd_generic(const float* pre, const float* whh, const float* bhh, const float* h0, const float* c0,
+                           const float* const* ranges, float* hout, float* hc_last, float* hsav, float* csav, int S, int B, int H, int k0,
+                           int k1, fqss_stream_t stream);
+int fqss_lstmq_bwd(const float* gout, const float* g_hc_last, const float* whh, const float* pre, const float* hsav, const float* csav,
+                   const float* c0, const float* const* ranges, double* const* gaccs, float* d_pre, float* d_hh, float* d_h0,
+                   float* d_c0, int S, int B, int H, int k0, int k1, fqss_stream_t stream);
 
 /* Sepformer (cfg 4 -- SURVEY.md §8 row a14): gLN and the positional-encoding add on the dual-path row layouts.
  * GroupNorm(1, C) over ALL rows of a sample of a row matrix x [R][C]; the sample of row r is b = (r % RB) / X
