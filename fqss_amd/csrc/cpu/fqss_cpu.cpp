@@ -7,6 +7,7 @@
 // anything else is absent from this library and fqss_amd/_lib.py raises.  Arithmetic: the same op sequences as the HIP kernels
 // (fp32, one IEEE operation per operator: built with -ffp-contract=off; IEEE division; round-half-even), reductions in fp64.
 // NOT the oracle: oracle/ is test infrastructure and is never loaded by the product; this file is product code selected by --use_cpu.
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -720,6 +721,204 @@ int fqss_kd_loss(const float* est, const float* fest, const float* tgt, int B, i
                 float* g = gest + ((int64_t)b * 2 + i) * T;
                 for (int64_t t = 0; t < T; ++t) g[t] = A * (e[t] - me) + Bt * (tt[t] - mt) + Bf * (ff[t] - mf);
             }
+        }
+    }
+    return FQSS_OK;
+}
+
+// the loss for n_src = S in 1..3 (include/fqss.h: fqss_kd_loss_n), a plain fp64 restatement of csrc/train_ops.hip's k_kd_*_n: the
+// moment row, the four PIT reductions over itertools.permutations order (first wins ties), the three modes, the gradient map
+namespace {
+void kd_moments_row(const float* est, const float* fest, const float* tgt, int b, int S, int64_t T, double* m) {
+    const int NM = 6 * S + 3 * S * S;
+    for (int i = 0; i < NM; ++i) m[i] = 0.0;
+    const float* sig[9];
+    for (int i = 0; i < S; ++i) {
+        sig[i] = est + ((int64_t)b * S + i) * T;
+        sig[S + i] = fest + ((int64_t)b * S + i) * T;
+        sig[2 * S + i] = tgt + ((int64_t)b * S + i) * T;
+    }
+    for (int64_t t = 0; t < T; ++t) {
+        double s[9];
+        for (int i = 0; i < 3 * S; ++i) s[i] = (double)sig[i][t];
+        for (int i = 0; i < 3 * S; ++i) {
+            m[i] += s[i];
+            m[3 * S + i] += s[i] * s[i];
+        }
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j) {
+                m[6 * S + i * S + j] += s[i] * s[2 * S + j];
+                m[6 * S + S * S + i * S + j] += s[i] * s[S + j];
+                m[6 * S + 2 * S * S + i * S + j] += s[S + i] * s[2 * S + j];
+            }
+    }
+}
+}  // namespace
+
+int fqss_kd_moments_n(const float* est, const float* fest, const float* tgt, int B, int S, int64_t T, double* stats, fqss_stream_t) {
+    REQUIRE(est && fest && tgt && stats, "null tensor");
+    REQUIRE(S >= 1 && S <= 3, "n_src must be in 1..3");
+    REQUIRE(B > 0 && B <= 1024 && T > 0, "B must be in 1..1024");
+    for (int b = 0; b < B; ++b) {
+        double* m = stats + (int64_t)b * FQSS_KD_STATS_STRIDE_N;
+        for (int i = 0; i < FQSS_KD_STATS_STRIDE_N; ++i) m[i] = 0.0;
+        kd_moments_row(est, fest, tgt, b, S, T, m);
+    }
+    return FQSS_OK;
+}
+
+int fqss_kd_loss_n(const float* est, const float* fest, const float* tgt, int B, int S, int64_t T, float kd_lambda, int mode,
+                   int use_threshold, float threshold, double* stats, float* out, float* w_out, float* sisdr_out, float* gest,
+                   fqss_stream_t) {
+    REQUIRE(est && fest && tgt && stats && out && w_out && sisdr_out, "null tensor");
+    REQUIRE(S >= 1 && S <= 3, "n_src must be in 1..3");
+    REQUIRE(B > 0 && B <= 1024 && T > 0, "B must be in 1..1024");
+    REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (asteroid), 1 (per sample) or 2 (teacher-free PIT SI-SDR)");
+    REQUIRE(mode != 1 || B == 1 || B == S,
+            "the per-sample KD weights broadcast [1, n_src, n_src] * [1, B]: B must be 1 or n_src (the reference raises otherwise)");
+    std::vector<std::vector<int>> perms;
+    {
+        std::vector<int> p((size_t)S);
+        for (int i = 0; i < S; ++i) p[(size_t)i] = i;
+        do perms.push_back(p);
+        while (std::next_permutation(p.begin(), p.end()));      // lexicographic = itertools.permutations(range(S))
+    }
+    const int oET = 6 * S, oEF = 6 * S + S * S, oFT = 6 * S + 2 * S * S;
+    const double Td = (double)T, lam = (double)kd_lambda;
+    struct Smp {
+        double rt[3][3], rf[3][3], w, task, kd, pit_db;
+        int pt, pf;
+    };
+    std::vector<Smp> smp((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        double* m = stats + (int64_t)b * FQSS_KD_STATS_STRIDE_N;
+        for (int i = 0; i < FQSS_KD_STATS_STRIDE_N; ++i) m[i] = 0.0;
+        kd_moments_row(est, fest, tgt, b, S, T, m);
+        Smp& q = smp[(size_t)b];
+        double nl_ft[3][3], nl_et[3][3];
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j) {
+                q.rt[i][j] = pair_sdr(m[i], m[2 * S + j], m[3 * S + i], m[5 * S + j], m[oET + i * S + j], Td).sdr;
+                q.rf[i][j] = pair_sdr(m[i], m[S + j], m[3 * S + i], m[4 * S + j], m[oEF + i * S + j], Td).sdr;
+                const double ft = pair_sdr(m[S + i], m[2 * S + j], m[4 * S + i], m[5 * S + j], m[oFT + i * S + j], Td).sdr;
+                nl_ft[i][j] = -10.0 * log10(ft + kEps);
+                nl_et[i][j] = -10.0 * log10(q.rt[i][j] + kEps);
+            }
+        double sdrs = 0.0, sdrqs = 0.0, tbest = 0.0;
+        int pe = 0;
+        q.pt = 0;
+        for (size_t k = 0; k < perms.size(); ++k) {
+            const std::vector<int>& p = perms[k];
+            double lf = 0.0, le = 0.0, tq = 0.0;
+            for (int i = 0; i < S; ++i) {
+                lf += nl_ft[p[(size_t)i]][i];
+                le += nl_et[p[(size_t)i]][i];
+                tq += q.rt[p[(size_t)i]][i];
+            }
+            lf /= (double)S;
+            le /= (double)S;
+            tq = -tq / (double)S;
+            if (k == 0 || lf < sdrs) sdrs = lf;
+            if (k == 0 || le < sdrqs) sdrqs = le, pe = (int)k;
+            if (k == 0 || tq < tbest) tbest = tq, q.pt = (int)k;
+        }
+        q.w = pow(10.0, (sdrs - sdrqs) / 10.0);
+        q.task = -tbest;
+        q.pit_db = sdrqs;
+        if (mode == 2) q.pt = pe;
+        w_out[b] = (float)q.w;
+        sisdr_out[b] = (float)(-sdrqs);
+    }
+    double task = 0.0, kd = 0.0;
+    for (int b = 0; b < B; ++b) {
+        Smp& q = smp[(size_t)b];
+        double kbest = 0.0;
+        q.pf = 0;
+        for (size_t k = 0; k < perms.size(); ++k) {
+            const std::vector<int>& p = perms[k];
+            double kq = 0.0;
+            for (int i = 0; i < S; ++i) {
+                const int j = p[(size_t)i];     // student source j on teacher source i
+                kq += ((mode == 1 && B == S) ? smp[(size_t)j].w : q.w) * q.rf[j][i];
+            }
+            kq = -kq / (double)S;
+            if (k == 0 || kq < kbest) kbest = kq, q.pf = (int)k;
+        }
+        q.kd = -kbest;
+        task += q.task;
+        kd += q.kd;
+    }
+    task /= (double)B;
+    kd /= (double)B;
+    std::vector<double> gt((size_t)B, 0.0), gkw((size_t)B, 0.0);     // the KD coefficient of student source j is gkw * (its weight)
+    if (mode == 2) {
+        double l = 0.0;
+        for (int b = 0; b < B; ++b) l += smp[(size_t)b].pit_db;
+        out[0] = (float)(l / (double)B);
+        out[1] = 0.0f;
+        out[2] = (float)task;
+        out[3] = 0.0f;
+    } else if (mode == 0) {
+        const double arg = (1.0 - lam) * task + lam * kd + kEps, dL = -10.0 / (log(10.0) * arg);
+        out[0] = (float)(-10.0 * log10(arg));
+        out[1] = (float)(-10.0 * log10(kd + kEps));
+        out[2] = (float)task;
+        out[3] = (float)kd;
+        for (int b = 0; b < B; ++b) {
+            gt[(size_t)b] = dL * (1.0 - lam) / ((double)S * (double)B);
+            gkw[(size_t)b] = dL * lam / ((double)S * (double)B);
+        }
+    } else {
+        std::vector<double> arg_b((size_t)B), loss_b((size_t)B);
+        int nkeep = 0;
+        for (int b = 0; b < B; ++b) {
+            arg_b[(size_t)b] = (1.0 - lam) * smp[(size_t)b].task + lam * smp[(size_t)b].kd + kEps;
+            loss_b[(size_t)b] = -10.0 * log10(arg_b[(size_t)b]);
+            if (!use_threshold || loss_b[(size_t)b] > (double)threshold) ++nkeep;
+        }
+        const double cnt = (double)(nkeep == 0 ? B : nkeep);
+        double l = 0.0;
+        for (int b = 0; b < B; ++b) {
+            const bool keep = nkeep == 0 || !use_threshold || loss_b[(size_t)b] > (double)threshold;
+            if (!keep) continue;
+            l += loss_b[(size_t)b];
+            const double dL = -10.0 / (log(10.0) * arg_b[(size_t)b]) / cnt;
+            gt[(size_t)b] = dL * (1.0 - lam) / (double)S;
+            gkw[(size_t)b] = dL * lam / (double)S;
+        }
+        out[0] = (float)(l / cnt);
+        out[1] = (float)(-10.0 * log10(kd + kEps));
+        out[2] = (float)task;
+        out[3] = (float)kd;
+    }
+    for (int b = 0; b < B; ++b) {
+        const Smp& q = smp[(size_t)b];
+        double* m = stats + (int64_t)b * FQSS_KD_STATS_STRIDE_N;
+        for (int i = 0; i < 3 * S; ++i) m[48 + i] = m[i] / Td;
+        for (int i = 0; i < S; ++i) {
+            int jt = 0, jf = 0;     // estimate i sits on signal j with p[j] == i (the inverse map)
+            for (int j = 0; j < S; ++j) {
+                if (perms[(size_t)q.pt][(size_t)j] == i) jt = j;
+                if (perms[(size_t)q.pf][(size_t)j] == i) jf = j;
+            }
+            const PairSdr a = pair_sdr(m[i], m[2 * S + jt], m[3 * S + i], m[5 * S + jt], m[oET + i * S + jt], Td);
+            const PairSdr c = pair_sdr(m[i], m[S + jf], m[3 * S + i], m[4 * S + jf], m[oEF + i * S + jf], Td);
+            const double gti = (mode == 2) ? -10.0 / (log(10.0) * (a.sdr + kEps)) / (double)S / (double)B : gt[(size_t)b];
+            const double gki = gkw[(size_t)b] * ((mode == 1 && B == S) ? smp[(size_t)i].w : q.w);
+            double* cf = m + 57 + 5 * i;
+            cf[0] = gti * a.cx + gki * c.cx;
+            cf[1] = gti * a.cy;
+            cf[2] = (double)jt;
+            cf[3] = gki * c.cy;
+            cf[4] = (double)jf;
+            if (!gest) continue;
+            const float A = (float)cf[0], Bt = (float)cf[1], Bf = (float)cf[3];
+            const float me = (float)m[48 + i], mt = (float)m[48 + 2 * S + jt], mf = (float)m[48 + S + jf];
+            const float* e = est + ((int64_t)b * S + i) * T;
+            const float* tt = tgt + ((int64_t)b * S + jt) * T;
+            const float* ff = fest + ((int64_t)b * S + jf) * T;
+            float* g = gest + ((int64_t)b * S + i) * T;
+            for (int64_t t = 0; t < T; ++t) g[t] = A * (e[t] - me) + Bt * (tt[t] - mt) + Bf * (ff[t] - mf);
         }
     }
     return FQSS_OK;

@@ -98,6 +98,29 @@ int main() {
     std::vector<float> out(4), wv(B), si(B), ge((size_t)B * 2 * TT);
     CHECK(fqss_kd_loss(est.data(), fe.data(), tg.data(), B, TT, 0.1f, nullptr, out.data(), wv.data(), si.data(), ge.data(), nullptr) == 0);
     CHECK(std::isfinite(out[0]) && std::isfinite(ge[5]));
+    // the same loss at 1 and 3 sources: every mode, the moment pass alone, the refused arguments
+    for (int NS : {1, 3}) {
+        const int64_t TN = 257;
+        const int BN = 3;
+        auto en = rnd((size_t)BN * NS * TN), fn = rnd((size_t)BN * NS * TN), tn = rnd((size_t)BN * NS * TN);
+        std::vector<double> stn((size_t)BN * FQSS_KD_STATS_STRIDE_N);
+        std::vector<float> on(4), wn(BN), sn(BN), gn_((size_t)BN * NS * TN);
+        for (int mode = 0; mode < 3; ++mode) {
+            const int Bm = (mode == 1) ? NS : BN;
+            CHECK(fqss_kd_loss_n(en.data(), fn.data(), tn.data(), Bm, NS, TN, 0.1f, mode, mode == 1, -30.0f, stn.data(), on.data(), wn.data(),
+                                 sn.data(), gn_.data(), nullptr) == 0);
+            CHECK(std::isfinite(on[0]) && std::isfinite(gn_[(size_t)Bm * NS * TN - 1]));
+        }
+        CHECK(fqss_kd_loss_n(en.data(), fn.data(), tn.data(), 1, NS, TN, 0.1f, 1, 0, 0.0f, stn.data(), on.data(), wn.data(), sn.data(), nullptr,
+                             nullptr) == 0);
+        CHECK(fqss_kd_moments_n(en.data(), fn.data(), tn.data(), BN, NS, TN, stn.data(), nullptr) == 0);
+        CHECK(std::isfinite(stn[(size_t)(BN - 1) * FQSS_KD_STATS_STRIDE_N + 6 * NS + 3 * NS * NS - 1]));
+        CHECK(fqss_kd_loss_n(en.data(), fn.data(), tn.data(), 2, 3, TN, 0.1f, 1, 0, 0.0f, stn.data(), on.data(), wn.data(), sn.data(), nullptr,
+                             nullptr) == FQSS_EINVAL);
+        CHECK(fqss_kd_loss_n(en.data(), fn.data(), tn.data(), 1, 4, TN, 0.1f, 0, 0, 0.0f, stn.data(), on.data(), wn.data(), sn.data(), nullptr,
+                             nullptr) == FQSS_EINVAL);
+        CHECK(fqss_kd_moments_n(en.data(), fn.data(), tn.data(), BN, 0, TN, stn.data(), nullptr) == FQSS_EINVAL);
+    }
     const int64_t n = 1001;
     auto p = rnd(n), gp = rnd(n);
     std::vector<float> m1(n, 0.f), v1(n, 0.f);

@@ -1184,20 +1184,30 @@ static int qpw_bwd_x_impl(const char* who, const float* gz1, const float* gz2, c
                  "q-GEMM dgrad needs Co % 16 == 0 and 16-B aligned gradient rows");
     FQSS_REQUIRE(Co2 == 0 || (ld_gz2 % 4 == 0 && aligned16(gz2) && ld_gz2 >= ((M + 3) & ~3)), "second gradient: 16-B aligned rows");
     FQSS_REQUIRE(aligned16(gx) && ld_gx % 4 == 0, "output rows must be 16-B aligned");
-    FQSS_REQUIRE(Co <= 1024, "dgrad stages delta_w of at most 1024 output channels in LDS");
-    if (B == 0 || M == 0) return FQSS_OK;
-    QGemmArgs g{};
-    g.A = wiT; g.B = gz1; g.C = gx; g.M = Ci; g.N = M; g.K = Co;
-    g.lda = Co; g.ldb = ld_gz1; g.ldc = ld_gx;
-    g.sAb = 0; g.sBb = (int64_t)Co1 * ld_gz1; g.sCb = (int64_t)Ci * ld_gx;
-    g.M1 = Ci; g.K1 = Co1; g.B2 = gz2; g.ldb2 = ld_gz2; g.sB2b = (int64_t)Co2 * ld_gz2;
-    g.dw = dw; g.ksplit = 1; g.kchunk = Co;
-    if (addend != nullptr) {
+    FQSS_REQUIRE(Co <= 1024 || Co2 == 0, "dgrad of a pair stages delta_w of at most 1024 output channels in LDS");
+    if (addend != nullptr)
         FQSS_REQUIRE(aligned16(addend) && ld_add % 4 == 0 && ld_add >= ((M + 3) & ~3), "addend rows must be 16-B aligned and padded to 4");
-        g.C2 = const_cast<float*>(addend); g.ldc2 = ld_add; g.sC2b = (int64_t)Ci * ld_add;
+    // More than 1024 output channels (the mask conv of three sources x 512 filters): the reduction runs in parts of at most 1024 rows,
+    // each a launch of the same kernel on a column range of W^T and the matching rows of gz.  Part p > 0 adds the sum so far, gx itself:
+    // a thread reads exactly the four outputs it then writes.  Up to 1024 channels this is the one launch it always was.
+    const int parts = (int)cdiv(Co, 1024);
+    const int part = (int)(cdiv(cdiv(Co, parts), 16) * 16);
+    for (int k0 = 0; k0 < Co; k0 += part) {
+        const int kn = Co - k0 < part ? Co - k0 : part;
+        QGemmArgs g{};
+        g.A = wiT + k0; g.B = gz1 + (int64_t)k0 * ld_gz1; g.C = gx; g.M = Ci; g.N = M; g.K = kn;
+        g.lda = Co; g.ldb = ld_gz1; g.ldc = ld_gx;
+        g.sAb = 0; g.sBb = (int64_t)Co1 * ld_gz1; g.sCb = (int64_t)Ci * ld_gx;
+        g.M1 = Ci; g.K1 = parts > 1 ? kn : Co1; g.B2 = gz2; g.ldb2 = ld_gz2; g.sB2b = (int64_t)Co2 * ld_gz2;
+        g.dw = dw + k0; g.ksplit = 1; g.kchunk = kn;
+        if (k0 > 0) {
+            g.C2 = gx; g.ldc2 = ld_gx; g.sC2b = (int64_t)Ci * ld_gx;
+        } else if (addend != nullptr) {
+            g.C2 = const_cast<float*>(addend); g.ldc2 = ld_add; g.sC2b = (int64_t)Ci * ld_add;
+        }
+        g.tiles_n = (int)cdiv(M, QBN); g.tiles_m = (int)cdiv(Ci, QBM); g.batches = B;
+        hipLaunchKernelGGL((k_qgemm<1, 3>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
     }
-    g.tiles_n = (int)cdiv(M, QBN); g.tiles_m = (int)cdiv(Ci, QBM); g.batches = B;
-    hipLaunchKernelGGL((k_qgemm<1, 3>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
     return launch_status(who);
 }
 

@@ -3,6 +3,8 @@
 //              one streaming pass accumulates the 24 second-order moments of (est, teacher, target)
 //              per sample in fp64, a one-block kernel does PIT / weights / loss / gradient
 //              coefficients, one streaming pass writes dL/d est.
+//   kd_loss_n  the same sequence for 1 to 3 sources (k_kd_moments_n<S>, k_kd_final_n<S>, k_kd_grad_n): 6S + 3S^2 moments,
+//              PIT over the S! permutations in itertools order.  Two sources keep the kernels above.
 //   sumsq + adam_clip   global-norm clip and Adam over ONE flat fp32 parameter buffer.
 //
 // Reference replaced: System.common_step (mysystem.py:124-151), PairwiseWSDR (wsdr.py:56-95),
@@ -240,6 +242,279 @@ __global__ __launch_bounds__(256) void k_kd_grad(const float* __restrict__ est, 
 }
 
 // =============================================================================================
+// The same three-kernel sequence for S = 1..3 sources (fqss_kd_loss_n / fqss_kd_moments_n).  The two-source kernels above stay as
+// they are; S = 2 is instantiated here only so that the tests can hold this code against them.
+// stats row of one sample (FQSS_KD_STATS_STRIDE_N doubles; signals e_0.. (student) f_0.. (teacher) t_0.. (targets)):
+//   [0, 3S) sums   [3S, 6S) self products   6S + i*S + j: e_i.t_j   6S + S^2 + i*S + j: e_i.f_j   6S + 2S^2 + i*S + j: f_i.t_j
+//   (6S + 3S^2 moments: 9 / 24 / 45; at S = 2 these are the slots of k_kd_moments).  The moments stay where they are; k_kd_final_n adds
+//   [48, 48 + 3S) the means and 57 + 5i + {0..4} = {A, Bt, jt, Bf, jf} of estimate i for k_kd_grad_n.
+constexpr int kStatStrideN = FQSS_KD_STATS_STRIDE_N;
+constexpr int kMeanSlotN = 48, kCoefSlotN = 57;
+static_assert(6 * 3 + 3 * 3 * 3 <= kMeanSlotN && kMeanSlotN + 3 * 3 <= kCoefSlotN && kCoefSlotN + 5 * 3 <= kStatStrideN, "stats row at S = 3");
+
+template <int S>
+__global__ __launch_bounds__(256) void k_kd_moments_n(const float* __restrict__ est, const float* __restrict__ fest,
+                                                       const float* __restrict__ tgt, int64_t T, double* stats) {
+    constexpr int NM = 6 * S + 3 * S * S;
+    __shared__ double red[NM * 4];
+    const int b = blockIdx.y;
+    const float* e0 = est + (int64_t)b * S * T;
+    const float* f0 = fest + (int64_t)b * S * T;
+    const float* t0 = tgt + (int64_t)b * S * T;
+    double a[NM];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) a[i] = 0.0;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (int64_t)gridDim.x * 256) {
+        double s[3 * S];
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            s[i] = (double)e0[(int64_t)i * T + t];
+            s[S + i] = (double)f0[(int64_t)i * T + t];
+            s[2 * S + i] = (double)t0[(int64_t)i * T + t];
+        }
+#pragma unroll
+        for (int i = 0; i < 3 * S; ++i) {
+            a[i] += s[i];
+            a[3 * S + i] += s[i] * s[i];
+        }
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int j = 0; j < S; ++j) {
+                a[6 * S + i * S + j] += s[i] * s[2 * S + j];
+                a[6 * S + S * S + i * S + j] += s[i] * s[S + j];
+                a[6 * S + 2 * S * S + i * S + j] += s[S + i] * s[2 * S + j];
+            }
+    }
+    block_sum<double, NM>(a, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NM; ++i) atomicAdd(&stats[(int64_t)b * kStatStrideN + i], a[i]);
+    }
+}
+
+// permutation q of itertools.permutations(range(S)), element i -- as arithmetic, so that no table is indexed at run time.
+// S = 3: the first element is q / 2, the other two follow ascending (q even) or descending (q odd).
+template <int S>
+__device__ __forceinline__ int perm_at(int q, int i) {
+    if (S == 1) return 0;
+    if (S == 2) return q ? 1 - i : i;
+    const int first = q >> 1, r0 = first == 0 ? 1 : 0, r1 = first == 2 ? 1 : 2;
+    return i == 0 ? first : ((i == 1) != ((q & 1) != 0) ? r0 : r1);
+}
+// the position j with perm(q)[j] == i: the signal that estimate i is paired with under permutation q (the inverse map)
+template <int S>
+__device__ __forceinline__ int perm_inv(int q, int i) {
+    int j = 0;
+#pragma unroll
+    for (int k = 1; k < S; ++k)
+        if (perm_at<S>(q, k) == i) j = k;
+    return j;
+}
+
+// one block; thread b < B handles sample b.  mode 0 / 1 / 2 = per_sample 0 / 1 / 2 of k_kd_final.  Every PIT candidate pairs the
+// student's source p[i] with signal i of the other side: asteroid's pw_mtx form mean_i pw[est = p[i]][tgt = i] and the speechbrain
+// wrapper's mean_i M[other = i][student = p[i]] are that same pairing, and the gradient of estimate i goes to signal p^-1[i].
+// Only the S*S ratios are kept per thread; the derivative coefficients of the S selected pairs are recomputed from the moments.
+template <int S>
+__global__ __launch_bounds__(1024) void k_kd_final_n(int B, int64_t T, float kd_lambda, double* stats, float* out, float* w_out,
+                                                      float* sisdr_out, int mode, int use_threshold, float threshold) {
+    constexpr int NP = S == 1 ? 1 : (S == 2 ? 2 : 6);
+    constexpr int oET = 6 * S, oEF = 6 * S + S * S, oFT = 6 * S + 2 * S * S;
+    __shared__ double red[2 * 16];
+    __shared__ double sh_w[S];
+    __shared__ int sh_keep;
+    __shared__ double sh_task, sh_kd;
+    const int b = threadIdx.x;
+    const double Td = (double)T, invS = 1.0 / (double)S;
+    double* m = stats + (int64_t)(b < B ? b : 0) * kStatStrideN;
+    double task_b = 0.0, kd_b = 0.0, wb = 0.0, pit_db = 0.0;
+    int pt = 0, pf = 0;     // selected permutation for task / kd
+    double rf[S][S];        // linear ratio of e_i against f_j
+    if (b < B) {
+        // four separate reductions over the permutations (at S = 3 they can select different ones); one table at a time, so that
+        // no more than two S x S tables are live
+        double sdrs = 0.0, sdrqs = 0.0, tbest = 0.0;
+        int pe = 0;
+        {
+            double nl_ft[S][S];     // teacher vs target, dB
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int j = 0; j < S; ++j)
+                    nl_ft[i][j] = -10.0 * log10(pair_sdr(m[S + i], m[2 * S + j], m[4 * S + i], m[5 * S + j], m[oFT + i * S + j], Td).sdr + kEps);
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                double lf = 0.0;
+#pragma unroll
+                for (int i = 0; i < S; ++i) lf += nl_ft[perm_at<S>(q, i)][i];
+                lf *= invS;
+                if (q == 0 || lf < sdrs) sdrs = lf;
+            }
+        }
+        {
+            double rt[S][S];        // student vs target, linear ratio
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int j = 0; j < S; ++j) rt[i][j] = pair_sdr(m[i], m[2 * S + j], m[3 * S + i], m[5 * S + j], m[oET + i * S + j], Td).sdr;
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                double le = 0.0, tq = 0.0;
+#pragma unroll
+                for (int i = 0; i < S; ++i) {
+                    le += -10.0 * log10(rt[perm_at<S>(q, i)][i] + kEps);
+                    tq += rt[perm_at<S>(q, i)][i];
+                }
+                le *= invS;
+                tq = -tq * invS;    // task / kd use the NEGATED linear ratio through the same PIT
+                if (q == 0 || le < sdrqs) {
+                    sdrqs = le;
+                    pe = q;
+                }
+                if (q == 0 || tq < tbest) {
+                    tbest = tq;
+                    pt = q;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int j = 0; j < S; ++j) rf[i][j] = pair_sdr(m[i], m[S + j], m[3 * S + i], m[4 * S + j], m[oEF + i * S + j], Td).sdr;
+        wb = pow(10.0, (sdrs - sdrqs) / 10.0);  // w = SDR_student / SDR_teacher (mysystem.py:141)
+        task_b = -tbest;
+        if (mode == 2) {    // the PIT runs over the mean of the dB values here, not over the mean ratio
+            pt = pe;
+            pit_db = sdrqs;
+        }
+        w_out[b] = (float)wb;
+        sisdr_out[b] = (float)(-sdrqs);
+        if (mode == 1 && b < S) sh_w[b] = wb;
+    }
+    if (mode == 1) {
+        if (threadIdx.x == 0) sh_keep = 0;
+        __syncthreads();
+    }
+    double wsrc[S];         // KD weight of student source j in this sample
+#pragma unroll
+    for (int j = 0; j < S; ++j) wsrc[j] = (mode == 1 && B == S) ? sh_w[j] : wb;
+    if (b < B) {
+        double kbest = 0.0;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            double kq = 0.0;
+#pragma unroll
+            for (int i = 0; i < S; ++i) kq += wsrc[perm_at<S>(q, i)] * rf[perm_at<S>(q, i)][i];
+            kq = -kq * invS;
+            if (q == 0 || kq < kbest) {
+                kbest = kq;
+                pf = q;
+            }
+        }
+        kd_b = -kbest;
+    }
+    double v[2] = {task_b, kd_b};
+    block_sum<double, 2>(v, red);
+    if (threadIdx.x == 0) {
+        sh_task = v[0] / (double)B;
+        sh_kd = v[1] / (double)B;
+    }
+    __syncthreads();
+    const double task = sh_task, kd = sh_kd;
+    const double lam = (double)kd_lambda;
+    // d loss / d (task ratio of a pair), d loss / d (kd ratio of student source j's pair); spelled so that at S = 2 every product
+    // rounds as in k_kd_final (invS = 0.5 is exact)
+    double gt = 0.0, gk[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) gk[j] = 0.0;
+    if (mode == 2) {
+        double lv[2] = {(b < B) ? pit_db : 0.0, 0.0};
+        block_sum<double, 2>(lv, red);
+        if (threadIdx.x == 0) {
+            out[0] = (float)(lv[0] / (double)B);
+            out[1] = 0.0f;
+            out[2] = (float)task;
+            out[3] = 0.0f;
+        }
+    } else if (mode == 0) {
+        const double arg = (1.0 - lam) * task + lam * kd + kEps;
+        if (threadIdx.x == 0) {
+            out[0] = (float)(-10.0 * log10(arg));
+            out[1] = (float)(-10.0 * log10(kd + kEps));
+            out[2] = (float)task;
+            out[3] = (float)kd;
+        }
+        // dL/d arg = -10/(ln10 * arg); d arg/d sdr_task(b, pair) = (1-lam)/(S B); d arg/d sdr_kd = lam*w_b/(S B)
+        const double dL = -10.0 / (log(10.0) * arg);
+        gt = dL * (1.0 - lam) * invS / (double)B;
+#pragma unroll
+        for (int j = 0; j < S; ++j) gk[j] = dL * lam * wb * invS / (double)B;
+    } else {
+        const double arg_b = (1.0 - lam) * task_b + lam * kd_b + kEps;
+        const double loss_b = (b < B) ? -10.0 * log10(arg_b) : 0.0;
+        const bool above = (b < B) && (!use_threshold || loss_b > (double)threshold);
+        if (above) atomicAdd(&sh_keep, 1);
+        __syncthreads();
+        const int nkeep = sh_keep;
+        const bool keep = (b < B) && (nkeep == 0 || above);       // nothing above the threshold: the loss stays as it is
+        const double cnt = (double)(nkeep == 0 ? B : nkeep);
+        double lv[2] = {keep ? loss_b : 0.0, 0.0};
+        block_sum<double, 2>(lv, red);
+        if (threadIdx.x == 0) {
+            out[0] = (float)(lv[0] / cnt);
+            out[1] = (float)(-10.0 * log10(kd + kEps));
+            out[2] = (float)task;
+            out[3] = (float)kd;
+        }
+        if (keep) {
+            const double dL = -10.0 / (log(10.0) * arg_b) / cnt;
+            gt = dL * (1.0 - lam) * invS;
+#pragma unroll
+            for (int j = 0; j < S; ++j) gk[j] = dL * lam * wsrc[j] * invS;
+        }
+    }
+    if (b < B) {
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            // estimate i sits on signal j with p[j] == i: the inverse map, not p[i] (they differ for the 3-cycles)
+            const int jt = perm_inv<S>(pt, i), jf = perm_inv<S>(pf, i);
+            const PairSdr a = pair_sdr(m[i], m[2 * S + jt], m[3 * S + i], m[5 * S + jt], m[oET + i * S + jt], Td);
+            const PairSdr c = pair_sdr(m[i], m[S + jf], m[3 * S + i], m[4 * S + jf], m[oEF + i * S + jf], Td);
+            // mode 2: the log is taken per pair, d loss / d (ratio of the pair of estimate i)
+            const double gti = (mode == 2) ? -10.0 / (log(10.0) * (a.sdr + kEps)) * invS / (double)B : gt;
+            const double gki = gk[i];
+            double* cf = m + kCoefSlotN + 5 * i;
+            cf[0] = gti * a.cx + gki * c.cx;    // coefficient of e~_i
+            cf[1] = gti * a.cy;                 // coefficient of t~_jt
+            cf[2] = (double)jt;
+            cf[3] = gki * c.cy;                 // coefficient of f~_jf
+            cf[4] = (double)jf;
+        }
+#pragma unroll
+        for (int i = 0; i < 3 * S; ++i) m[kMeanSlotN + i] = m[i] / Td;
+    }
+}
+
+// gest[b][i][t] = A*(e_i - mean) + Bt*(t_jt - mean) + Bf*(f_jf - mean); grid (column blocks, S * B)
+__global__ __launch_bounds__(256) void k_kd_grad_n(const float* __restrict__ est, const float* __restrict__ fest,
+                                                    const float* __restrict__ tgt, int S, int64_t T, const double* stats,
+                                                    float* __restrict__ gest) {
+    const int b = blockIdx.y / S, i = blockIdx.y - b * S;
+    const double* m = stats + (int64_t)b * kStatStrideN;
+    const double* cf = m + kCoefSlotN + 5 * i;
+    const int jt = (int)cf[2], jf = (int)cf[4];
+    const float A = (float)cf[0], Bt = (float)cf[1], Bf = (float)cf[3];
+    const float me = (float)m[kMeanSlotN + i], mt = (float)m[kMeanSlotN + 2 * S + jt], mf = (float)m[kMeanSlotN + S + jf];
+    const float* e = est + ((int64_t)b * S + i) * T;
+    const float* tt = tgt + ((int64_t)b * S + jt) * T;
+    const float* ff = fest + ((int64_t)b * S + jf) * T;
+    float* g = gest + ((int64_t)b * S + i) * T;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (int64_t)gridDim.x * 256)
+        g[t] = A * (e[t] - me) + Bt * (tt[t] - mt) + Bf * (ff[t] - mf);
+}
+
+// =============================================================================================
 __global__ __launch_bounds__(256) void k_sumsq(const float* __restrict__ g, int64_t n, double* acc) {
     __shared__ double red[4];
     double s = 0.0;
@@ -356,6 +631,55 @@ extern "C" int fqss_kd_moments(const float* est, const float* fest, const float*
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(k_kd_moments, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, s, est, fest, tgt, T, stats);
     return launch_status("fqss_kd_moments");
+}
+
+// ---- S = 1..3 sources (the kernels templated on S above)
+template <int S>
+static void kd_launch_n(const float* est, const float* fest, const float* tgt, int B, int64_t T, float kd_lambda, int mode, int use_threshold,
+                        float threshold, double* stats, float* out, float* w_out, float* sisdr_out, bool final_pass, hipStream_t s) {
+    int64_t nb = cdiv(T, 256 * 8);
+    if (nb > 64) nb = 64;
+    if (nb < 1) nb = 1;
+    hipLaunchKernelGGL(k_kd_moments_n<S>, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, s, est, fest, tgt, T, stats);
+    if (final_pass)
+        hipLaunchKernelGGL(k_kd_final_n<S>, dim3(1), dim3(1024), 0, s, B, T, kd_lambda, stats, out, w_out, sisdr_out, mode, use_threshold,
+                           threshold);
+}
+
+extern "C" int fqss_kd_loss_n(const float* est, const float* fest, const float* tgt, int B, int S, int64_t T, float kd_lambda, int mode,
+                              int use_threshold, float threshold, double* stats, float* out, float* w_out, float* sisdr_out, float* gest,
+                              fqss_stream_t stream) {
+    FQSS_REQUIRE(est && fest && tgt && stats && out && w_out && sisdr_out, "null tensor");
+    FQSS_REQUIRE(S >= 1 && S <= 3, "n_src must be in 1..3");
+    FQSS_REQUIRE(B > 0 && B <= 1024 && T > 0, "B must be in 1..1024");
+    FQSS_REQUIRE(mode >= 0 && mode <= 2, "mode must be 0 (asteroid), 1 (per sample) or 2 (teacher-free PIT SI-SDR)");
+    FQSS_REQUIRE(mode != 1 || B == 1 || B == S,
+                 "the per-sample KD weights broadcast [1, n_src, n_src] * [1, B]: B must be 1 or n_src (the reference raises otherwise)");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(stats, 0, sizeof(double) * kStatStrideN * B, s) != hipSuccess) return launch_status("fqss_kd_loss_n(memset)");
+    const int ut = use_threshold ? 1 : 0;
+    if (S == 1) kd_launch_n<1>(est, fest, tgt, B, T, kd_lambda, mode, ut, threshold, stats, out, w_out, sisdr_out, true, s);
+    else if (S == 2) kd_launch_n<2>(est, fest, tgt, B, T, kd_lambda, mode, ut, threshold, stats, out, w_out, sisdr_out, true, s);
+    else kd_launch_n<3>(est, fest, tgt, B, T, kd_lambda, mode, ut, threshold, stats, out, w_out, sisdr_out, true, s);
+    if (gest) {
+        int64_t ng = cdiv(T, 256 * 4);
+        if (ng > 256) ng = 256;
+        hipLaunchKernelGGL(k_kd_grad_n, dim3((unsigned)ng, (unsigned)(S * B)), dim3(256), 0, s, est, fest, tgt, S, T, stats, gest);
+    }
+    return launch_status("fqss_kd_loss_n");
+}
+
+extern "C" int fqss_kd_moments_n(const float* est, const float* fest, const float* tgt, int B, int S, int64_t T, double* stats,
+                                 fqss_stream_t stream) {
+    FQSS_REQUIRE(est && fest && tgt && stats, "null tensor");
+    FQSS_REQUIRE(S >= 1 && S <= 3, "n_src must be in 1..3");
+    FQSS_REQUIRE(B > 0 && B <= 1024 && T > 0, "B must be in 1..1024");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(stats, 0, sizeof(double) * kStatStrideN * B, s) != hipSuccess) return launch_status("fqss_kd_moments_n(memset)");
+    if (S == 1) kd_launch_n<1>(est, fest, tgt, B, T, 0.0f, 0, 0, 0.0f, stats, nullptr, nullptr, nullptr, false, s);
+    else if (S == 2) kd_launch_n<2>(est, fest, tgt, B, T, 0.0f, 0, 0, 0.0f, stats, nullptr, nullptr, nullptr, false, s);
+    else kd_launch_n<3>(est, fest, tgt, B, T, 0.0f, 0, 0, 0.0f, stats, nullptr, nullptr, nullptr, false, s);
+    return launch_status("fqss_kd_moments_n");
 }
 
 // ---- FQSS_DETERMINISTIC=1 (fqss_dev.h: grad_add): the control blocks of every TU, the finish pass

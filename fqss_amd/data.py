@@ -5,11 +5,12 @@ import torch
 import torch.nn.functional as F
 
 
-def synth_batch(B, T, seed=0, device="cpu"):
+def synth_batch(B, T, seed=0, device="cpu", n_src=2):
+    """(mixture [B, 1, T], sources [B, n_src, T]); n_src = 2 draws what it always drew"""
     g = torch.Generator().manual_seed(seed)
-    s = 0.05 * torch.randn(B, 2, T + 4, generator=g)
+    s = 0.05 * torch.randn(B, n_src, T + 4, generator=g)
     fir = torch.tensor([0.1, 0.25, 0.3, 0.25, 0.1]).view(1, 1, 5)
-    s = F.conv1d(s.view(B * 2, 1, T + 4), fir).view(B, 2, T)
+    s = F.conv1d(s.view(B * n_src, 1, T + 4), fir).view(B, n_src, T)
     return s.sum(1, keepdim=True).to(device), s.to(device)
 
 

@@ -1181,19 +1181,32 @@ def frames_wgrad1_q(ac, qmin, qmax, sig, gw, stride):
 
 
 # ------------------------------------------------------------------ K15 / K16
+KD_STATS_STRIDE_N = _lib.CONSTANTS["FQSS_KD_STATS_STRIDE_N"]     # stats row of the n-source entry points (include/fqss.h)
+
+
+def _n_src(S):
+    """two sources run the two-source entry points; 1 and 3 the n-source ones (fqss_kd_loss_n / fqss_kd_moments_n)"""
+    if S not in (1, 2, 3):
+        raise NotImplementedError(f"the PIT / KD loss kernels are built for n_src = 1 to 3, got {S}")
+    return S
+
+
 def kd_loss(est, fest, tgt, kd_lambda, want_grad=True, per_sample=False, threshold=None):
-    """per_sample: the speechbrain env's objective (log per sample, mean over the samples whose loss exceeds `threshold`), B <= 2"""
+    """per_sample: the speechbrain env's objective (log per sample, mean over the samples whose loss exceeds `threshold`), B = 1 or
+    n_src"""
     _need_gpu(est, fest, tgt)
     est, fest, tgt = est.contiguous(), fest.contiguous(), tgt.contiguous()
     B, S, T = est.shape
-    assert S == 2, "the PIT kernel is built for n_src = 2"
     dev = est.device
-    stats = torch.empty(B, 32, device=dev, dtype=torch.float64)
+    stats = torch.empty(B, 32 if _n_src(S) == 2 else KD_STATS_STRIDE_N, device=dev, dtype=torch.float64)
     out = torch.empty(4, device=dev, dtype=torch.float32)
     w = torch.empty(B, device=dev, dtype=torch.float32)
     sisdr = torch.empty(B, device=dev, dtype=torch.float32)
     gest = torch.empty_like(est) if want_grad else None
-    if per_sample:
+    if S != 2:
+        _lib.call("fqss_kd_loss_n", _p(est), _p(fest), _p(tgt), B, S, T, float(kd_lambda), int(bool(per_sample)),
+                  int(per_sample and threshold is not None), float(threshold or 0.0), _p(stats), _p(out), _p(w), _p(sisdr), _p(gest), _stream())
+    elif per_sample:
         _lib.call("fqss_kd_loss_per_sample", _p(est), _p(fest), _p(tgt), B, T, float(kd_lambda), int(threshold is not None),
                   float(threshold or 0.0), _p(stats), _p(out), _p(w), _p(sisdr), _p(gest), _stream())
     else:
@@ -1207,23 +1220,30 @@ def pit_sisdr_loss(est, tgt, want_grad=True):
     _need_gpu(est, tgt)
     est, tgt = est.contiguous(), tgt.contiguous()
     B, S, T = est.shape
-    assert S == 2, "the PIT kernel is built for n_src = 2"
     dev = est.device
-    stats = torch.empty(B, 32, device=dev, dtype=torch.float64)
+    stats = torch.empty(B, 32 if _n_src(S) == 2 else KD_STATS_STRIDE_N, device=dev, dtype=torch.float64)
     out, w, sisdr = torch.empty(4, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
     gest = torch.empty_like(est) if want_grad else None
-    _lib.call("fqss_pit_sisdr_loss", _p(est), _p(tgt), B, T, _p(stats), _p(out), _p(w), _p(sisdr), _p(gest), _stream())
+    if S != 2:
+        _lib.call("fqss_kd_loss_n", _p(est), _p(tgt), _p(tgt), B, S, T, 0.0, 2, 0, 0.0, _p(stats), _p(out), _p(w), _p(sisdr), _p(gest), _stream())
+    else:
+        _lib.call("fqss_pit_sisdr_loss", _p(est), _p(tgt), B, T, _p(stats), _p(out), _p(w), _p(sisdr), _p(gest), _stream())
     return out, sisdr, gest
 
 
 def kd_moments(est, fest, tgt):
-    """the 24 fp64 second-order moments per sample that the streaming pass of fqss_kd_loss accumulates ([B, 32], slots as in
-    csrc/train_ops.hip: sums 0..5 of e0 e1 f0 f1 t0 t1, self products 6..11, e_i.t_j 12..15, e_i.f_j 16..19, f_i.t_j 20..23)"""
+    """the fp64 second-order moments per sample that the streaming pass of the loss accumulates, signals ordered e_0.. f_0.. t_0..:
+    sums [0, 3S), self products [3S, 6S), e_i.t_j at 6S + i*S + j, e_i.f_j at 6S + S*S + i*S + j, f_i.t_j at 6S + 2*S*S + i*S + j.
+    Two sources: [B, 32] from fqss_kd_moments (24 moments, the slots of csrc/train_ops.hip); 1 and 3 sources: [B,
+    KD_STATS_STRIDE_N] from fqss_kd_moments_n (9 / 45 moments)."""
     _need_gpu(est, fest, tgt)
     est, fest, tgt = est.contiguous(), fest.contiguous(), tgt.contiguous()
     B, S, T = est.shape
-    assert S == 2, "the moment kernel is built for n_src = 2"
     dev = est.device
+    if _n_src(S) != 2:
+        stats = torch.empty(B, KD_STATS_STRIDE_N, device=dev, dtype=torch.float64)
+        _lib.call("fqss_kd_moments_n", _p(est), _p(fest), _p(tgt), B, S, T, _p(stats), _stream())
+        return stats
     stats = torch.empty(B, 32, device=dev, dtype=torch.float64)
     _lib.call("fqss_kd_moments", _p(est), _p(fest), _p(tgt), B, T, _p(stats), _stream())
     return stats

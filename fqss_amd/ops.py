@@ -1180,7 +1180,7 @@ def fork2(x):
 
 
 class KDLoss(Function):
-    """loss = -10 log10((1-l)*task + l*kd + eps) with SDR-weighted KD and 2-speaker PIT
+    """loss = -10 log10((1-l)*task + l*kd + eps) with SDR-weighted KD and PIT over 1 to 3 speakers
     (mysystem.py:124-151); forward and backward come out of ONE kernel sequence."""
 
     @staticmethod

@@ -249,6 +249,8 @@ class BF_module(DPT_base):
 class DPTNetQ(nn.Module):
     def __init__(self, n_spks=2, kernel_size=2, enc_dim=256, feature_dim=64, hidden_dim=128, layer=6, segment_size=250):
         super().__init__()
+        if n_spks != 2:     # the loss kernels take 1 to 3 sources; this model's dual-path kernels are proven at two only
+            raise NotImplementedError(f"DPTNetQ is served for n_spks = 2 (got {n_spks}); ConvTasNetQ takes 1 to 3 sources")
         self.set_splitter_combiner(1, 1)
         self.window = kernel_size
         self.enc_dim, self.feature_dim, self.hidden_dim, self.segment_size = enc_dim, feature_dim, hidden_dim, segment_size

@@ -199,6 +199,8 @@ class MaskGenerator(nn.Module):
 class SepformerQ(nn.Module):
     def __init__(self, n_spks=1, kernel_size=16, stride=8, n_filters=256, n_repeats=2, n_heads=8, chunk_size=250, device="cpu"):
         super().__init__()
+        if n_spks != 2:     # the loss kernels take 1 to 3 sources; this model's dual-path kernels are proven at two only
+            raise NotImplementedError(f"SepformerQ is served for n_spks = 2 (got {n_spks}); ConvTasNetQ takes 1 to 3 sources")
         self.n_srcs = n_spks
         self.enc_num_feats = n_filters
         self.set_splitter_combiner(1, 1)

@@ -45,8 +45,8 @@ class _Data:
     """the two loaders of prepare_datasets (:53-67): shuffled / sequential batches of training_cfg.batch_size, drop_last; under DDP
     every rank reads its DistributedSampler share (Lightning's replacement sampler).  `train(epoch)` yields (x, tgt, x_next)."""
 
-    def __init__(self, dataset_cfg, training_cfg, comm, device):
-        self.cfg, self.tc, self.comm, self.device = dataset_cfg, training_cfg, comm, device
+    def __init__(self, dataset_cfg, training_cfg, comm, device, n_src=2):
+        self.cfg, self.tc, self.comm, self.device, self.n_src = dataset_cfg, training_cfg, comm, device, int(n_src)
         self.synthetic = dataset_cfg.get("name") == "synthetic"
         self.loader_wait_s = 0.0
         if self.synthetic:
@@ -62,7 +62,7 @@ class _Data:
         n = int(ds.get("steps_per_epoch" if split == "train" else "val_steps", 20 if split == "train" else 4))
         for i in range(n):
             yield synth_batch(self.tc["batch_size"], T, seed=(0 if split == "train" else 10_000) + i * comm.world + comm.rank,
-                              device=self.device)
+                              device=self.device, n_src=self.n_src)
 
     def _files(self, split, epoch):
         ds = self.train_set if split == "train" else self.val_set
@@ -142,7 +142,7 @@ def _train(yml_path, device, resume=None):
     if str(opt.get("optimizer", "adam")).lower() != "adam" or float(opt.get("weight_decay", 0) or 0) != 0:
         raise NotImplementedError(f"asteroid env: optim {opt!r}: only adam with weight_decay 0 has a fused kernel")
     betas = tuple(opt.get("betas", (0.9, 0.999)))
-    data = _Data(dataset_cfg, training_cfg, comm, dev)
+    data = _Data(dataset_cfg, training_cfg, comm, dev, n_src=model_cfg.get("n_src", 2))
     # the loader's next mixture is on the device a step early: the frozen teacher runs on it beside the current step (KDTrainStep
     # teacher_ahead: the path bench.py measures; HIP backend only)
     ahead = (not cpu) and training_cfg.get("kd_lambda", 0) > 0 and bool(training_cfg.get("teacher_ahead", True))

@@ -1,8 +1,8 @@
 """SDR losses of the asteroid env on MI355X (reference: train_env/asteroid_librimix/wsdr.py:46-95).
 
-`PairwiseWSDR("sisdr")` + PIT over 2 speakers + the SDR-weighted KD objective are ONE fused HIP
-kernel sequence (csrc/train_ops.hip, fqss_kd_loss); this module keeps the reference's names for the
-pieces a training script touches."""
+`PairwiseWSDR("sisdr")` + PIT over 1 to 3 speakers + the SDR-weighted KD objective are ONE fused HIP
+kernel sequence (csrc/train_ops.hip: fqss_kd_loss at two sources, fqss_kd_loss_n at one and three);
+this module keeps the reference's names for the pieces a training script touches."""
 import torch
 
 from ... import kernels as K
@@ -21,18 +21,18 @@ class KDObjective:
 
 
 def si_sdr(est, targets):
-    """mean best-permutation SI-SDR in dB of a [B,2,T] estimate (no gradient)"""
+    """mean best-permutation SI-SDR in dB of a [B,n_src,T] estimate (no gradient)"""
     out, w, sisdr, _ = K.kd_loss(est.detach(), targets, targets, 0.0, want_grad=False)
     return sisdr
 
 
 def _pair_moments(est, targets, zero_mean):
-    """per sample: energy of estimate i, of target j, their dot product -- [B,2,1], [B,1,2], [B,2,2] fp64, from ONE streaming pass
-    of the moment kernel over the waveforms (everything after it is arithmetic on 24 numbers per sample)"""
-    T = est.shape[-1]
+    """per sample: energy of estimate i, of target j, their dot product -- [B,S,1], [B,1,S], [B,S,S] fp64, from ONE streaming pass
+    of the moment kernel over the waveforms (everything after it is arithmetic on 6S + 3S^2 numbers per sample; slots: K.kd_moments)"""
+    S, T = est.shape[1], est.shape[-1]
     m = K.kd_moments(est.detach(), targets.detach(), targets.detach())
-    se, st = m[:, 0:2], m[:, 4:6]
-    ee, tt, et = m[:, 6:8], m[:, 10:12], m[:, 12:16].reshape(-1, 2, 2)
+    se, st = m[:, 0:S], m[:, 2 * S:3 * S]
+    ee, tt, et = m[:, 3 * S:4 * S], m[:, 5 * S:6 * S], m[:, 6 * S:6 * S + S * S].reshape(-1, S, S)
     if zero_mean:
         ee = ee - se * se / T
         tt = tt - st * st / T
@@ -43,7 +43,7 @@ def _pair_moments(est, targets, zero_mean):
 class PairwiseWSDR:
     """PairwiseWSDR(sdr_type)(est_targets, targets, weights=None) -> [batch, n_src, n_src] (reference wsdr.py:46-95; entry [b, i, j]
     pairs estimate i with target j).  Evaluation form (no autograd: the training objective and its gradient are the fused
-    fqss_kd_loss); n_src = 2, the moment kernel's size."""
+    fqss_kd_loss / fqss_kd_loss_n); n_src = 1 to 3, the moment kernels' sizes."""
 
     def __init__(self, sdr_type, zero_mean=True, take_log=True, EPS=1e-8):
         assert sdr_type in ["snr", "sisdr", "sdsdr"]

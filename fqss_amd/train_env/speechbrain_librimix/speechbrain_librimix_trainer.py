@@ -7,8 +7,9 @@ batch_size, lr, clip_grad_norm, loss_upper_lim, training_signal_len, seed, kd_la
 `!ref <key>` references are resolved, `!new:` / `!name:` object tags (loggers, augmenters, speechbrain callables) are read as
 plain mappings and ignored.  Step semantics kept:
   * KD objective per sample, then the mean over the batch (:99-115): `KDTrainStep(loss="sisdr_pit_per_sample")`, the per-sample form of
-    the fused KD-loss kernel (fqss_kd_loss_per_sample).  Per-GPU batch 1 (shipped) or 2: the reference broadcasts the KD weights as
-    `[1, n_src, n_src] * [1, B]`, which only exists for B in (1, n_src) -- larger batches are refused here as they fail there;
+    the fused KD-loss kernel (fqss_kd_loss_per_sample; fqss_kd_loss_n at one or three sources).  Per-GPU batch 1 (shipped) or n_src:
+    the reference broadcasts the KD weights as `[1, n_src, n_src] * [1, B]`, which only exists for B in (1, n_src) -- other batches
+    are refused here as they fail there;
   * `threshold_byloss`: `loss[loss > th]` -- samples at or below the threshold leave the batch mean; an empty selection leaves the
     loss as it is (:141-149), which at batch 1 makes the option a no-op; the kernel applies it on the device;
   * a step whose loss is not below `loss_upper_lim` (NaN / inf) is skipped and counted (:157-176); under data parallelism the
@@ -17,7 +18,8 @@ plain mappings and ignored.  Step semantics kept:
     from speechbrain 0.5.14's published behaviour: third-party, parity unpinned).
 Data: `dataset_cfg.name: librimix` is the reference's configuration (configs/sepformer_2spks_8k.yaml:27-39): `prepare_librimix` writes
 the CSVs into `save_folder`, `SbLibriMix` (prepare_data.py) serves whole utterances with the train-time speed perturbation / re-mix /
-random cut of `compute_forward` on the device, a batch ahead of the step (fqss_amd/loader.py); `synthetic`: seeded 2-speaker mixtures.
+random cut of `compute_forward` on the device, a batch ahead of the step (fqss_amd/loader.py); `synthetic`: seeded mixtures of
+`model_cfg.n_src` speakers.
 Every epoch ends with `<work_dir>/checkpoint.pth`, the full training state (what speechbrain's Checkpointer keeps); the top-level
 key `resume: <path> | auto` continues from one (fqss_amd/checkpoint.py)."""
 import json
@@ -147,7 +149,7 @@ class _Data:
             n = int(ds.get("steps_per_epoch" if split == "train" else "val_steps", 20 if split == "train" else 4))
             for i in range(n):
                 yield synth_batch(int(hp["batch_size"]), T, seed=(0 if split == "train" else 10_000) + i * comm.world + comm.rank,
-                                  device=self.device)
+                                  device=self.device, n_src=int(hp["model_cfg"].get("n_src", 2)))
             return
         opts = hp.get("dataloader_opts") or {}
         bs = int(opts.get("batch_size", hp["batch_size"]))
@@ -168,8 +170,9 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda", resum
     hp = load_hparams(yml_path)
     if resume is not None:
         hp["resume"] = resume
-    if int(hp.get("batch_size", 1)) not in (1, 2):
-        raise ValueError("speechbrain env: per-GPU batch_size must be 1 or n_src = 2 (the reference's KD weights broadcast "
+    n_src = int(hp.get("model_cfg", {}).get("n_src", 2))
+    if int(hp.get("batch_size", 1)) not in (1, n_src):
+        raise ValueError(f"speechbrain env: per-GPU batch_size must be 1 or n_src = {n_src} (the reference's KD weights broadcast "
                          "[1, n_src, n_src] * [1, B] and raise for any other batch)")
     set_seed(hp.get("seed", 0))
     comm = Comm.from_env("cuda")

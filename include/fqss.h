@@ -252,7 +252,9 @@ int fqss_wq_codes_bits(const float* w, int8_t* idx, int8_t* idxT, float* dw, flo
 int fqss_qpw_fwd(const uint8_t* xc, const int8_t* wi, const float* dw, const float* rw,
                  const float* bias, const float* qmin_x, const float* qmax_x, float* z, int B, int Ci,
                  int Co, int M, int64_t ld_xc, int64_t ld_z, fqss_stream_t stream);
-/* gx[b] = W_q^T gz[b] */
+/* gx[b] = W_q^T gz[b].  One launch up to Co = 1024 (the kernel stages delta_w of its reduction rows in LDS); above that -- the mask conv
+ * of three sources x 512 filters -- the reduction runs in ceil(Co / 1024) equal parts, each adding to the sum of the parts before it
+ * (fqss_qpw_bwd_x_add likewise; the paired form fqss_qpw_bwd_x2 stays at Co1 + Co2 <= 1024) */
 int fqss_qpw_bwd_x(const float* gz, const int8_t* wiT, const float* dw, float* gx, int B, int Ci,
                    int Co, int M, int64_t ld_gz, int64_t ld_gx, fqss_stream_t stream);
 /* gw[Co][Ci] += sum_b gz[b] x[b]^T   (gradient w.r.t. the fake-quantized weight) */
@@ -633,6 +635,25 @@ int fqss_pit_sisdr_loss(const float* est, const float* tgt, int B, int64_t T, do
  * (wsdr.py:10-95) are computed from */
 int fqss_kd_moments(const float* est, const float* fest, const float* tgt, int B, int64_t T, double* stats,
                     fqss_stream_t stream);
+
+/* K15 for n_src = S in 1..3 (Libri3Mix sep_*, enh_single): the same three-launch sequence with the PIT over the S! permutations in
+ * itertools.permutations order, the first one winning ties.  est/fest/tgt: [B][S][T] dense; B in 1..1024.
+ * mode 0: fqss_kd_loss's objective; mode 1: fqss_kd_loss_per_sample's (use_threshold / threshold as there; B must be 1 or S, else
+ * FQSS_EINVAL: at B = S student source j carries w[j] in every sample); mode 2: fqss_pit_sisdr_loss's (fest is read like any
+ * operand: pass tgt; kd_lambda is ignored).  out / w_out / sisdr_out / gest as in those entry points.
+ * stats: fp64 scratch [B][FQSS_KD_STATS_STRIDE_N], zeroed by the callee.  Row of sample b, signals ordered e_0.. f_0.. t_0..:
+ *   [0, 3S) sums, [3S, 6S) self products, 6S + i*S + j: e_i.t_j, 6S + S*S + i*S + j: e_i.f_j, 6S + 2*S*S + i*S + j: f_i.t_j
+ *   (6S + 3S*S moments, at most 45; at S = 2 the slots of fqss_kd_moments), left in place;
+ *   [48, 48 + 3S) the means of the 3S signals; 57 + 5*i + {0, 1, 2, 3, 4} = {A, Bt, jt, Bf, jf} of estimate i, from which
+ *   gest[b][i] = A (e_i - mean) + Bt (t_jt - mean) + Bf (f_jf - mean).
+ * S = 2 serves as the cross-check against the two-source entry points above, which stay what the product calls at S = 2. */
+#define FQSS_KD_STATS_STRIDE_N 72
+int fqss_kd_loss_n(const float* est, const float* fest, const float* tgt, int B, int S, int64_t T, float kd_lambda, int mode,
+                   int use_threshold, float threshold, double* stats, float* out, float* w_out, float* sisdr_out, float* gest,
+                   fqss_stream_t stream);
+/* the streaming pass of fqss_kd_loss_n alone: the moments of the row layout above */
+int fqss_kd_moments_n(const float* est, const float* fest, const float* tgt, int B, int S, int64_t T, double* stats,
+                      fqss_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K16  global-norm clip + Adam over one flat fp32 parameter buffer
