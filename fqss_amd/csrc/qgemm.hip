@@ -1114,6 +1114,7 @@ static int qpw_fwd_impl(const char* who, const uint8_t* xc, const int8_t* wi, co
         g.qy_min1 = qq->min1; g.qy_max1 = qq->max1; g.qy_min2 = qq->min2; g.qy_max2 = qq->max2;
         g.qact = qq->act; g.qslope = qq->slope;
         FQSS_REQUIRE(!qq->stats || Co2 == 0, "output statistics: single-output launches only");
+        FQSS_REQUIRE(!qq->stats || fqss_qpw_stat_slots(Co1, M) > 0, "output statistics: fqss_qpw_stat_slots(Co1, M) is 0 for this shape");
         g.stats = qq->stats;
         const FqssAddAfter* ad[2] = {qq->add1, qq->add2};
         for (int i = 0; i < 2; ++i) {

@@ -308,7 +308,8 @@ int fqss_qpw_fwdq(const uint8_t* xc, const int8_t* wi, const float* dw, const fl
                   int64_t* stats1, fqss_stream_t stream);
 /* stats1 (nullable, Co2 = 0 only): exact integer statistics (sum c, sum c^2) of the output codes yc1, one slot per workgroup,
  * [B][fqss_qpw_stat_slots(Co1, M)][2] int64 -- handed to fqss_gnq_fwd when the consumer is a GroupNormQ ("stats can
- * be produced by the previous kernel's epilogue").  fqss_*_stat_slots return 0 when that shape cannot emit them. */
+ * be produced by the previous kernel's epilogue").  fqss_*_stat_slots return 0 when that shape cannot emit them; fqss_qpw_fwdq
+ * refuses a non-null stats1 for such a shape (FQSS_EINVAL: the buffer the count sizes would hold no slot). */
 int fqss_qpw_stat_slots(int Co, int M);
 int fqss_dwq_stat_slots(int C, int M);
 /* fqss_qpw_fwdq (no activation) with the AddQ layers that are the ONLY consumers of its outputs evaluated in the same epilogue:
