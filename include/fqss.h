@@ -694,7 +694,12 @@ int fqss_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, cons
  *           the input projection inside _VF.lstm (LSTMQ :590), the 1x1 Conv2dQ of DPT.output (dptnetq.py:187) + autograd
  *   fwd   : z[r][o]   = sum_i x[r][i] w[o][i] + bias[o]   (bias optional)
  *   bwd_x : gx[r][i]  = sum_o gz[r][o] w[o][i]
- *   bwd_w : gw[o][i] += sum_r gz[r][o] x[r][i]                                                     */
+ *   bwd_w : gw[o][i] += sum_r gz[r][o] x[r][i]
+ * Operands may sit at any 4-B aligned address with any row stride >= the row length (16-B aligned bases and row strides that are
+ * multiples of 4 floats and >= the row length rounded up to 4 take the split-bf16 kernel, everything else the scalar-load fp32 one);
+ * padding floats of a row are read but never enter a result.  Writes: exactly [R][Co] of z, [R][Ci] of gx, the Co x Ci of gw -- nothing
+ * in the row padding, no whole float4 past the last live column: column-block views of a wider matrix are legal outputs.
+ * R = 0 is a no-op. (tests/test_gpu_rowgemm_kernels.py)                                                */
 int fqss_rowlin_fwd(const float* x, const float* w, const float* bias, float* z, int64_t R, int Ci, int Co,
                     int64_t ld_x, int64_t ld_w, int64_t ld_z, fqss_stream_t stream);
 /* fqss_rowlin_fwd with the weight given as its three exact bf16 planes [3][Co][Ci] (fqss_split3_planes): for weights that do not
@@ -933,7 +938,12 @@ int fqss_bcast_sum(const float* g, float* out, int64_t L, int64_t Bp, int C, fqs
  *   z[r][o] = dw[o] * (dx * sum_i wk[o][i] xc[r][i] + min_x * rw[o]) + bias[o]
  * xc: u8 activation codes [R][Ci] (rows 16-B aligned) with the ranges (qmin_x, qmax_x) of the quantizer that produced them;
  * wk / dw / rw: the weight's int8 codes, per-row step and code sum from fqss_wq_codes.  Ci a multiple of 16.
- * replaces: F.linear on fake-quantized operands (qat_layers.py:521-536, 889-901, 941) in the quantizing phase.            */
+ * replaces: F.linear on fake-quantized operands (qat_layers.py:521-536, 889-901, 941) in the quantizing phase.
+ * 16 <= Ci <= 2048, ld_x a multiple of 16; z (and y of fqss_qrow_fwdq) may have any row stride >= Co and any 4-B aligned base: 16-B
+ * aligned bases with row strides that are multiples of 4 floats leave through the LDS-staged epilogue, everything else through scalar
+ * stores, with the same result bits (fqss_qrow_fwdq2 takes the staged form only: Co a multiple of 4, 16-B aligned z / y rows, 4-B
+ * aligned yc rows).  Writes: exactly [R][Co] of z / y / yc -- nothing in the row padding, no whole float4 (or code
+ * word) past column Co: column-block views of a wider matrix are legal outputs.  Reads of xc stay inside [R][Ci].  R = 0 is a no-op.  */
 int fqss_qrow_fwd(const uint8_t* xc, const int8_t* wk, const float* dw, const float* rw, const float* bias,
                   const float* qmin_x, const float* qmax_x, float* z, int64_t R, int Ci, int Co, int64_t ld_x,
                   int64_t ld_z, fqss_stream_t stream);
@@ -954,7 +964,10 @@ int fqss_qrow_fwdq2(const uint8_t* xc, const int8_t* wk, const float* dw, const 
  * three MFMA products per k instead of the six of the fp32 x fp32 form.
  *   fqss_qrow_bwd_x: gx[r][i]  = sum_o gz[r][o] * (dw[o] * wi[o][i])       wi int8 [Co][Ci] dense
  *   fqss_qrow_bwd_w: gw[o][i] += sum_r gz[r][o] * (dx * c[r][i] + min_x)   c u8 [R][ld_xc], (dx, min_x) from the range scalars
- * Ci, Co and the row strides are multiples of 4, operands 16-B (codes 4-B) aligned */
+ * Ci, Co and the row strides of gz and xc are multiples of 4, gz and dw 16-B (codes 4-B) aligned; gx and gw may have any row stride >=
+ * Ci.  Writes: exactly [R][Ci] of gx, the Co x Ci of gw (row stride ld_gw) and Co floats of gbias -- nothing in the row padding or
+ * between the slots of a batched / grouped call; gbias is added once per call, not once per column tile.  R = 0 is a no-op (in a job of
+ * fqss_qrow_bwd_w_group it is refused; njobs = 0 is the no-op there). */
 int fqss_qrow_bwd_x(const float* gz, const int8_t* wi, const float* dw, float* gx, int64_t R, int Ci, int Co,
                     int64_t ld_gz, int64_t ld_gx, fqss_stream_t stream);
 int fqss_qrow_bwd_w(const float* gz, const uint8_t* xc, const float* qmin_x, const float* qmax_x, float* gw,
