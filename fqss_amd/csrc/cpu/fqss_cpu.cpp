@@ -966,6 +966,22 @@ int fqss_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, cons
     if (gnorm_out) *gnorm_out = (float)norm;
     return FQSS_OK;
 }
+// gradient accumulation: the moves between the gradient arena and the window's accumulator (same contract as the HIP entry point)
+int fqss_grad_accum(float* acc, float* g, int64_t n, int mode, fqss_stream_t) {
+    REQUIRE(acc && g, "null pointer");
+    REQUIRE(mode >= 0 && mode <= 3, "mode: 0 (acc = g), 1 (acc += g), 2 (g += acc) or 3 (g = acc)");
+    REQUIRE(n >= 0 && n % 4 == 0 && ((uintptr_t)acc & 15u) == 0 && ((uintptr_t)g & 15u) == 0,
+            "n must be a multiple of 4 floats and both pointers 16-B aligned");
+    REQUIRE(acc + n <= g || g + n <= acc, "acc and g overlap");
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+        if (mode == 0) acc[i] = g[i];
+        else if (mode == 1) acc[i] = acc[i] + g[i];
+        else if (mode == 2) g[i] = acc[i] + g[i];
+        else g[i] = acc[i];
+    }
+    return FQSS_OK;
+}
 
 // ------------------------------------------------------------------------------------------------ data side (LibriMix dataset, librimix_dataset.py:54, 139-153)
 // the op sequences of csrc/data_ops.hip: energies in fp64, gains in fp32 (process.py:77-103), max_clip(0.9) (process.py:57-62)

@@ -133,6 +133,16 @@ int main() {
     const float p7 = p[7];
     CHECK(fqss_adam_clip(p.data(), gp.data(), m1.data(), v1.data(), n, &ss, 5.0f, 1.0f, 1e-3f, 0.9f, 0.999f, 1e-8f, &stp, t0.data(), &gn, nullptr) == 0);
     CHECK(stp == 1 && p[7] == p7 && fabs(gn - sqrt(ss)) < 1e-3);
+    // gradient accumulation: the four modes on a 16-B aligned pair, the refused arguments
+    {
+        alignas(16) float ac[8] = {1, 2, 3, 4, 5, 6, 7, 8}, gg[8] = {.5f, .5f, .5f, .5f, -1, -1, -1, -1};
+        CHECK(fqss_grad_accum(ac, gg, 8, 1, nullptr) == 0 && ac[0] == 1.5f && ac[7] == 7.0f && gg[7] == -1.0f);
+        CHECK(fqss_grad_accum(ac, gg, 8, 2, nullptr) == 0 && gg[0] == 2.0f && gg[7] == 6.0f && ac[7] == 7.0f);
+        CHECK(fqss_grad_accum(ac, gg, 8, 0, nullptr) == 0 && ac[3] == gg[3] && fqss_grad_accum(ac, gg, 8, 3, nullptr) == 0 && gg[4] == ac[4]);
+        CHECK(fqss_grad_accum(ac, gg, 0, 1, nullptr) == 0);
+        CHECK(fqss_grad_accum(ac, gg, 6, 1, nullptr) == FQSS_EINVAL && fqss_grad_accum(ac + 1, gg, 4, 1, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_grad_accum(ac, gg, 8, 4, nullptr) == FQSS_EINVAL && fqss_grad_accum(nullptr, gg, 8, 1, nullptr) == FQSS_EINVAL);
+    }
     // signal-to-distortion ratio: pitched rows, a signal shorter than the filter, a silent target, refused arguments
     {
         const int P = 3, ldp = 310;

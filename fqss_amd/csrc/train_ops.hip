@@ -565,6 +565,24 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const 
     }
 }
 
+// gradient accumulation (fqss.h: fqss_grad_accum): the four moves between the gradient arena g and the window's accumulator acc.
+// Thread i owns float4 i of both: one fp32 add per element, no order to depend on.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_grad_accum(float4* __restrict__ acc, float4* __restrict__ g, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        if (MODE == 0) {
+            acc[i] = g[i];
+        } else if (MODE == 3) {
+            g[i] = acc[i];
+        } else {
+            const float4 a = acc[i], b = g[i];
+            const float4 s = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+            if (MODE == 1) acc[i] = s;
+            else g[i] = s;
+        }
+    }
+}
+
 __global__ void k_step_end(int32_t* step_t, const double* sumsq, float grad_scale, float* gnorm_out) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         *step_t = *step_t + 1;
@@ -736,6 +754,25 @@ extern "C" int fqss_sumsq(const float* g, int64_t n, double* sumsq, fqss_stream_
     if (nb > 1024) nb = 1024;
     hipLaunchKernelGGL(k_sumsq, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, g, n, sumsq);
     return launch_status("fqss_sumsq");
+}
+
+extern "C" int fqss_grad_accum(float* acc, float* g, int64_t n, int mode, fqss_stream_t stream) {
+    FQSS_REQUIRE(acc && g, "null pointer");
+    FQSS_REQUIRE(mode >= 0 && mode <= 3, "mode: 0 (acc = g), 1 (acc += g), 2 (g += acc) or 3 (g = acc)");
+    FQSS_REQUIRE(n >= 0 && n % 4 == 0 && aligned16(acc) && aligned16(g), "n must be a multiple of 4 floats and both pointers 16-B aligned");
+    FQSS_REQUIRE(acc + n <= g || g + n <= acc, "acc and g overlap");
+    if (n == 0) return FQSS_OK;
+    const int64_t n4 = n / 4;
+    int64_t nb = cdiv(n4, 256);
+    if (nb > 2048) nb = 2048;
+    hipStream_t s = (hipStream_t)stream;
+    float4* a4 = reinterpret_cast<float4*>(acc);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    if (mode == 0) hipLaunchKernelGGL(k_grad_accum<0>, dim3((unsigned)nb), dim3(256), 0, s, a4, g4, n4);
+    else if (mode == 1) hipLaunchKernelGGL(k_grad_accum<1>, dim3((unsigned)nb), dim3(256), 0, s, a4, g4, n4);
+    else if (mode == 2) hipLaunchKernelGGL(k_grad_accum<2>, dim3((unsigned)nb), dim3(256), 0, s, a4, g4, n4);
+    else hipLaunchKernelGGL(k_grad_accum<3>, dim3((unsigned)nb), dim3(256), 0, s, a4, g4, n4);
+    return launch_status("fqss_grad_accum");
 }
 
 extern "C" int fqss_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq,

@@ -1326,6 +1326,19 @@ def adam_clip(p, g, m, v, sumsq_acc, step_t, gnorm_out, max_norm, grad_scale, lr
               _stream())
 
 
+ACC_SET, ACC_ADD, ACC_FINISH, ACC_TAKE = 0, 1, 2, 3      # fqss_grad_accum modes: acc = g | acc += g | g += acc | g = acc
+
+
+def grad_accum(acc, g, mode):
+    """gradient accumulation between the gradient arena `g` and the window's accumulator `acc` (whole buffers or equal slices of them;
+    contiguous fp32, 16-B aligned, a multiple of 4 floats)"""
+    _need_gpu(acc, g)
+    if acc.numel() != g.numel() or not (acc.is_contiguous() and g.is_contiguous()):
+        raise _lib.FqssError(f"grad_accum: acc ({acc.numel()}) and g ({g.numel()}) must be contiguous and of one size")
+    if g.numel():        # (an empty slice has no address to hand over)
+        _lib.call("fqss_grad_accum", _p(acc), _p(g), g.numel(), int(mode), _stream())
+
+
 # ------------------------------------------------------------------ BatchNorm under BatchNormQ (csrc/batchnorm.hip)
 def bn_moments(x):
     """[B, C, M] -> fp64 [C, 2]: (sum, sum of squares) per channel"""

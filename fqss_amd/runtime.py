@@ -8,6 +8,7 @@ MI355X-first choices:
   * nothing on the step reads device memory from the host (the reference syncs ~400x per forward,
     qat_quant.py:235-238), so the whole step can be captured in a hipGraph.
 """
+import operator
 import os
 
 import torch
@@ -19,7 +20,7 @@ from . import ops_dp
 
 
 class ParamArena:
-    def __init__(self, params, align=64):
+    def __init__(self, params, align=64, accumulator=False):
         params = [p for p in params if p.requires_grad]
         assert params, "no trainable parameters"
         dev = params[0].device
@@ -36,6 +37,9 @@ class ParamArena:
         self.sumsq = torch.zeros(1, device=dev, dtype=torch.float64)
         self.step_t = torch.zeros(1, device=dev, dtype=torch.int32)
         self.gnorm = torch.zeros(1, device=dev)
+        # gradient accumulation only (KDTrainStep(accumulate=N > 1)): the sum of a window's micro-batch gradients while the next
+        # micro-batch rewrites flat_g.  Empty between windows, so it is not state
+        self.acc = torch.zeros(n, device=dev) if accumulator else None
         # torch.optim.Adam counts steps per parameter, from the first step the parameter has a gradient
         self.t0 = torch.full((n,), 2 ** 31 - 1, device=dev, dtype=torch.int32)
         self._inactive = list(zip(params, offs))
@@ -448,7 +452,7 @@ class KDTrainStep:
 
     def __init__(self, model, fmodel, kd_lambda=0.1, lr=1e-3, clip=5.0, comm=None, loss="sisdr_pit", source_weights=None,
                  batched_quantizers=True, fast=True, coded=True, buckets=None, sync_observer_ranges=True,
-                 betas=(0.9, 0.999), loss_threshold=None, teacher_ahead=False):
+                 betas=(0.9, 0.999), loss_threshold=None, teacher_ahead=False, accumulate=1):
         """loss: "sisdr_pit" = the asteroid KD loss (mysystem.py:124-151); "sisdr_pit_per_sample" = the speechbrain env's form of it
         (speechbrain_librimix_trainer.py:99-115, 141-149: log per sample, mean over the samples whose loss exceeds `loss_threshold`;
         per-GPU batch 1 or 2, see fqss_kd_loss_per_sample); "l1_sdr" = the htdemucs solver's
@@ -466,7 +470,24 @@ class KDTrainStep:
         changes (mysystem.py:132-133 runs it under no_grad on the raw mixture), so a loader that knows the next batch can hide it
         behind the student's VALU / HBM-bound kernels.  Still one teacher forward per step; the step that finds no look-ahead
         result for its mixture (the first one, or a caller that did not announce it) runs the teacher beside its own forward as
-        before.  Same values either way (tests/test_gpu_kdstep_path.py)."""
+        before.  Same values either way (tests/test_gpu_kdstep_path.py).
+        accumulate = N: one optimizer update per window of N consecutive micro-batches (pl.Trainer(accumulate_grad_batches=N),
+        speechbrain's grad_accumulation_factor): the update takes the SUM of the window's micro-batch gradients at grad_scale
+        1 / (world * N) -- the data-parallel contract in time instead of space.  Each call runs one micro-batch; the N-th also
+        exchanges and updates (`pending`: micro-batches of the open window).  micro_batch() / commit(keep) is the same in two
+        halves for trainers that may drop a micro-batch, flush() ends a window early (end of an epoch).  1: the step as it always
+        was -- no accumulator, the same launches, the one-graph replay."""
+        try:
+            accumulate = operator.index(accumulate)
+        except TypeError:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}") from None
+        if accumulate < 1:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
+        self.accumulate = accumulate
+        self._pos = 0               # micro-batches committed in the open window (kept or dropped)
+        self._kept = 0              # ... of which the accumulator holds this many
+        self._open = False          # a micro-batch has run and waits for its commit()
+        self._win_eager = False     # a micro-batch of the open window ran eagerly: its update activates parameters eagerly too
         self.model, self.fmodel = model, fmodel
         self.cpu = _lib.BACKEND == "cpu"
         if self.cpu:
@@ -511,7 +532,7 @@ class KDTrainStep:
                 rest = [p for p in params if id(p) not in seen]       # anything the model did not assign: with the first segment
                 self._seg_ids[0] |= {id(p) for p in rest}
                 params = rest + ordered
-        self.arena = ParamArena(params)
+        self.arena = ParamArena(params, accumulator=accumulate > 1)
         name_of = {id(p): n for n, p in model.named_parameters()}
         self.arena.names = [name_of[id(p)] for p in self.arena.params]       # the layout a stored arena is checked against
         # FQSS_DETERMINISTIC=1: bit-reproducible gradients (kernels.DetMode; no effect on the values beyond fp32 summation order)
@@ -572,7 +593,11 @@ class KDTrainStep:
         While the ranks' activation ranges differ, every rank's ranges and n_iter travel too (`rank_ranges`, [world, quantizers, 3]
         int32 words: the bits of min and max, n_iter) -- which makes this a COLLECTIVE call at world > 1: every rank calls it, every rank
         gets the same `rank_ranges`.  Not stored: QuantTables, graphs and look-ahead results (rebuilt by the next eager quantizing step
-        and maybe_capture), and the integer shadows of FQSS_DETERMINISTIC=1, which are empty between steps."""
+        and maybe_capture), and the integer shadows of FQSS_DETERMINISTIC=1, which are empty between steps.  Nor the gradient
+        accumulator: a window with micro-batches pending is refused (the trainers flush() before they write a checkpoint)."""
+        if self.pending or self._open:
+            raise RuntimeError(f"KDTrainStep.state_dict: {self.pending + int(self._open)} micro-batch(es) of an accumulation window are "
+                               "pending; call flush() first (their gradients are not part of the stored state)")
         aqs, wqs = self._quantizers()
         c = lambda t: t.detach().cpu().clone()
         held = {id(p) for p in self.arena.params}
@@ -640,6 +665,7 @@ class KDTrainStep:
             self._ranges_synced = bool(sd["ranges_synced"])
         self.tables, self._graphs, self._graph_all, self._tgraph, self._ahead, self._ahead_key = None, None, None, None, None, None
         self._eager_q, self._odd, self.last = 0, 0, None
+        self._pos, self._kept, self._open, self._win_eager = 0, 0, False, False      # (whatever window was open here is abandoned)
 
     def can_capture(self):
         from .quantization.qat.qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize
@@ -654,8 +680,8 @@ class KDTrainStep:
         """training loops: once the observer phase is over (and after every learning-rate change) record the step into hipGraphs
         WITHOUT running it (warmup=0: no extra optimizer step); later calls with same-shaped batches replay.  At least one
         quantizing-phase step must have run eagerly first: it builds the QuantTables and starts the Adam clocks of the activation
-        ranges (the captured clip+Adam launch does not activate parameters)"""
-        if self.use_graph and self._graphs is None and self._eager_q >= 1 and self.can_capture():
+        ranges (the captured clip+Adam launch does not activate parameters).  accumulate > 1: recorded at a window boundary only"""
+        if self.use_graph and self._graphs is None and self._eager_q >= 1 and self.can_capture() and not (self._pos or self._open):
             self.capture(x, tgt, warmup=0)
         elif self._graphs is not None and not self._fits(x, tgt):
             # a batch of another shape (a file-backed loader's short utterance) runs eagerly (__call__); only when the NEW shape stays
@@ -823,7 +849,8 @@ class KDTrainStep:
     def _optimize(self, activate=True):
         if activate:
             self.arena._activate_touched()
-        self.arena.clip_adam_step(self.lr, self.clip, 1.0 / self._world(), betas=self.betas, activate=False)
+        # the update takes the average of the gradients it is given: over the ranks and over the micro-batches of a window
+        self.arena.clip_adam_step(self.lr, self.clip, 1.0 / (self._world() * self.accumulate), betas=self.betas, activate=False)
 
     def _maybe_sync_ranges(self):
         """world > 1: once, when the observer phase is over, every rank takes the mean of the observed activation ranges"""
@@ -831,20 +858,100 @@ class KDTrainStep:
             self.comm.sync_observer_ranges(self.model)
             self._ranges_synced = True
 
-    def _step_eager(self, x, tgt, x_next=None):
+    def _step_eager(self, x, tgt, x_next=None, exchange=True):
         """fwd + loss, then per backward segment: backward -> all-reduce of its gradient slice on the communication stream, which
-        overlaps the next segment's backward; the optimizer waits for the last exchange"""
+        overlaps the next segment's backward; the optimizer waits for the last exchange.  exchange=False (a micro-batch of an
+        accumulation window): no collective -- the window's sum is exchanged once, by commit() / flush()"""
         fest = self._take_ahead(x) if self.teacher_ahead else None
         res, est, gest, cuts = self._forward_loss(x, tgt, x_next if self.teacher_ahead else None, fest)
         nseg = self._nseg(cuts)
         for k in range(nseg):
             self._backward_segment(k, est, gest, cuts)
-            self._reduce_segment(k, nseg)
-        self._join_reduces()
+            if exchange:
+                self._reduce_segment(k, nseg)
+        if exchange:
+            self._join_reduces()
         return res
 
+    # ---- gradient accumulation: a window of `accumulate` micro-batches per update (DESIGN.md "Gradient accumulation") ---------
+    @property
+    def pending(self):
+        """micro-batches of the open window, kept or dropped (0: the last call ended with an update, or nothing has run)"""
+        return self._pos
+
+    def micro_batch(self, x, tgt, x_next=None):
+        """first half of a call: fwd + loss + bwd of one micro-batch into the gradient arena (hipGraph replay where the graphs fit).
+        Nothing is exchanged, accumulated or updated before commit() says whether this micro-batch counts."""
+        if self._open:
+            raise RuntimeError("KDTrainStep.micro_batch: the previous micro-batch has not been committed")
+        self._maybe_sync_ranges()
+        if self._graphs is not None and self.use_graph and self._fits(x, tgt):
+            r = self.replay_fwd_bwd(x, tgt, x_next if (x_next is not None and x_next.shape == x.shape) else None, exchange=False)
+        else:
+            self.last = r = self._step_eager(x, tgt, x_next, exchange=False)
+            self._win_eager = True
+        self._open = True
+        return r
+
+    def commit(self, keep=True):
+        """second half: keep=True adds the micro-batch's gradient to the window, keep=False drops it; either way the window moves on
+        and its divisor stays world * accumulate.  The last micro-batch of a window brings the sum into the gradient arena, exchanges
+        it and updates -- unless every micro-batch was dropped: then nothing is updated and no Adam clock moves.  At world > 1 every
+        rank passes the same `keep` (the exchange is a collective).  True when an update ran."""
+        if not self._open:
+            raise RuntimeError("KDTrainStep.commit: no micro-batch to commit")
+        self._open = False
+        a = self.arena
+        last = self._pos + 1 == self.accumulate
+        if last:
+            # kept, with earlier ones held: g += acc; dropped: g = acc; kept and alone: g is the sum already
+            mode = (K.ACC_FINISH if keep else K.ACC_TAKE) if self._kept else None
+            return self._end_window(mode, update=bool(keep or self._kept))
+        if keep:
+            K.grad_accum(a.acc, a.flat_g, K.ACC_ADD if self._kept else K.ACC_SET)      # (the first kept one needs no zeroed accumulator)
+            self._kept += 1
+        self._pos += 1
+        return False
+
+    def flush(self):
+        """end the open window early (end of an epoch, before validation and the checkpoint): the held sum is exchanged and applied at
+        the same 1 / (world * accumulate) -- each micro-batch's share was fixed when it ran, as under pl.Trainer.  Nothing pending:
+        nothing happens.  True when an update ran."""
+        if self._open:
+            raise RuntimeError("KDTrainStep.flush: the last micro-batch has not been committed")
+        if self._pos == 0:
+            return False
+        return self._end_window(K.ACC_TAKE if self._kept else None, update=self._kept > 0)
+
+    def _end_window(self, mode, update):
+        """the window's sum into the gradient arena (fqss_grad_accum `mode`; None: it is there already), slice by slice in the order the
+        backward segments finish, each slice's all-reduce on the communication stream behind its own launch (it overlaps the next
+        slice's); then clip + Adam on the averaged sum"""
+        a = self.arena
+        if update:
+            nseg = len(self.segments) if self.segments is not None else 1
+            for k in range(nseg):
+                lo, hi = (0, a.numel) if nseg == 1 else self.segments[nseg - 1 - k]
+                if mode is not None:
+                    K.grad_accum(a.acc[lo:hi], a.flat_g[lo:hi], mode)
+                self._reduce_segment(k, nseg)
+            self._join_reduces()
+            if self._graphs is not None and not self._win_eager:
+                self.replay_optimize()
+            else:
+                self._optimize()
+                if self.tables is not None or (not self.batched_quantizers and self.can_capture()):
+                    self._eager_q += 1
+        self._pos, self._kept, self._win_eager = 0, 0, False
+        return update
+
     def __call__(self, x, tgt, x_next=None):
-        """x_next (teacher_ahead=True only): the mixture tensor the NEXT call will be given -- the same tensor object, unmodified"""
+        """x_next (teacher_ahead=True only): the mixture tensor the NEXT call will be given -- the same tensor object, unmodified.
+        accumulate > 1: one micro-batch; the call that completes a window also updates (`pending` is 0 after it)"""
+        if self.accumulate > 1:
+            r = self.micro_batch(x, tgt, x_next)
+            self.commit()
+            return r
         self._maybe_sync_ranges()
         if self._graphs is not None and self.use_graph and self._fits(x, tgt):
             return self.replay(x, tgt, x_next if (x_next is not None and x_next.shape == x.shape) else None)
@@ -859,6 +966,8 @@ class KDTrainStep:
         # a prefetching loader's reader thread allocates and launches on its own stream: not while this thread records a graph (the
         # default capture mode faults on another thread's hipMalloc / event calls)
         from .loader import DEVICE_WORK_LOCK
+        if self._pos or self._open:
+            raise RuntimeError("KDTrainStep.capture: an accumulation window is open; graphs are recorded at a window boundary")
         with DEVICE_WORK_LOCK:
             return self._capture(x, tgt, warmup)
 
@@ -870,12 +979,19 @@ class KDTrainStep:
             if isinstance(m, GradientWeightFakeQuantize):
                 assert not m.observer_mode, "capture() needs the weight observers to have run"
         self._maybe_sync_ranges()
+        self._own_det()         # (another step of this process may have run since this one's last eager call)
         self._sx, self._st = x.clone(), tgt.clone()
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             for _ in range(warmup):              # eager steps: activates every live parameter's Adam clock (bench: warm caches)
+                if self.accumulate > 1:          # ... whole windows of them
+                    for _ in range(self.accumulate):
+                        self.last = self._step_eager(self._sx, self._st, exchange=False)
+                        self._open = self._win_eager = True
+                        self.commit()
+                    continue
                 self.last = self._step_eager(self._sx, self._st)
                 self._optimize()
         cur.wait_stream(side)
@@ -917,8 +1033,9 @@ class KDTrainStep:
         del est, gest, cuts
         # single rank, one segment: nothing has to happen between the two halves, so the whole step is ALSO captured as one graph
         # (replay() then costs one launch; replay_fwd_bwd / replay_optimize keep serving the trainers that may skip an update)
+        # (accumulate > 1: an accumulate launch, and on most micro-batches no update, sits between the halves -- the two-graph form serves)
         self._graph_all = None
-        if not self._exchange() and len(graphs) == 1:
+        if not self._exchange() and len(graphs) == 1 and self.accumulate == 1:
             ga = torch.cuda.CUDAGraph()
             with torch.cuda.graph(ga, pool=graphs[0].pool()):
                 self.last_all, est, gest, cuts = self._forward_loss(self._sx, self._st, None, fest_cur, False)
@@ -969,8 +1086,9 @@ class KDTrainStep:
         if self.det is not None and K.DetMode.owner is not self.det:
             self.det.activate()
 
-    def replay_fwd_bwd(self, x=None, tgt=None, x_next=None):
-        """first half of a captured step (fwd + loss + bwd, gradients exchanged); the caller then calls replay_optimize() or skips"""
+    def replay_fwd_bwd(self, x=None, tgt=None, x_next=None, exchange=True):
+        """first half of a captured step (fwd + loss + bwd, gradients exchanged); the caller then calls replay_optimize() or skips.
+        exchange=False (a micro-batch of an accumulation window): no collective is due here, commit() / flush() issue the window's"""
         self._own_det()
         self._stage(x, tgt, x_next)
         graphs = self._graphs[0]
@@ -979,8 +1097,10 @@ class KDTrainStep:
             gk.replay()
             if ev is not None and k == len(graphs) - 1:
                 ev[0].record()                  # the backward is over: whatever the optimizer still waits for is exposed exchange time
-            self._reduce_segment(k, len(graphs))
-        self._join_reduces()
+            if exchange:
+                self._reduce_segment(k, len(graphs))
+        if exchange:
+            self._join_reduces()
         if ev is not None:
             ev[1].record()
         return self.last
@@ -990,6 +1110,14 @@ class KDTrainStep:
         self._graphs[1].replay()
 
     def replay(self, x=None, tgt=None, x_next=None):
+        if self.accumulate > 1:
+            # one micro-batch; the one that completes the window also exchanges and replays clip + Adam (commit)
+            if self._open:
+                raise RuntimeError("KDTrainStep.replay: the previous micro-batch has not been committed")
+            r = self.replay_fwd_bwd(x, tgt, x_next, exchange=False)
+            self._open = True
+            self.commit()
+            return r
         if getattr(self, "_graph_all", None) is not None:
             self._own_det()
             self._stage(x, tgt, x_next)

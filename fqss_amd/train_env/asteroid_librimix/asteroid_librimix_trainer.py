@@ -147,7 +147,7 @@ def _train(yml_path, device, resume=None):
     # teacher_ahead: the path bench.py measures; HIP backend only)
     ahead = (not cpu) and training_cfg.get("kd_lambda", 0) > 0 and bool(training_cfg.get("teacher_ahead", True))
     system = System(model, fmodel, training_cfg.get("kd_lambda", 0), lr=opt.get("lr", 1e-3), clip=5.0, comm=comm, betas=betas,
-                    teacher_ahead=ahead)
+                    teacher_ahead=ahead, accumulate=training_cfg.get("accumulate_grad_batches", 1))
     global LAST_SYSTEM
     LAST_SYSTEM = system                # tools / tests: the stepper of the run that just finished (its graphs, its model)
     best, history, since_best, first_epoch = float("inf"), [], 0, 0
@@ -171,6 +171,9 @@ def _train(yml_path, device, resume=None):
         for i, (x, tgt, x_next) in enumerate(data.train(epoch)):
             system.training_step((x, tgt), i, x_next=x_next)
             n_steps += 1
+        # accumulate_grad_batches (pl.Trainer): an epoch that ends inside a window updates on what the window holds, before the
+        # validation and the checkpoint
+        system.stepper.flush()
         if not cpu:
             torch.cuda.synchronize()
         t_epoch = time.perf_counter() - t_epoch

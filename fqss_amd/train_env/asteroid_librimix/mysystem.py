@@ -13,7 +13,7 @@ from .wsdr import KDObjective, si_sdr
 class System:
     default_monitor = "val_loss"
 
-    def __init__(self, model, fmodel, kd_lambda, lr=1e-3, clip=5.0, comm=None, betas=(0.9, 0.999), teacher_ahead=False):
+    def __init__(self, model, fmodel, kd_lambda, lr=1e-3, clip=5.0, comm=None, betas=(0.9, 0.999), teacher_ahead=False, accumulate=1):
         # kd_lambda = 0: the reference trains on the plain PIT SI-SDR loss without the teacher (mysystem.py:153-156); KDTrainStep then
         # runs fqss_pit_sisdr_loss and never calls the teacher
         self.model = model
@@ -21,7 +21,7 @@ class System:
         self.kd_lambda = kd_lambda
         self.objective = KDObjective(kd_lambda)
         self.stepper = KDTrainStep(model, fmodel, kd_lambda=kd_lambda, lr=lr, clip=clip, comm=comm, betas=betas,
-                                   teacher_ahead=teacher_ahead)
+                                   teacher_ahead=teacher_ahead, accumulate=accumulate)
         self.logged = {}
 
     def forward(self, *a, **k):
@@ -40,7 +40,8 @@ class System:
         return -si_sdr(est, targets).mean(), 0
 
     def training_step(self, batch, batch_nb, x_next=None):
-        """one optimiser step through the fused runtime; logs `loss` / `kd_loss` like the reference.  x_next: the mixture of the
+        """one optimiser step through the fused runtime (accumulate_grad_batches = N: one micro-batch, the N-th of a window updates);
+        logs each call's `loss` / `kd_loss` like the reference.  x_next: the mixture of the
         NEXT call (a prefetching loader has it on the device already): the teacher starts on it beside this step"""
         self.stepper.maybe_capture(*batch)      # quantizing phase: the step replays as hipGraphs from here on
         r = self.stepper(*batch, x_next=x_next if self.stepper.teacher_ahead else None)

@@ -77,7 +77,8 @@ class Solver:
         self.weights = torch.tensor(conf.get("weights", [1.0] * model.n_srcs), device=device, dtype=torch.float32)
         self.step = KDTrainStep(model, fmodel, kd_lambda=float(conf.get("kd_lambda", 0.1)), lr=float(opt["lr"]),
                                 clip=float(opt.get("clip_grad") or 0.0), comm=comm, loss="l1_sdr", source_weights=self.weights,
-                                betas=(float(opt.get("momentum", 0.9)), float(opt.get("beta2", 0.999))))
+                                betas=(float(opt.get("momentum", 0.9)), float(opt.get("beta2", 0.999))),
+                                accumulate=opt.get("accumulate_grad_batches", 1))    # ours (demucs has none): micro-batches per update
         self.history = []
         self.best_state, self.best_loss = None, float("inf")
         self.ckpt_file = os.path.join(conf["work_dir"], checkpoint.NAME)
@@ -151,6 +152,8 @@ class Solver:
                     est = self.model(mix)
                     loss, task, _, _, _ = K.hd_kd_loss(est, est, sources, self.weights, 0.0, want_grad=False)    # kd_lambda 0: the L1 task loss
                 tot += loss.double()
+        if train:
+            self.step.flush()       # optim.accumulate_grad_batches: a window the epoch cut short updates on what it holds
         self.comm.all_reduce_sum(tot)
         out = {"loss": tot.item() / (n * self.comm.world), "reco": tot.item() / (n * self.comm.world)}
         if train:

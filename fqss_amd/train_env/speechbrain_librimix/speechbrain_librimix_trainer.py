@@ -200,7 +200,9 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda", resum
     upper = float(hp.get("loss_upper_lim", 999999))
     threshold = float(hp["threshold"]) if hp.get("threshold_byloss") and "threshold" in hp else None
     step = KDTrainStep(model, fmodel, kd_lambda=kd_lambda, lr=lr, clip=clip if clip >= 0 else 1e30, comm=comm,
-                       loss="sisdr_pit_per_sample", loss_threshold=threshold)
+                       loss="sisdr_pit_per_sample", loss_threshold=threshold,
+                       accumulate=hp.get("grad_accumulation_factor", 1))      # speechbrain Brain's run option: micro-batches per update
+    accum = step.accumulate > 1
     sch = hp.get("lr_scheduler") or {}
     sched = ReduceLROnPlateau(sch.get("factor", 0.5), sch.get("patience", 2), sch.get("dont_halve_until_epoch", 65))
     history, best, nonfinite, done = [], float("inf"), 0, 0
@@ -219,23 +221,31 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda", resum
             step.maybe_capture(x, tgt)        # quantizing phase: both halves of the step replay as hipGraphs
             # (an utterance shorter than training_signal_len gives a batch of another shape: that step runs eagerly)
             graphed = step._graphs is not None and x.shape == step._sx.shape
-            step._maybe_sync_ranges()
-            # fwd + loss + bwd with the gradient exchange of the data-parallel ranks (both forms all-reduce the flat gradient)
-            r = step.replay_fwd_bwd(x, tgt) if graphed else step._step_eager(x, tgt)
+            if accum:
+                # grad_accumulation_factor = N: one micro-batch, no collective; the gate below decides whether it joins its window
+                r = step.micro_batch(x, tgt)
+            else:
+                step._maybe_sync_ranges()
+                # fwd + loss + bwd with the gradient exchange of the data-parallel ranks (both forms all-reduce the flat gradient)
+                r = step.replay_fwd_bwd(x, tgt) if graphed else step._step_eager(x, tgt)
             # (the hard threshold of easy items, threshold_byloss, is applied inside the loss kernel)
             flag.copy_((r["loss"] < upper).float().reshape(1))       # False for NaN / inf as well
             if comm.world > 1:
                 comm.all_reduce_sum(flag)
-            if flag.item() >= comm.world:        # the reference syncs here too (loss.detach().cpu(), :199)
-                if graphed:
-                    step.replay_optimize()
-                else:
-                    step._optimize()
-                    step._eager_q += 1 if step.tables is not None else 0
+            keep = flag.item() >= comm.world     # the reference syncs here too (loss.detach().cpu(), :199)
+            if accum:
+                step.commit(keep)                # a dropped micro-batch adds nothing; the window's N-th call exchanges and updates
+            elif keep and graphed:
+                step.replay_optimize()
+            elif keep:
+                step._optimize()
+                step._eager_q += 1 if step.tables is not None else 0
+            if keep:
                 losses.append(r["loss"].item())
             else:
                 nonfinite += 1
                 print(f"Warning: Loss is {r['loss'].item()}, skipping this sample! nonfinite_count={nonfinite}")
+        step.flush()      # a window the epoch cut short updates on what it holds, before the validation and the checkpoint
         with torch.no_grad():
             val = torch.stack([-si_sdr(model(x), tgt).mean() for x, tgt in data.batches("val", epoch)]).mean().reshape(1)
         comm.all_reduce_sum(val)

@@ -683,6 +683,18 @@ int fqss_sumsq(const float* g, int64_t n, double* sumsq, fqss_stream_t stream);
 int fqss_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq,
                    float max_norm, float grad_scale, float lr, float beta1, float beta2, float eps,
                    int32_t* step_t, const int32_t* t0, float* gnorm_out, fqss_stream_t stream);
+/* Gradient accumulation: one optimizer update per N micro-batches (pl.Trainer(accumulate_grad_batches=N), speechbrain's
+ * grad_accumulation_factor).  Every micro-batch's backward rewrites the gradient arena g; acc, a second arena of the same layout,
+ * holds the window's sum in between:
+ *   mode 0:  acc  = g        first kept micro-batch of a window (no zeroing pass)
+ *   mode 1:  acc += g
+ *   mode 2:  g   += acc      last micro-batch: the window's sum lands in the gradient arena, where the exchange, fqss_sumsq and
+ *                            fqss_adam_clip (grad_scale = 1 / (world * N)) find it as after any other backward
+ *   mode 3:  g    = acc      the last micro-batch was dropped, or the window ends early
+ * One element-wise pass, element i by thread i, no atomics: each result is the fp32 sum a + b, bit for bit, on every run.
+ * acc and g: non-overlapping, 16-B aligned, n a multiple of 4 (arena slices are multiples of 64 floats from a 64-float-aligned
+ * base); anything else, a null pointer or another mode is refused.  n = 0 is a no-op. (tests/test_gpu_accum.py)             */
+int fqss_grad_accum(float* acc, float* g, int64_t n, int mode, fqss_stream_t stream);
 
 /* =============================================================================================
  * Dual-path models (DPTNet, cfg 3 -- SURVEY.md §8 row a13).  Inside the dual-path blocks tensors are
