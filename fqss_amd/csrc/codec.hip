@@ -14,10 +14,17 @@
 
 namespace fqss {
 
+// torch.clip(v, -128, 127) of process.py:14: a NaN stays NaN (fminf / fmaxf would return the bound, and the 0 / 0 of a silent row
+// would come out as -1 where the reference -- and include/fqss.h -- say NaN)
+__device__ __forceinline__ float split_clip(float v) {
+    v = v < -128.0f ? -128.0f : v;
+    return v > 127.0f ? 127.0f : v;
+}
+
 // process.py:10-14 with threshold=1, n_bits=8, sign=True
 __device__ __forceinline__ float split_q(float x) {
     const float delta = 0.0078125f;
-    return fminf(fmaxf(floorf(x / delta), -128.0f), 127.0f) * delta;
+    return split_clip(floorf(x / delta)) * delta;
 }
 
 // the two channels of one sample under threshold thr (process.py:22-36): k_splitter2 and k_splitter2_rows split through this one body
@@ -77,10 +84,10 @@ __global__ __launch_bounds__(256) void k_splitter2_raw(const float* __restrict__
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / T, t = i - b * T;
         const float v = x[i];
-        const float q0 = fminf(fmaxf(floorf(v / delta), -128.0f), 127.0f) * delta;
+        const float q0 = split_clip(floorf(v / delta)) * delta;
         const float r = ((2.0f * (v - q0)) * thr) / delta - thr;      // process.py:35 op order
         out[(b * 2 + 0) * T + t] = q0;
-        out[(b * 2 + 1) * T + t] = fminf(fmaxf(floorf(r / delta), -128.0f), 127.0f) * delta;
+        out[(b * 2 + 1) * T + t] = split_clip(floorf(r / delta)) * delta;
     }
 }
 

@@ -520,9 +520,13 @@ int fqss_mul_bcast_bwd(const float* gz, const float* mask, const float* feat, fl
 }
 
 // ------------------------------------------------------------------------------------------------ splitter, framing conv, overlap-add
+static inline float split_clip(float v) {   // torch.clip(v, -128, 127): a NaN (the 0 / 0 of a silent row) stays NaN
+    v = v < -128.0f ? -128.0f : v;
+    return v > 127.0f ? 127.0f : v;
+}
 static inline float split_q(float x) {      // process.py:10-14 with threshold = 1, n_bits = 8, sign = True
     const float delta = 0.0078125f;
-    return fminf(fmaxf(floorf(x / delta), -128.0f), 127.0f) * delta;
+    return split_clip(floorf(x / delta)) * delta;
 }
 static inline void split2(float x, float thr, float& msb, float& lsb) {      // process.py:22-36
     const float delta = 0.0078125f;

@@ -567,39 +567,63 @@ int fqss_mul_bcast_bwd(const float* gz, const float* mask, const float* feat, fl
  *           ResidualErrorBlock (qat_layers.py:1028-1039, 1189-1192); F.conv_transpose1d of
  *           ConvTr1dDecoderQ / ResidualErrorBlock (:1330-1341, 1194-1202) + autograd
  * ------------------------------------------------------------------------------------------- */
-/* x [B][T] -> out [B][2][T]; obs_ws must hold the global min/max of x (fqss_minmax) */
+/* Write extents of this family (tests/test_gpu_codec_kernels.py holds a guard behind each): every entry writes its live elements and
+ * nothing else, with ONE exception -- fqss_frames_conv_fwd / _add_fwd in the four-frames-per-lane form store whole float4s, so columns
+ * [M, (M + 3) & ~3) of a z row may be written (with unspecified values, NaN included) and nothing beyond; that form is taken only when
+ * ld_z >= (M + 3) & ~3.  The splitters write [B][2][T]; both decoder forms exactly [0, T) of every out row; the weight gradients exactly
+ * the C x K (x Ci) elements of gw they accumulate into.  Operand row padding (columns [M, ld)) is never a value of a result: it may
+ * hold anything, NaN included.  N = 0 / M = 0 (B = 0 / T = 0 for fqss_splitter2, _raw) return FQSS_OK and write nothing.
+ *
+ * x [B][T] -> out [B][2][T]; obs_ws must hold the global min/max of x (fqss_minmax).  The clamp is torch.clip's: a NaN stays NaN, so
+ * an all-zero x (0 / 0) comes out NaN as in the reference. */
 int fqss_splitter2(const float* x, float* out, int B, int64_t T, const uint32_t* obs_ws,
                    fqss_stream_t stream);
 /* the per-item form: x [B][T] -> out [B][2][T] with one threshold per row, thr_b = max|x[b][:]| (what the reference computes when it
- * calls the model on one chunk at a time); row_max: B words zeroed by the caller.  A silent row is NaN in that row only.  */
+ * calls the model on one chunk at a time); row_max: B words zeroed by the caller, left holding the bit images of max|x[b][:]|.  A silent
+ * row is NaN in that row only (0 / 0, as process.preprocess gives for that chunk alone); the other rows are unaffected.  */
 int fqss_splitter2_rows(const float* x, float* out, int B, int64_t T, uint32_t* row_max, fqss_stream_t stream);
 /* the same with normalize=False (process.py:26-27: threshold = max|x|, x is not divided by it; HTDemucs time branch) */
 int fqss_splitter2_raw(const float* x, float* out, int B, int64_t T, const uint32_t* obs_ws, fqss_stream_t stream);
-/* z[n][co][m] = sum_{ci,k} w[co][ci][k] * x[n][ci][m*stride+k]   (x: [N][Ci][T] dense)        */
+/* z[n][co][m] = sum_{ci,k} w[co][ci][k] * x[n][ci][m*stride+k]   (x: [N][Ci][T] dense; T may exceed (M-1)*stride + K: a tail no frame
+ * covers).  One (ci, k)-ordered fmaf chain per element in either form, so the forms are bit-identical.  Writes columns [0, M) of each
+ * z row; with (K, stride) in {(16, 8), (32, 16)}, Ci in {1, 2}, x and z 16-B aligned, T % 4 == 0, ld_z % 4 == 0 and
+ * ld_z >= (M + 3) & ~3 (and the addend alike) whole float4s: columns [0, (M + 3) & ~3), see above.  N <= 65535. */
 int fqss_frames_conv_fwd(const float* x, const float* w, float* z, int N, int Ci, int Co,
                          int64_t T, int K, int stride, int M, int64_t ld_z, fqss_stream_t stream);
 /* the same + add[n][co][m]: as the decoder's input gradient it sums in the gradient that the decoder input receives from its other
  * consumer (ResidualErrorBlock's Y - Y_q, qat_layers.py:1193), which autograd would add in a pass of its own */
 int fqss_frames_conv_add_fwd(const float* x, const float* w, const float* add, int64_t ld_add, float* z, int N, int Ci,
                              int Co, int64_t T, int K, int stride, int M, int64_t ld_z, fqss_stream_t stream);
-/* out[n][t] = sum_{c} sum_{m*stride+k=t} x[n][c][m] * w[c][k]   (w: [C][K], out: [N][T] dense) */
+/* out[n][t] = sum_{c} sum_{m*stride+k=t} x[n][c][m] * w[c][k]   (w: [C][K], out: [N][T] dense, T == (M-1)*stride + K).  Writes exactly
+ * [0, T) of every out row.  Two forms that sum the channels in different orders: the matrix-core form -- (K, stride) = (16, 8), operand
+ * rows 16-B aligned with ld_x % 4 == 0 (codes: ld_x % 16 == 0) and ld_x >= (M + 3) & ~3; the masking form asks the same of feat / ld_f --
+ * gives each wave a contiguous block of channels, the generic form every fourth channel.  Each is within rounding of the exact sum; they
+ * are bit-identical to each other only where no rounding occurs (C = 1, integers below 2^24). */
 int fqss_ola_convtr_fwd(const float* x, const float* w, float* out, int N, int C, int M,
                         int64_t ld_x, int K, int stride, int64_t T, fqss_stream_t stream);
 /* the same on an operand that arrives as the u8 codes of a per-tensor quantizer (de-quantised on load: the decoder input of the
  * student -- MulQ's output, the residual block's quantized error -- never exists in fp32; qat_layers.py:1305-1361, 1105-1202);
- * bit-identical to fqss_decode + fqss_ola_convtr_fwd.  Code rows 16-B aligned, (K, stride) in {(16, 8), (32, 16)} */
+ * bit-identical to fqss_decode + fqss_ola_convtr_fwd WHEN BOTH CALLS TAKE THE SAME FORM (above): at (16, 8) that is code rows with
+ * ld_x % 16 == 0 against decoded rows with ld % 4 == 0, both 16-B aligned and >= (M + 3) & ~3 -- or neither; always at (32, 16) and
+ * (2, 1), where only the generic form exists.  With the codes in one form and the decoded operand in the other the two results differ
+ * by summation order (measured: 9 of 10 real-valued cases differ, within 7.5e-7 of the rms).  (K, stride) in {(2, 1), (16, 8), (32, 16)} */
 int fqss_ola_convtr_fwd_q(const uint8_t* xc, const float* qmin, const float* qmax, const float* w, float* out, int N,
                           int C, int M, int64_t ld_x, int K, int stride, int64_t T, fqss_stream_t stream);
 /* the float model's masking product formed on load: x[n][c][m] = mask[n][c][m] * feat[n / NS][c][m] (convtasnetq.py:277-279 of the
- * float teacher: `masked = mask * feats` then the decoder); bit-identical to fqss_mul_bcast_fwd + fqss_ola_convtr_fwd */
+ * float teacher: `masked = mask * feats` then the decoder); bit-identical to fqss_mul_bcast_fwd + fqss_ola_convtr_fwd under the
+ * same condition: both calls in the same form (here mask AND feat rows decide the fused call's form, the product's rows the chain's).
+ * N % NS == 0, ld_f >= M */
 int fqss_ola_convtr_mul_fwd(const float* mask, const float* feat, const float* w, float* out, int N, int NS, int C, int M,
                             int64_t ld_m, int64_t ld_f, int K, int stride, int64_t T, fqss_stream_t stream);
-/* gw[c][ci][k] += sum_{n,m} a[n][c][m] * x[n][ci][m*stride+k]    (a: [N][C][M] ld_a; x dense) */
+/* gw[c][ci][k] += sum_{n,m} a[n][c][m] * x[n][ci][m*stride+k]    (a: [N][C][M] ld_a; x dense; gw [C][Ci][K] dense).  Any layout of a
+ * and x, any (K, stride); adds into exactly the C x Ci x K elements of gw (fp32 atomics over the split of the frame range). */
 int fqss_frames_wgrad(const float* a, const float* x, float* gw, int N, int C, int Ci, int M,
                       int64_t ld_a, int64_t T, int K, int stride, fqss_stream_t stream);
 /* the Ci = 1 case (residual encoder Conv1d(1, C, K, stride); the mono decoder's weight gradient with a = its input, sig = dL/dout)
  * as a dedicated fp32-MFMA kernel: gw[c][k] += sum_{n,m} a[n][c][m] * sig[n][m*stride + k]; (K, stride) in {(16, 8), (32, 16)}, rows
- * of a 16-B aligned (FQSS_EINVAL otherwise: callers fall back to fqss_frames_wgrad).  _q: a as u8 codes (qmin, qmax). */
+ * of a 16-B aligned -- fp32: ld_a % 4 == 0, codes: ld_a % 16 == 0 -- and N <= 65535 (FQSS_EINVAL otherwise, gw untouched: callers
+ * fall back to fqss_frames_wgrad).  _q: a as u8 codes (qmin, qmax).  Adds into exactly C x K elements: rows of K floats, ld_gw apart
+ * for _wgrad1s (the other columns of a gw row are not touched). */
 int fqss_frames_wgrad1(const float* a, const float* sig, float* gw, int N, int C, int M, int64_t ld_a, int64_t T, int K,
                        int stride, fqss_stream_t stream);
 /* one input channel of a multi-channel framing conv: sig = x + ci * T (signals sig_ns = Ci * T apart), gw = gw0 + ci * K (rows ld_gw = Ci * K apart) */
