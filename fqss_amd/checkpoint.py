@@ -9,7 +9,11 @@ when asked to resume (`resume: <path> | auto` in the YAML, `--resume [PATH]` on 
 The file is `{"format": "fqss-train-v1", "step", "trainer", "teacher", "rng"}`: tensors and plain Python values only, so
 `torch.load(..., weights_only=True)` reads it -- a checkpoint is never a reason to unpickle code.  It is written to a temporary file in
 the same directory and moved into place with `os.replace`: a process killed while writing leaves the previous file as it was.
-File order needs no entry: `loader.epoch_batches(seed, epoch)` derives it from the epoch number."""
+A run on plain Adam without weight decay and without EMA copies writes exactly these keys.  Any other run's `step` entry also says
+which optimizer its moments belong to (`optim`: kind, weight_decay, momentum, nesterov, per-parameter decays) and, where the step
+keeps EMA copies of the model, carries them (`ema`: kinds, decays, counts, the copies); `KDTrainStep.load_state_dict` refuses a file
+of another optimizer kind or another EMA list with a ValueError naming both.
+File order needs no entry:`loader.epoch_batches(seed, epoch)` derives it from the epoch number."""
 import os
 import random
 

@@ -970,6 +970,87 @@ int fqss_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, cons
     if (gnorm_out) *gnorm_out = (float)norm;
     return FQSS_OK;
 }
+// the optimizer family on the same clip and clocks (fqss.h: fqss_optim_clip; the op sequence of csrc/train_ops.hip k_optim_clip)
+int fqss_optim_clip(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq, float max_norm, float grad_scale, float lr,
+                    float beta1, float beta2, float eps, int32_t* step_t, const int32_t* t0, float* gnorm_out, int kind, float weight_decay,
+                    const float* wd_slot, float momentum, int nesterov, fqss_stream_t) {
+    REQUIRE(kind == FQSS_OPT_ADAM || kind == FQSS_OPT_ADAMW || kind == FQSS_OPT_SGD, "kind: FQSS_OPT_ADAM, FQSS_OPT_ADAMW or FQSS_OPT_SGD");
+    REQUIRE(p && g && sumsq && step_t && n >= 0, "bad args");
+    REQUIRE(weight_decay >= 0.0f, "weight_decay must be >= 0");
+    REQUIRE(momentum >= 0.0f && momentum < 1.0f, "momentum must lie in [0, 1)");
+    REQUIRE(nesterov == 0 || (nesterov == 1 && momentum > 0.0f), "nesterov: 0 or 1, and 1 needs a momentum > 0");
+    REQUIRE(kind == FQSS_OPT_SGD ? (m || momentum == 0.0f) : (m && v), "null moment buffer");
+    REQUIRE(!wd_slot || n % 64 == 0, "a decay table needs n to be a multiple of 64 floats");
+    const bool adam = kind != FQSS_OPT_SGD, use_buf = !adam && momentum != 0.0f;
+    const float mu = momentum;
+    const int tg = *step_t + 1;
+    const double norm = sqrt(*sumsq) * (double)grad_scale;
+    double coef = (double)max_norm / (norm + 1e-6);
+    if (coef > 1.0) coef = 1.0;
+    if (max_norm <= 0.0f) coef = 1.0;
+    const float gs = (float)((double)grad_scale * coef);
+    const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
+    int cached = -1;
+    float step_size = 0.0f, bc2_sqrt = 1.0f;
+    for (int64_t i = 0; i < n; ++i) {
+        const int t = tg - (t0 ? t0[i] : 0);
+        if (t <= 0) continue;
+        const float wd = wd_slot ? wd_slot[i >> 6] : weight_decay;
+        float gi = g[i] * gs, pi = p[i];
+        if (kind == FQSS_OPT_ADAMW) {
+            if (wd != 0.0f) pi = pi * (float)(1.0 - (double)lr * (double)wd);
+        } else if (wd != 0.0f) {
+            gi = fmaf(wd, pi, gi);      // add(alpha=): one rounding in torch's kernels
+        }
+        if (adam) {
+            if (t != cached) {
+                const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+                step_size = (float)((double)lr / bc1);
+                bc2_sqrt = (float)sqrt(bc2);
+                cached = t;
+            }
+            const float mi = m[i] + omb1 * (gi - m[i]);
+            const float vi = v[i] * beta2 + (omb2 * gi) * gi;
+            m[i] = mi;
+            v[i] = vi;
+            const float denom = sqrtf(vi) / bc2_sqrt + eps;
+            p[i] = pi + ((-step_size) * mi) / denom;
+        } else {
+            float d = gi;
+            if (use_buf) {
+                const float buf = (t == 1) ? gi : m[i] * mu + gi;
+                m[i] = buf;
+                d = nesterov ? fmaf(mu, buf, gi) : buf;
+            }
+            p[i] = fmaf(-lr, d, pi);
+        }
+    }
+    *step_t = tg;
+    if (gnorm_out) *gnorm_out = (float)norm;
+    return FQSS_OK;
+}
+// EMA copies (fqss.h: fqss_ema_update / fqss_ema_update_dev; `count` is host memory on this backend)
+static void ema_apply(float* ema, const float* p, int64_t n, double wd) {
+    const float w = (float)wd, omw = (float)(1.0 - wd);
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) ema[i] = ema[i] * omw + w * p[i];
+}
+int fqss_ema_update(float* ema, const float* p, int64_t n, float w, fqss_stream_t) {
+    REQUIRE(ema && p && n >= 0, "null pointer");
+    REQUIRE(w >= 0.0f && w <= 1.0f, "w must lie in [0, 1]");
+    REQUIRE(ema + n <= p || p + n <= ema, "ema and p overlap");
+    ema_apply(ema, p, n, (double)w);
+    return FQSS_OK;
+}
+int fqss_ema_update_dev(float* ema, const float* p, int64_t n, double decay, double* count, fqss_stream_t) {
+    REQUIRE(ema && p && count && n >= 0, "null pointer");
+    REQUIRE(decay >= 0.0 && decay < 1.0, "decay must lie in [0, 1)");
+    REQUIRE(ema + n <= p || p + n <= ema, "ema and p overlap");
+    if (n == 0) return FQSS_OK;
+    *count = *count * decay + 1.0;
+    ema_apply(ema, p, n, 1.0 / *count);
+    return FQSS_OK;
+}
 // gradient accumulation: the moves between the gradient arena and the window's accumulator (same contract as the HIP entry point)
 int fqss_grad_accum(float* acc, float* g, int64_t n, int mode, fqss_stream_t) {
     REQUIRE(acc && g, "null pointer");

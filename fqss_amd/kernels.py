@@ -1326,7 +1326,39 @@ def adam_clip(p, g, m, v, sumsq_acc, step_t, gnorm_out, max_norm, grad_scale, lr
               _stream())
 
 
-ACC_SET, ACC_ADD, ACC_FINISH, ACC_TAKE = 0, 1, 2, 3      # fqss_grad_accum modes: acc = g | acc += g | g += acc | g = acc
+OPT_KINDS = {"adam": _lib.CONSTANTS["FQSS_OPT_ADAM"], "adamw": _lib.CONSTANTS["FQSS_OPT_ADAMW"], "sgd": _lib.CONSTANTS["FQSS_OPT_SGD"]}
+
+
+def optim_clip(p, g, m, v, sumsq_acc, step_t, gnorm_out, max_norm, grad_scale, lr, beta1=0.9, beta2=0.999, eps=1e-8, t0=None,
+               kind="adam", weight_decay=0.0, wd_slot=None, momentum=0.0, nesterov=False):
+    """adam_clip's clip and clocks with torch.optim.Adam(weight_decay) / AdamW / SGD(momentum, nesterov) behind them (fqss.h:
+    fqss_optim_clip).  kind: a name of OPT_KINDS or the integer itself; wd_slot: one fp32 decay per 64 floats of p (overrides
+    weight_decay); SGD keeps its momentum buffer in m and does not read v"""
+    if wd_slot is not None and (wd_slot.dtype != torch.float32 or not wd_slot.is_contiguous() or wd_slot.numel() * 64 != p.numel()):
+        raise _lib.FqssError(f"optim_clip: wd_slot must be {p.numel()} / 64 contiguous fp32 values, got {tuple(wd_slot.shape)} {wd_slot.dtype}")
+    _lib.call("fqss_optim_clip", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(sumsq_acc), float(max_norm), float(grad_scale), float(lr),
+              float(beta1), float(beta2), float(eps), _p(step_t), _p(t0), _p(gnorm_out), int(OPT_KINDS.get(kind, kind)),
+              float(weight_decay), _p(wd_slot), float(momentum), int(bool(nesterov)), _stream())
+
+
+def ema_update(ema, p, w=None, decay=None, count=None):
+    """ema = ema * (1 - w) + w * p over two flat fp32 buffers (demucs' ModelEMA.update).  Either the host's `w`, or `decay` with the
+    one-double tensor `count` that lives where the backend computes: the call advances count = count * decay + 1 and uses
+    w = 1 / count, so a captured launch moves on with every replay"""
+    _need_gpu(ema, p)
+    if ema.numel() != p.numel() or not (ema.is_contiguous() and p.is_contiguous()):
+        raise _lib.FqssError(f"ema_update: ema ({ema.numel()}) and p ({p.numel()}) must be contiguous and of one size")
+    if (w is None) == (count is None):
+        raise _lib.FqssError("ema_update: give either w or (decay, count)")
+    if count is None:
+        _lib.call("fqss_ema_update", _p(ema), _p(p), p.numel(), float(w), _stream())
+    else:
+        if count.dtype != torch.float64 or count.numel() != 1 or count.is_cuda != p.is_cuda:
+            raise _lib.FqssError("ema_update: count is one float64 value beside the buffers")
+        _lib.call("fqss_ema_update_dev", _p(ema), _p(p), p.numel(), float(decay), _p(count), _stream())
+
+
+ACC_SET, ACC_ADD, ACC_FINISH, ACC_TAKE = 0, 1, 2, 3     # fqss_grad_accum modes: acc = g | acc += g | g += acc | g = acc
 
 
 def grad_accum(acc, g, mode):

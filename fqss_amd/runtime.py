@@ -129,6 +129,45 @@ class ParamArena:
         K.adam_clip(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.sumsq, self.step_t, self.gnorm,
                     max_norm, grad_scale, lr, betas[0], betas[1], eps, t0=self.t0)
 
+    def decay_table(self, param_decay, weight_decay=0.0):
+        """param_decay {parameter name: its own weight decay} over the scalar `weight_decay` -> the per-slot table of fqss_optim_clip
+        (one fp32 value per 64 floats of the arena; slices start and end on slot boundaries), or None when no parameter departs
+        from the scalar.  A name the arena does not hold raises."""
+        if not param_decay:
+            return None
+        names = self.layout()["names"]
+        unknown = sorted(set(param_decay) - set(names))
+        if unknown:
+            raise ValueError(f"param_decay names parameters the arena does not hold: {unknown[:3]}")
+        for n, wd in param_decay.items():
+            if not float(wd) >= 0.0:
+                raise ValueError(f"param_decay[{n!r}] must be >= 0, got {wd!r}")
+        if all(float(wd) == float(weight_decay) for wd in param_decay.values()):
+            return None
+        assert self.numel % 64 == 0 and all(o % 64 == 0 for o in self.offsets), "the decay table needs 64-float slots"
+        table = torch.full((self.numel // 64,), float(weight_decay), dtype=torch.float32)
+        for n, p, o in zip(names, self.params, self.offsets):
+            if n in param_decay:
+                table[o // 64:(o + p.numel() + 63) // 64] = float(param_decay[n])
+        return table.to(self.flat_p.device)
+
+    def clip_optim_step(self, lr, max_norm=5.0, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, activate=True, kind="adam",
+                        weight_decay=0.0, momentum=0.0, nesterov=False, wd_slot=None):
+        """clip + update with any optimizer of the family.  The default configuration -- adam, no decay anywhere, no table -- IS
+        clip_adam_step: the same two launches (fqss_sumsq, fqss_adam_clip), so the default run's graphs and bench.py's path do not
+        change; everything else goes to fqss_optim_clip.  SGD keeps its momentum buffer in exp_avg."""
+        if kind not in K.OPT_KINDS:
+            raise ValueError(f"unknown optimizer {kind!r}: one of {sorted(K.OPT_KINDS)}")
+        if kind == "adam" and float(weight_decay) == 0.0 and wd_slot is None:
+            return self.clip_adam_step(lr, max_norm, grad_scale, betas, eps, activate)
+        if activate:
+            self._activate_touched()
+        self.sumsq.zero_()
+        K.sumsq(self.flat_g, self.sumsq)
+        K.optim_clip(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.sumsq, self.step_t, self.gnorm, max_norm,
+                     grad_scale, lr, betas[0], betas[1], eps, t0=self.t0, kind=kind, weight_decay=weight_decay, wd_slot=wd_slot,
+                     momentum=momentum, nesterov=nesterov)
+
 
 TEACHER_STREAM = True    # False: the teacher forward on the step's own stream (tests and tools/stress_step.py patch it)
 
@@ -452,7 +491,8 @@ class KDTrainStep:
 
     def __init__(self, model, fmodel, kd_lambda=0.1, lr=1e-3, clip=5.0, comm=None, loss="sisdr_pit", source_weights=None,
                  batched_quantizers=True, fast=True, coded=True, buckets=None, sync_observer_ranges=True,
-                 betas=(0.9, 0.999), loss_threshold=None, teacher_ahead=False, accumulate=1):
+                 betas=(0.9, 0.999), loss_threshold=None, teacher_ahead=False, accumulate=1, optimizer="adam", weight_decay=0.0,
+                 momentum=0.0, nesterov=False, param_decay=None, ema_decays=(), ema_epoch_decays=()):
         """loss: "sisdr_pit" = the asteroid KD loss (mysystem.py:124-151); "sisdr_pit_per_sample" = the speechbrain env's form of it
         (speechbrain_librimix_trainer.py:99-115, 141-149: log per sample, mean over the samples whose loss exceeds `loss_threshold`;
         per-GPU batch 1 or 2, see fqss_kd_loss_per_sample); "l1_sdr" = the htdemucs solver's
@@ -476,7 +516,30 @@ class KDTrainStep:
         1 / (world * N) -- the data-parallel contract in time instead of space.  Each call runs one micro-batch; the N-th also
         exchanges and updates (`pending`: micro-batches of the open window).  micro_batch() / commit(keep) is the same in two
         halves for trainers that may drop a micro-batch, flush() ends a window early (end of an epoch).  1: the step as it always
-        was -- no accumulator, the same launches, the one-graph replay."""
+        was -- no accumulator, the same launches, the one-graph replay.
+        optimizer: "adam" | "adamw" | "sgd" with weight_decay, momentum / nesterov (sgd) -- torch.optim.Adam(weight_decay=) /
+        AdamW / SGD(momentum, nesterov) on the clip and the per-parameter clocks of the fused update (fqss.h: fqss_optim_clip).
+        param_decay {parameter name: decay}: parameters with a decay of their own (the reference's make_optim_group).  adam with no
+        decay anywhere is the step as it always was: fqss_adam_clip, the same launches.
+        ema_decays / ema_epoch_decays: exponential moving averages of the model (demucs' ModelEMA, unbias=True), one flat copy of
+        the arena per decay.  The batch-level copies (ema_decays, numbered first) are updated by every optimizer update, inside the
+        captured optimize graph; the epoch-level ones by ema_epoch_update().  ema_state(k) / ema_swap(k) read and borrow copy k."""
+        if optimizer not in K.OPT_KINDS:
+            raise ValueError(f"unknown optimizer {optimizer!r}: one of {sorted(K.OPT_KINDS)}")
+        if not float(weight_decay) >= 0.0:
+            raise ValueError(f"weight_decay must be >= 0, got {weight_decay!r}")
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError(f"momentum must lie in [0, 1), got {momentum!r}")
+        if nesterov and not float(momentum) > 0.0:
+            raise ValueError("nesterov needs a momentum > 0")
+        if optimizer != "sgd" and (float(momentum) != 0.0 or nesterov):
+            raise ValueError(f"momentum / nesterov belong to sgd; {optimizer}'s first-moment decay is betas[0]")
+        self.optim = {"kind": optimizer, "weight_decay": float(weight_decay), "momentum": float(momentum), "nesterov": bool(nesterov),
+                      "param_decay": {str(n): float(w) for n, w in (param_decay or {}).items()}}
+        self.ema_kinds = ["batch"] * len(tuple(ema_decays)) + ["epoch"] * len(tuple(ema_epoch_decays))
+        self.ema_decays = [float(d) for d in tuple(ema_decays) + tuple(ema_epoch_decays)]
+        if any(not 0.0 <= d < 1.0 for d in self.ema_decays):
+            raise ValueError(f"EMA decays must lie in [0, 1), got {self.ema_decays}")
         try:
             accumulate = operator.index(accumulate)
         except TypeError:
@@ -535,6 +598,15 @@ class KDTrainStep:
         self.arena = ParamArena(params, accumulator=accumulate > 1)
         name_of = {id(p): n for n, p in model.named_parameters()}
         self.arena.names = [name_of[id(p)] for p in self.arena.params]       # the layout a stored arena is checked against
+        self._wd_slot = self.arena.decay_table(self.optim["param_decay"], self.optim["weight_decay"])
+        # EMA copies: the arena's layout once more per decay, the count of the unbiased form beside them on the device, and the few
+        # float32 state_dict entries the arena does not hold (buffers, frozen parameters).  A copy starts as the model (ModelEMA)
+        self.ema = [self.arena.flat_p.clone() for _ in self.ema_decays]
+        self.ema_count = torch.zeros(len(self.ema_decays), dtype=torch.float64, device=self.arena.flat_p.device)
+        held = {id(p) for p in self.arena.params}
+        self._ema_outside = [(n, t) for n, t in model.state_dict(keep_vars=True).items()
+                             if t.dtype == torch.float32 and id(t) not in held] if self.ema_decays else []
+        self.ema_extra = [{n: t.detach().clone() for n, t in self._ema_outside} for _ in self.ema_decays]
         # FQSS_DETERMINISTIC=1: bit-reproducible gradients (kernels.DetMode; no effect on the values beyond fp32 summation order)
         self.det = None
         if os.environ.get("FQSS_DETERMINISTIC", "0") == "1" and not self.cpu:
@@ -586,6 +658,30 @@ class KDTrainStep:
         them, and for good where that synchronisation was declined (sync_observer_ranges=False)"""
         return self._world() > 1 and (not self._sync_ranges or not self._ranges_synced)
 
+    def _optim_block(self):
+        """the checkpoint's `optim` entry: None for the default configuration (adam, no decay anywhere), whose files keep the keys they
+        always had"""
+        o = self.optim
+        if o["kind"] == "adam" and o["weight_decay"] == 0.0 and self._wd_slot is None:
+            return None
+        return {"kind": o["kind"], "weight_decay": o["weight_decay"], "momentum": o["momentum"], "nesterov": o["nesterov"],
+                "param_decay": dict(o["param_decay"]) if self._wd_slot is not None else {}}
+
+    def _check_stored_optim(self, sd):
+        """the moments of one optimizer mean nothing to another (SGD's buffer lives where Adam's first moment does), and an EMA copy
+        belongs to its decay: a file written under another kind or another EMA list is refused, naming both"""
+        default = {"kind": "adam", "weight_decay": 0.0, "momentum": 0.0, "nesterov": False, "param_decay": {}}
+        mine, theirs = self._optim_block() or default, sd.get("optim") or default
+        for key in ("kind", "momentum", "nesterov"):
+            if mine[key] != theirs[key]:
+                raise ValueError(f"KDTrainStep.load_state_dict: the file was written by optimizer {theirs['kind']!r} (momentum "
+                                 f"{theirs['momentum']}, nesterov {theirs['nesterov']}), this step runs {mine['kind']!r} (momentum "
+                                 f"{mine['momentum']}, nesterov {mine['nesterov']}); their state does not carry over")
+        ema = sd.get("ema") or {"kinds": [], "decays": []}
+        if list(ema["kinds"]) != self.ema_kinds or [float(d) for d in ema["decays"]] != self.ema_decays:
+            raise ValueError(f"KDTrainStep.load_state_dict: the file holds the EMA copies {list(zip(ema['kinds'], ema['decays']))}, "
+                             f"this step keeps {list(zip(self.ema_kinds, self.ema_decays))}")
+
     def state_dict(self):
         """Everything that says where this QAT run stands, as host tensors and plain Python values: the arena (parameters, Adam moments
         and clocks), the host state of every quantizer by module path (activation: n_iter, observer_mode, sign; weight: observer_mode),
@@ -594,7 +690,8 @@ class KDTrainStep:
         int32 words: the bits of min and max, n_iter) -- which makes this a COLLECTIVE call at world > 1: every rank calls it, every rank
         gets the same `rank_ranges`.  Not stored: QuantTables, graphs and look-ahead results (rebuilt by the next eager quantizing step
         and maybe_capture), and the integer shadows of FQSS_DETERMINISTIC=1, which are empty between steps.  Nor the gradient
-        accumulator: a window with micro-batches pending is refused (the trainers flush() before they write a checkpoint)."""
+        accumulator: a window with micro-batches pending is refused (the trainers flush() before they write a checkpoint).
+        Only a step that departs from plain Adam without decay adds `optim`; only a step with EMA copies adds `ema`."""
         if self.pending or self._open:
             raise RuntimeError(f"KDTrainStep.state_dict: {self.pending + int(self._open)} micro-batch(es) of an accumulation window are "
                                "pending; call flush() first (their gradients are not part of the stored state)")
@@ -606,7 +703,13 @@ class KDTrainStep:
             mine = torch.stack([torch.cat([m.min_range.data.reshape(1), m.max_range.data.reshape(1)]).view(torch.int32) for _, m in aqs])
             mine = torch.cat([mine.cpu(), torch.tensor([[int(m.n_iter)] for _, m in aqs], dtype=torch.int32)], 1)
             rank_ranges = torch.stack(self.comm.all_gather(mine))
-        return {"arena": self.arena.state_dict(),
+        more = {}
+        if self._optim_block() is not None:
+            more["optim"] = self._optim_block()
+        if self.ema_decays:
+            more["ema"] = {"kinds": list(self.ema_kinds), "decays": list(self.ema_decays), "count": c(self.ema_count),
+                           "copies": [c(e) for e in self.ema], "extra": [{n: c(t) for n, t in x.items()} for x in self.ema_extra]}
+        return {**more, "arena": self.arena.state_dict(),
                 "act_quantizers": {n: {"n_iter": int(m.n_iter), "observer_mode": bool(m.observer_mode), "sign": bool(m.sign)} for n, m in aqs},
                 "weight_quantizers": {n: {"observer_mode": bool(m.observer_mode)} for n, m in wqs},
                 "ranges_synced": bool(self._ranges_synced), "lr": float(self.lr), "world": int(self._world()),
@@ -619,6 +722,7 @@ class KDTrainStep:
         ranks' ranges differed resumes at the SAME world size only, each rank taking its own ranges and n_iter; any other file serves
         any world size and any `buckets` (the arena is loaded by parameter name, whatever order the gradient buckets gave it).  Tables, graphs and look-ahead state are dropped: the next step runs eagerly, rebuilds the QuantTables (and
         starts no Adam clock again -- t0 is restored), and maybe_capture records the graphs afresh."""
+        self._check_stored_optim(sd)
         aqs, wqs = self._quantizers()
         for kind, have, want in (("activation", aqs, sd["act_quantizers"]), ("weight", wqs, sd["weight_quantizers"])):
             if [n for n, _ in have] != list(want):
@@ -635,6 +739,21 @@ class KDTrainStep:
             if bad or (kind == "buffers" and set(have) != set(want)):
                 raise ValueError(f"KDTrainStep.load_state_dict: the stored {kind} are not this model's (e.g. {(bad or sorted(set(have) ^ set(want)))[:3]})")
         self.arena.load_state_dict(sd["arena"])
+        if self.ema_decays:
+            # the copies share the arena's layout: one written under another parameter order is gathered by name, like the arena
+            mine, theirs = self.arena.layout(), sd["arena"]["layout"]
+            at = dict(zip(theirs["names"], theirs["offsets"]))
+            with torch.no_grad():
+                for k, src in enumerate(sd["ema"]["copies"]):
+                    if mine != theirs:
+                        dst = torch.zeros(self.arena.numel, dtype=src.dtype)
+                        for n, o, m in zip(mine["names"], mine["offsets"], mine["numel"]):
+                            dst[o:o + m] = src[at[n]:at[n] + m]
+                        src = dst
+                    self.ema[k].copy_(src)
+                    for n, t in sd["ema"]["extra"][k].items():
+                        self.ema_extra[k][n].copy_(t)
+                self.ema_count.copy_(sd["ema"]["count"])
         with torch.no_grad():
             for n, t in sd["buffers"].items():
                 buffers[n].copy_(t)
@@ -850,7 +969,69 @@ class KDTrainStep:
         if activate:
             self.arena._activate_touched()
         # the update takes the average of the gradients it is given: over the ranks and over the micro-batches of a window
-        self.arena.clip_adam_step(self.lr, self.clip, 1.0 / (self._world() * self.accumulate), betas=self.betas, activate=False)
+        o = self.optim
+        self.arena.clip_optim_step(self.lr, self.clip, 1.0 / (self._world() * self.accumulate), betas=self.betas, activate=False,
+                                   kind=o["kind"], weight_decay=o["weight_decay"], momentum=o["momentum"], nesterov=o["nesterov"],
+                                   wd_slot=self._wd_slot)
+        # the batch-level EMA copies follow every update (solver.py:425-427), every rank computing the same average
+        for k, kind in enumerate(self.ema_kinds):
+            if kind == "batch":
+                self._ema_update(k)
+
+    # ---- EMA copies of the model (demucs' ModelEMA; fqss.h: fqss_ema_update) --------------------------------------------------
+    def _ema_update(self, k):
+        """one launch over the whole arena; w = 1 / count comes from the device-resident count, which the launch advances -- so the
+        update may sit inside a captured graph.  The float32 state_dict entries outside the arena follow with torch ops on the same
+        device word"""
+        count = self.ema_count[k:k + 1]
+        K.ema_update(self.ema[k], self.arena.flat_p, decay=self.ema_decays[k], count=count)
+        if self._ema_outside:
+            w = (1.0 / count).to(torch.float32)
+            for n, t in self._ema_outside:
+                self.ema_extra[k][n].mul_(1.0 - w).add_(t.detach() * w)
+
+    def ema_epoch_update(self):
+        """the epoch-level copies, once per epoch after training (solver.py:438-440)"""
+        for k, kind in enumerate(self.ema_kinds):
+            if kind == "epoch":
+                self._ema_update(k)
+
+    def ema_state(self, k):
+        """copy k shaped like model.state_dict(): views of the copy for the arena's parameters, the copy's own tensors for the other
+        float32 entries, the model's entries for whatever is not float32 (ModelEMA keeps float32 entries only)"""
+        at = {id(p): (o, p) for p, o in zip(self.arena.params, self.arena.offsets)}
+        out = {}
+        for n, t in self.model.state_dict(keep_vars=True).items():
+            if id(t) in at:
+                o, p = at[id(t)]
+                out[n] = self.ema[k][o:o + p.numel()].view(p.shape)
+            elif n in self.ema_extra[k]:
+                out[n] = self.ema_extra[k][n]
+            else:
+                out[n] = t.detach()
+        return out
+
+    def ema_swap(self, k):
+        """context manager: the model computes with copy k inside, with its own parameters again after.  The exchange is device to
+        device INTO the arena's buffer, so p.data keeps its address and graphs and device tables stay valid"""
+        import contextlib
+
+        def exchange():
+            with torch.no_grad():
+                pairs = [(self.arena.flat_p, self.ema[k])] + [(t.detach(), self.ema_extra[k][n]) for n, t in self._ema_outside]
+                for a, b in pairs:
+                    tmp = a.clone()
+                    a.copy_(b)
+                    b.copy_(tmp)
+
+        @contextlib.contextmanager
+        def swapped():
+            exchange()
+            try:
+                yield self
+            finally:
+                exchange()
+        return swapped()
 
     def _maybe_sync_ranges(self):
         """world > 1: once, when the observer phase is over, every rank takes the mean of the observed activation ranges"""

@@ -137,17 +137,20 @@ def _train(yml_path, device, resume=None):
                 yaml.safe_dump(blk, out)
 
     opt = training_cfg.get("optim", {})
-    # make_optimizer(**training_cfg["optim"]) of the reference (asteroid_librimix_trainer.py:94): the fused clip + Adam kernel serves
-    # Adam without weight decay (every shipped config); anything else is refused rather than silently ignored
-    if str(opt.get("optimizer", "adam")).lower() != "adam" or float(opt.get("weight_decay", 0) or 0) != 0:
-        raise NotImplementedError(f"asteroid env: optim {opt!r}: only adam with weight_decay 0 has a fused kernel")
+    # make_optimizer(**training_cfg["optim"]) of the reference (asteroid_librimix_trainer.py:94): adam, adamw and sgd have a fused clip +
+    # update kernel (fqss_adam_clip / fqss_optim_clip); any other name is refused rather than silently replaced
+    opt_name = str(opt.get("optimizer", "adam")).lower()
+    if opt_name not in ("adam", "adamw", "sgd"):
+        raise NotImplementedError(f"asteroid env: optim.optimizer {opt.get('optimizer')!r}: one of adam, adamw, sgd has a fused kernel")
+    optim = dict(optimizer=opt_name, weight_decay=float(opt.get("weight_decay", 0) or 0), momentum=float(opt.get("momentum", 0) or 0),
+                 nesterov=bool(opt.get("nesterov", False)))
     betas = tuple(opt.get("betas", (0.9, 0.999)))
     data = _Data(dataset_cfg, training_cfg, comm, dev, n_src=model_cfg.get("n_src", 2))
     # the loader's next mixture is on the device a step early: the frozen teacher runs on it beside the current step (KDTrainStep
     # teacher_ahead: the path bench.py measures; HIP backend only)
     ahead = (not cpu) and training_cfg.get("kd_lambda", 0) > 0 and bool(training_cfg.get("teacher_ahead", True))
     system = System(model, fmodel, training_cfg.get("kd_lambda", 0), lr=opt.get("lr", 1e-3), clip=5.0, comm=comm, betas=betas,
-                    teacher_ahead=ahead, accumulate=training_cfg.get("accumulate_grad_batches", 1))
+                    teacher_ahead=ahead, accumulate=training_cfg.get("accumulate_grad_batches", 1), **optim)
     global LAST_SYSTEM
     LAST_SYSTEM = system                # tools / tests: the stepper of the run that just finished (its graphs, its model)
     best, history, since_best, first_epoch = float("inf"), [], 0, 0

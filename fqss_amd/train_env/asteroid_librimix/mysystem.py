@@ -13,15 +13,17 @@ from .wsdr import KDObjective, si_sdr
 class System:
     default_monitor = "val_loss"
 
-    def __init__(self, model, fmodel, kd_lambda, lr=1e-3, clip=5.0, comm=None, betas=(0.9, 0.999), teacher_ahead=False, accumulate=1):
+    def __init__(self, model, fmodel, kd_lambda, lr=1e-3, clip=5.0, comm=None, betas=(0.9, 0.999), teacher_ahead=False, accumulate=1,
+                 **optim):
         # kd_lambda = 0: the reference trains on the plain PIT SI-SDR loss without the teacher (mysystem.py:153-156); KDTrainStep then
         # runs fqss_pit_sisdr_loss and never calls the teacher
         self.model = model
         self.fmodel = fmodel
         self.kd_lambda = kd_lambda
         self.objective = KDObjective(kd_lambda)
+        # optim: optimizer / weight_decay / momentum / nesterov of make_optimizer(**training_cfg["optim"]), handed to the fused update
         self.stepper = KDTrainStep(model, fmodel, kd_lambda=kd_lambda, lr=lr, clip=clip, comm=comm, betas=betas,
-                                   teacher_ahead=teacher_ahead, accumulate=accumulate)
+                                   teacher_ahead=teacher_ahead, accumulate=accumulate, **optim)
         self.logged = {}
 
     def forward(self, *a, **k):

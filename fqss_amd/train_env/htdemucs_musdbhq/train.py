@@ -66,19 +66,41 @@ def synth_stems(B, S, C, T, seed, device):
     return (torch.randn(B, S, C, T, generator=g) * 0.1).to(device)
 
 
+def group_decays(model):
+    """{parameter name: weight decay} of the modules that form an optimizer group of their own in the reference (make_optim_group,
+    htdemucsq.py:525-529: the cross-transformer, with its `weight_decay` attribute -- t_weight_decay).  A group learning rate is not
+    built: it is None in every configuration."""
+    from ...quantization.qat.models.htdemucsq import CrossTransformerEncoder
+    out = {}
+    for name, module in model.named_modules():
+        if isinstance(module, CrossTransformerEncoder):
+            if module.lr is not None:
+                raise NotImplementedError(f"htdemucs env: {name} asks for a learning rate of its own (t_lr = {module.lr}); not built")
+            for n, p in module.named_parameters():
+                if p.requires_grad:
+                    out[f"{name}.{n}" if name else n] = float(module.weight_decay)
+    return out
+
+
 class Solver:
     def __init__(self, conf, model, fmodel, comm, device):
         self.conf, self.model, self.fmodel, self.comm, self.device = conf, model, fmodel, comm, device
         opt = conf["optim"]
-        if opt.get("optim", "adam") != "adam" or opt.get("loss", "l1") != "l1" or opt.get("weight_decay", 0):
-            raise NotImplementedError("htdemucs env: Adam without weight decay on the L1 loss is the shipped configuration")
-        if any(conf.get("ema", {}).get(k) for k in ("epoch", "batch")):
-            raise NotImplementedError("htdemucs env: EMA copies are not built")
+        if opt.get("loss", "l1") != "l1":
+            raise NotImplementedError("htdemucs env: optim.loss: the L1 loss is the one that is built")
+        # get_optimizer (train.py:88-119): Adam or AdamW over the model, the modules with a make_optim_group() -- the cross-transformer --
+        # in a group of their own, with their own weight decay whatever optim.weight_decay says
+        kind = str(opt.get("optim", "adam")).lower()
+        if kind not in ("adam", "adamw"):
+            raise ValueError(f"htdemucs env: optim.optim {opt.get('optim')!r}: adam or adamw")
         self.weights = torch.tensor(conf.get("weights", [1.0] * model.n_srcs), device=device, dtype=torch.float32)
+        ema = conf.get("ema") or {}
         self.step = KDTrainStep(model, fmodel, kd_lambda=float(conf.get("kd_lambda", 0.1)), lr=float(opt["lr"]),
                                 clip=float(opt.get("clip_grad") or 0.0), comm=comm, loss="l1_sdr", source_weights=self.weights,
                                 betas=(float(opt.get("momentum", 0.9)), float(opt.get("beta2", 0.999))),
-                                accumulate=opt.get("accumulate_grad_batches", 1))    # ours (demucs has none): micro-batches per update
+                                accumulate=opt.get("accumulate_grad_batches", 1),    # ours (demucs has none): micro-batches per update
+                                optimizer=kind, weight_decay=float(opt.get("weight_decay", 0) or 0), param_decay=group_decays(model),
+                                ema_decays=tuple(ema.get("batch") or ()), ema_epoch_decays=tuple(ema.get("epoch") or ()))
         self.history = []
         self.best_state, self.best_loss = None, float("inf")
         self.ckpt_file = os.path.join(conf["work_dir"], checkpoint.NAME)
@@ -154,6 +176,7 @@ class Solver:
                 tot += loss.double()
         if train:
             self.step.flush()       # optim.accumulate_grad_batches: a window the epoch cut short updates on what it holds
+            self.step.ema_epoch_update()    # ema.epoch: once per epoch, after training (solver.py:438-440)
         self.comm.all_reduce_sum(tot)
         out = {"loss": tot.item() / (n * self.comm.world), "reco": tot.item() / (n * self.comm.world)}
         if train:
@@ -169,9 +192,28 @@ class Solver:
             key = self.conf.get("test", {}).get("metric", "loss")
             if key != "loss":
                 raise NotImplementedError("htdemucs env: best-model selection by nsdr needs demucs' evaluation (third party)")
+            # the EMA copies are validated with the model's own pass; the best of them all by `loss` is the epoch's candidate for
+            # best_state, under the name the reference records (solver.py:220-236)
+            # (a run without copies keeps the history it always wrote: `valid` is the model's own pass)
+            bcopy = None
+            if self.step.ema_kinds:
+                main = m["valid"]
+                m["valid"] = {"main": main}
+                bvalid, bname = main, "main"
+                for k, kind in enumerate(self.step.ema_kinds):
+                    name = f"ema_{kind}_{self.step.ema_kinds[:k].count(kind)}"
+                    with self.step.ema_swap(k):
+                        v = self._run_one_epoch(epoch, train=False)
+                    m["valid"][name] = v
+                    if v["loss"] < bvalid["loss"]:
+                        bvalid, bname, bcopy = v, name, k
+                m["valid"].update(bvalid)
+                m["valid"]["bname"] = bname
+            self.model.train()
             if m["valid"]["loss"] <= self.best_loss:
                 self.best_loss = m["valid"]["loss"]
-                self.best_state = {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}
+                state = self.model.state_dict() if bcopy is None else self.step.ema_state(bcopy)
+                self.best_state = {k: v.detach().cpu().clone() for k, v in state.items()}
             m["valid"]["best"] = self.best_loss
             self.history.append(m)
             if self.comm.rank == 0:

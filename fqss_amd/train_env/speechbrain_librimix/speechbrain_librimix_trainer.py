@@ -14,6 +14,8 @@ plain mappings and ignored.  Step semantics kept:
     loss as it is (:141-149), which at batch 1 makes the option a no-op; the kernel applies it on the device;
   * a step whose loss is not below `loss_upper_lim` (NaN / inf) is skipped and counted (:157-176); under data parallelism the
     decision is taken collectively so that every rank applies or skips the same update;
+  * `optimizer_cfg: {name: adam | adamw | sgd, weight_decay, momentum, nesterov}` (ours: the reference's `optimizer: !name:...` tag is
+    not instantiated by this loader; absent = Adam(lr)) selects the fused update, like `grad_accumulation_factor` a plain key;
   * clip_grad_norm, Adam(lr), `ReduceLROnPlateau(factor, patience, dont_halve_until_epoch)` on the validation loss (restated
     from speechbrain 0.5.14's published behaviour: third-party, parity unpinned).
 Data: `dataset_cfg.name: librimix` is the reference's configuration (configs/sepformer_2spks_8k.yaml:27-39): `prepare_librimix` writes
@@ -199,9 +201,17 @@ def train(yml_path, local_rank=0, distributed_launch=False, device="cuda", resum
     clip = float(hp.get("clip_grad_norm", 5))
     upper = float(hp.get("loss_upper_lim", 999999))
     threshold = float(hp["threshold"]) if hp.get("threshold_byloss") and "threshold" in hp else None
+    # `optimizer: !name:torch.optim.Adam` of the reference's YAML is an object tag this loader does not instantiate; the plain mapping
+    # `optimizer_cfg: {name: adam | adamw | sgd, weight_decay, momentum, nesterov}` names the fused update instead (default: Adam(lr))
+    ocfg = hp.get("optimizer_cfg") or {}
+    oname = str(ocfg.get("name", "adam")).lower()
+    if oname not in ("adam", "adamw", "sgd"):
+        raise NotImplementedError(f"speechbrain env: optimizer_cfg.name {ocfg.get('name')!r}: one of adam, adamw, sgd has a fused kernel")
     step = KDTrainStep(model, fmodel, kd_lambda=kd_lambda, lr=lr, clip=clip if clip >= 0 else 1e30, comm=comm,
                        loss="sisdr_pit_per_sample", loss_threshold=threshold,
-                       accumulate=hp.get("grad_accumulation_factor", 1))      # speechbrain Brain's run option: micro-batches per update
+                       accumulate=hp.get("grad_accumulation_factor", 1),      # speechbrain Brain's run option: micro-batches per update
+                       optimizer=oname, weight_decay=float(ocfg.get("weight_decay", 0) or 0),
+                       momentum=float(ocfg.get("momentum", 0) or 0), nesterov=bool(ocfg.get("nesterov", False)))
     accum = step.accumulate > 1
     sch = hp.get("lr_scheduler") or {}
     sched = ReduceLROnPlateau(sch.get("factor", 0.5), sch.get("patience", 2), sch.get("dont_halve_until_epoch", 65))

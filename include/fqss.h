@@ -707,6 +707,49 @@ int fqss_sumsq(const float* g, int64_t n, double* sumsq, fqss_stream_t stream);
 int fqss_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq,
                    float max_norm, float grad_scale, float lr, float beta1, float beta2, float eps,
                    int32_t* step_t, const int32_t* t0, float* gnorm_out, fqss_stream_t stream);
+/* The optimizer family behind the same clip: torch.optim.Adam with L2 decay, torch.optim.AdamW and torch.optim.SGD with momentum
+ * (single-tensor paths, foreach=False, maximize=False, amsgrad=False, dampening 0) -- what the reference's trainers accept beyond
+ * plain Adam (asteroid make_optimizer(**optim), htdemucs get_optimizer + make_optim_group, speechbrain's `optimizer:`).
+ * The arguments of fqss_adam_clip in their order, then:
+ *   kind          FQSS_OPT_ADAM | FQSS_OPT_ADAMW | FQSS_OPT_SGD
+ *   weight_decay  >= 0, every element's decay unless wd_slot is given
+ *   wd_slot       (nullable) n / 64 floats: the decay of each 64-float slot of the arena (arena slices are multiples of 64 floats from a
+ *                 64-float-aligned base, so a parameter group's own decay is one table read per slot); needs n % 64 == 0
+ *   momentum      SGD: mu in [0, 1); the buffer lives in m, v is not read (and may be NULL); mu = 0 keeps no buffer (m may be NULL)
+ *   nesterov      SGD: 0 | 1 (needs mu > 0)
+ * Per element, with the clock of fqss_adam_clip (t = step + 1 - t0[i]; t <= 0: p, m and v are not touched, decay included -- torch
+ * skips a parameter without a gradient), gc = the clipped, grad_scale'd gradient and wd the element's decay:
+ *   ADAM   g = gc + wd * p (wd != 0);  then the update of fqss_adam_clip
+ *   ADAMW  p *= 1 - lr * wd (wd != 0); then the update of fqss_adam_clip on gc
+ *   SGD    g = gc + wd * p (wd != 0);  mu > 0: buf = g at t == 1 (torch clones the first gradient), else buf = mu * buf + g;
+ *          d = nesterov ? g + mu * buf : buf;  mu = 0: d = g;  p += -lr * d
+ * The three `x + alpha * y` forms (g + wd * p, g + mu * buf, p + -lr * d) round once, as fused multiply-adds: that is what torch's
+ * add(alpha=) is in its vectorised CPU kernel and in its device kernels, and where g + wd * p cancels the second rounding shows.
+ * FQSS_OPT_ADAM with weight_decay 0 and no table gives the bits of fqss_adam_clip.  gnorm_out: the norm of the raw, grad_scale'd
+ * gradient.  One grid-stride pass, element i by the same thread on every run, no atomics; 16-B accesses when p, g, m, v and t0 are
+ * all 16-B aligned (the arena's are).  Refused (non-zero, nothing launched): another kind, a negative or NaN decay, a momentum
+ * outside [0, 1), nesterov without momentum, a null p / g / sumsq / step_t (or m / v where the kind uses them), wd_slot with
+ * n % 64 != 0. (tests/test_optim_cpu.py, tests/test_gpu_optim.py)                                                            */
+#define FQSS_OPT_ADAM 0
+#define FQSS_OPT_ADAMW 1
+#define FQSS_OPT_SGD 2
+int fqss_optim_clip(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq,
+                    float max_norm, float grad_scale, float lr, float beta1, float beta2, float eps,
+                    int32_t* step_t, const int32_t* t0, float* gnorm_out, int kind, float weight_decay, const float* wd_slot,
+                    float momentum, int nesterov, fqss_stream_t stream);
+/* Exponential moving average copies of the model (demucs' published ModelEMA, which the htdemucs solver keeps per batch and per
+ * epoch, solver.py:52-58, 425-440):
+ *     update():  count = count * decay + 1;  w = 1 / count            (unbias=True, the solver's setting; count starts at 0)
+ *                state[k].mul_(1 - w).add_(value, alpha=w)            for every float32 entry of the model's state_dict
+ * fqss_ema_update:      ema[i] = ema[i] * (1 - w) + w * p[i] with the host's w; 1 - w is formed in fp64 and rounded once.
+ * fqss_ema_update_dev:  the same with count held on the device (one double): the launch reads *count, uses
+ *                       w = 1 / (*count * decay + 1) (fp64, then rounded to fp32 like torch rounds the two Python scalars) and a
+ *                       one-thread launch behind it stores the advanced count -- graph-replay safe like step_t: a captured
+ *                       update advances w on every replay, where a host scalar would be frozen into the graph.
+ * One launch over the whole arena per copy, element i by thread i, no atomics.  ema and p: non-null, non-overlapping; w in [0, 1],
+ * decay in [0, 1); anything else is refused.  n = 0 is a no-op (the device count does not advance). */
+int fqss_ema_update(float* ema, const float* p, int64_t n, float w, fqss_stream_t stream);
+int fqss_ema_update_dev(float* ema, const float* p, int64_t n, double decay, double* count, fqss_stream_t stream);
 /* Gradient accumulation: one optimizer update per N micro-batches (pl.Trainer(accumulate_grad_batches=N), speechbrain's
  * grad_accumulation_factor).  Every micro-batch's backward rewrites the gradient arena g; acc, a second arena of the same layout,
  * holds the window's sum in between:
