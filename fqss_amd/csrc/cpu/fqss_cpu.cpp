@@ -63,6 +63,8 @@ inline float wq_levels(int n_bits) { return (float)((1 << n_bits) - 1); }
 inline float wq_qlo(int n_bits) { return -(float)(1 << (n_bits - 1)); }
 inline float wq_qhi(int n_bits) { return (float)((1 << (n_bits - 1)) - 1); }
 inline float wq_delta(float lo, float hi, float L) { return (2.0f * fmaxf(fabsf(lo), fabsf(hi))) / L; }
+inline float wq_code(float w, float delta, float qlo, float qhi) { return fminf(fmaxf(nearbyintf(w / delta), qlo), qhi); }
+inline float wq_mse_ratio(int k) { return (float)(FQSS_WQ_MSE_DEN - k) / (float)FQSS_WQ_MSE_DEN; }
 }  // namespace
 
 extern "C" {
@@ -234,8 +236,7 @@ int fqss_wq_fwd_bits(const float* w, float* wq, int8_t* idx, int64_t outer, int6
     for (int64_t e = 0; e < n; ++e) {
         const int64_t c = (e / inner) % C;
         const float delta = wq_delta(qmin[c], qmax[c], L);
-        const float X = nearbyintf(w[e] / delta);
-        const float q = fminf(fmaxf(X, qlo), qhi);
+        const float q = wq_code(w[e], delta, qlo, qhi);
         wq[e] = delta * q;
         if (idx) idx[e] = (int8_t)q;
     }
@@ -282,6 +283,76 @@ int fqss_wq_bwd_bits(const float* w, const float* g, float* gw, float* gmin, flo
 int fqss_wq_bwd(const float* w, const float* g, float* gw, float* gmin, float* gmax, int64_t outer, int64_t C, int64_t inner,
                 const float* qmin, const float* qmax, int accumulate, fqss_stream_t s) {
     return fqss_wq_bwd_bits(w, g, gw, gmin, gmax, outer, C, inner, qmin, qmax, accumulate, 8, s);
+}
+
+// MSE observer (include/fqss.h): candidate 0 is fqss_wq_observe's pair; e_k summed in fp64 in element order, candidates in order
+int fqss_wq_observe_mse(const float* w, int64_t outer, int64_t C, int64_t inner, float* qmin, float* qmax, int n_bits, int* k_out,
+                        double* err, fqss_stream_t) {
+    REQUIRE(w && qmin && qmax && outer > 0 && C > 0 && inner > 0, "bad args");
+    REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < C; ++c) {
+        float lo = INFINITY, hi = -INFINITY;
+        for (int64_t o = 0; o < outer; ++o)
+            for (int64_t i = 0; i < inner; ++i) {
+                const float v = w[(o * C + c) * inner + i];
+                lo = fminf(lo, v);
+                hi = fmaxf(hi, v);
+            }
+        const float amax = fmaxf(fabsf(lo), fabsf(hi));
+        const int nk = (amax > 0.0f && amax < INFINITY) ? FQSS_WQ_MSE_STEPS : 1;
+        double e0 = 0.0, ebest = 0.0;
+        int kbest = 0;
+        for (int k = 0; k < nk; ++k) {
+            const float r = wq_mse_ratio(k);
+            const float delta = wq_delta(r * lo, r * hi, L);
+            double e = 0.0;
+            for (int64_t o = 0; o < outer; ++o)
+                for (int64_t i = 0; i < inner; ++i) {
+                    const float v = w[(o * C + c) * inner + i];
+                    const double d = (double)v - (double)(delta * wq_code(v, delta, qlo, qhi));
+                    e += d * d;
+                }
+            if (k == 0) {
+                e0 = ebest = e;
+            } else if (e < ebest) {      // strict: ties go to the wider range
+                ebest = e;
+                kbest = k;
+            }
+        }
+        const float r = wq_mse_ratio(kbest);
+        qmin[c] = r * lo;
+        qmax[c] = r * hi;
+        if (k_out) k_out[c] = kbest;
+        if (err) {
+            err[2 * c] = e0;
+            err[2 * c + 1] = ebest;
+        }
+    }
+    return FQSS_OK;
+}
+
+int fqss_wq_error(const float* w, int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax, int n_bits, double* err,
+                  double* pow, fqss_stream_t) {
+    REQUIRE(w && qmin && qmax && err && pow && outer > 0 && C > 0 && inner > 0, "bad args");
+    REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < C; ++c) {
+        const float delta = wq_delta(qmin[c], qmax[c], L);
+        double e = 0.0, p = 0.0;
+        for (int64_t o = 0; o < outer; ++o)
+            for (int64_t i = 0; i < inner; ++i) {
+                const float v = w[(o * C + c) * inner + i];
+                const double d = (double)v - (double)(delta * wq_code(v, delta, qlo, qhi));
+                e += d * d;
+                p += (double)v * (double)v;
+            }
+        err[c] = e;
+        pow[c] = p;
+    }
+    return FQSS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ pointwise conv (qat_layers.py:137-146)

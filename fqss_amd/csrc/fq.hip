@@ -615,6 +615,12 @@ __global__ __launch_bounds__(256) void k_wq_observe(const float* __restrict__ w,
     }
 }
 
+// the clamped code of one weight as a float: one IEEE division, round-half-even, clip
+__device__ __forceinline__ float wq_code(float w, float delta, float qlo, float qhi) {
+    const float X = rintf(w / delta);
+    return fminf(fmaxf(X, qlo), qhi);
+}
+
 __global__ __launch_bounds__(256) void k_wq_fwd(const float* __restrict__ w, float* __restrict__ wq,
                                                  int8_t* __restrict__ idx, int64_t n, int64_t C, int64_t inner,
                                                  const float* __restrict__ qmin, const float* __restrict__ qmax, int n_bits) {
@@ -622,8 +628,7 @@ __global__ __launch_bounds__(256) void k_wq_fwd(const float* __restrict__ w, flo
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t c = (e / inner) % C;
         const float delta = wq_delta(qmin[c], qmax[c], L);
-        const float X = rintf(w[e] / delta);
-        const float q = fminf(fmaxf(X, qlo), qhi);
+        const float q = wq_code(w[e], delta, qlo, qhi);
         wq[e] = delta * q;
         if (idx != nullptr) idx[e] = (int8_t)q;
     }
@@ -665,6 +670,131 @@ __global__ __launch_bounds__(256) void k_wq_bwd(const float* __restrict__ w, con
         const float dmin = (float)(D * wl * sl), dmax = (float)(D * wh * sh);
         gmin[c] = accumulate ? gmin[c] + dmin : dmin;
         gmax[c] = accumulate ? gmax[c] + dmax : dmax;
+    }
+}
+
+// MSE observer of the weight quantizer (include/fqss.h, fqss_wq_observe_mse): one workgroup per channel.  The min / max pass is
+// k_wq_observe's, operation for operation (same per-thread order, same wave tree, same combine in thread 0), so candidate 0 is bit for
+// bit what that kernel writes.  A channel of up to kMseStage values is parked in LDS during that pass (32 KB: every weight of the four
+// model families fits; lanes read consecutive words, no bank conflicts) and the 81 candidates read it from there; a longer channel is
+// re-read from memory once per candidate group.  kMseGroup candidates share one pass over the channel and one block reduction (9 barrier
+// pairs instead of 81); each thread adds its elements in index order, the waves are added in wave order, thread 0 keeps the running
+// best in candidate order: a fixed association, the same bits every run.
+constexpr int kMseStage = 8192;
+constexpr int kMseGroup = 9;
+static_assert(FQSS_WQ_MSE_STEPS % kMseGroup == 0, "candidate groups must tile the candidate list");
+
+__device__ __forceinline__ float wq_mse_ratio(int k) { return (float)(FQSS_WQ_MSE_DEN - k) / (float)FQSS_WQ_MSE_DEN; }
+
+__global__ __launch_bounds__(256) void k_wq_observe_mse(const float* __restrict__ w, int64_t outer, int64_t C, int64_t inner,
+                                                         float* qmin, float* qmax, int n_bits, int* k_out, double* err) {
+    __shared__ float s_w[kMseStage];
+    __shared__ float smin[4], smax[4];
+    __shared__ double red[kMseGroup * 4];
+    const int64_t c = blockIdx.x;
+    const int64_t n = outer * inner;
+    const bool staged = n <= kMseStage;      // (workgroup-uniform)
+    float vmin = INFINITY, vmax = -INFINITY;
+    for (int64_t e = threadIdx.x; e < n; e += blockDim.x) {
+        const int64_t o = e / inner, i = e - o * inner;
+        const float v = w[(o * C + c) * inner + i];
+        vmin = fminf(vmin, v);
+        vmax = fmaxf(vmax, v);
+        if (staged) s_w[e] = v;
+    }
+    vmin = wave_min(vmin);
+    vmax = wave_max(vmax);
+    if ((threadIdx.x & 63) == 0) {
+        smin[threadIdx.x >> 6] = vmin;
+        smax[threadIdx.x >> 6] = vmax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < (int)(blockDim.x >> 6); ++k) {
+            vmin = fminf(vmin, smin[k]);
+            vmax = fmaxf(vmax, smax[k]);
+        }
+        smin[0] = vmin;
+        smax[0] = vmax;
+    }
+    __syncthreads();
+    const float lo = smin[0], hi = smax[0];
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
+    const float amax = fmaxf(fabsf(lo), fabsf(hi));
+    // an all-zero channel or one without a finite range keeps candidate 0: only the first group runs, only its first sum is read
+    const int nk = (amax > 0.0f && amax < INFINITY) ? FQSS_WQ_MSE_STEPS : 1;
+    double e0 = 0.0, ebest = 0.0;
+    int kbest = 0;
+    for (int k0 = 0; k0 < nk; k0 += kMseGroup) {
+        float delta[kMseGroup];
+        double acc[kMseGroup];
+#pragma unroll
+        for (int j = 0; j < kMseGroup; ++j) {
+            const float r = wq_mse_ratio(k0 + j);
+            delta[j] = wq_delta(r * lo, r * hi, L);
+            acc[j] = 0.0;
+        }
+        for (int64_t e = threadIdx.x; e < n; e += blockDim.x) {
+            float v;
+            if (staged) {
+                v = s_w[e];
+            } else {
+                const int64_t o = e / inner, i = e - o * inner;
+                v = w[(o * C + c) * inner + i];
+            }
+#pragma unroll
+            for (int j = 0; j < kMseGroup; ++j) {
+                const double d = (double)v - (double)(delta[j] * wq_code(v, delta[j], qlo, qhi));
+                acc[j] += d * d;
+            }
+        }
+        block_sum<double, kMseGroup>(acc, red);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < kMseGroup; ++j) {
+                const int k = k0 + j;
+                if (k == 0) {
+                    e0 = ebest = acc[j];
+                } else if (k < nk && acc[j] < ebest) {      // strict: ties go to the wider range
+                    ebest = acc[j];
+                    kbest = k;
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        const float r = wq_mse_ratio(kbest);     // k = 0: r = 1, the observed pair itself
+        qmin[c] = r * lo;
+        qmax[c] = r * hi;
+        if (k_out != nullptr) k_out[c] = kbest;
+        if (err != nullptr) {
+            err[2 * c] = e0;
+            err[2 * c + 1] = ebest;
+        }
+    }
+}
+
+// squared error of a channel on the grid of the given ranges and the channel's power, fp64, fixed order (k_wq_observe_mse's e_k)
+__global__ __launch_bounds__(256) void k_wq_error(const float* __restrict__ w, int64_t outer, int64_t C, int64_t inner,
+                                                   const float* __restrict__ qmin, const float* __restrict__ qmax, int n_bits,
+                                                   double* err, double* pow) {
+    __shared__ double red[2 * 4];
+    const int64_t c = blockIdx.x;
+    const float L = wq_levels(n_bits), qlo = wq_qlo(n_bits), qhi = wq_qhi(n_bits);
+    const float delta = wq_delta(qmin[c], qmax[c], L);
+    const int64_t n = outer * inner;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t e = threadIdx.x; e < n; e += blockDim.x) {
+        const int64_t o = e / inner, i = e - o * inner;
+        const float v = w[(o * C + c) * inner + i];
+        const double d = (double)v - (double)(delta * wq_code(v, delta, qlo, qhi));
+        acc[0] += d * d;
+        acc[1] += (double)v * (double)v;
+    }
+    block_sum<double, 2>(acc, red);
+    if (threadIdx.x == 0) {
+        err[c] = acc[0];
+        pow[c] = acc[1];
     }
 }
 
@@ -954,6 +1084,24 @@ extern "C" int fqss_wq_bwd(const float* w, const float* g, float* gw, float* gmi
                            int64_t C, int64_t inner, const float* qmin, const float* qmax, int accumulate,
                            fqss_stream_t stream) {
     return fqss_wq_bwd_bits(w, g, gw, gmin, gmax, outer, C, inner, qmin, qmax, accumulate, 8, stream);
+}
+
+extern "C" int fqss_wq_observe_mse(const float* w, int64_t outer, int64_t C, int64_t inner, float* qmin, float* qmax, int n_bits,
+                                   int* k_out, double* err, fqss_stream_t stream) {
+    FQSS_REQUIRE(w && qmin && qmax && outer > 0 && C > 0 && inner > 0, "bad args");
+    FQSS_REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    hipLaunchKernelGGL(k_wq_observe_mse, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, w, outer, C, inner, qmin, qmax, n_bits,
+                       k_out, err);
+    return launch_status("fqss_wq_observe_mse");
+}
+
+extern "C" int fqss_wq_error(const float* w, int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax, int n_bits,
+                             double* err, double* pow, fqss_stream_t stream) {
+    FQSS_REQUIRE(w && qmin && qmax && err && pow && outer > 0 && C > 0 && inner > 0, "bad args");
+    FQSS_REQUIRE(n_bits >= FQSS_WQ_MIN_BITS && n_bits <= FQSS_WQ_MAX_BITS, "weight width outside 2..8 bits");
+    hipLaunchKernelGGL(k_wq_error, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, w, outer, C, inner, qmin, qmax, n_bits, err,
+                       pow);
+    return launch_status("fqss_wq_error");
 }
 
 static bool gluq_rows_ok(const void* a, const void* b, int64_t lda, int64_t ldb, int64_t M) {

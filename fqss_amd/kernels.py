@@ -19,6 +19,7 @@ ACT_GELU, ACT_POST_RELU = _h("ACT_GELU", "ACT_POST_RELU")
 GACC_DOUBLES = _h("GACC_SLOTS")[0] * 3   # FQSS_GACC_SLOTS x (dmin, dmax, dslope)
 WQ_DESC_WORDS, = _h("WQ_DESC_WORDS")     # int64 words per weight descriptor (word 17 = the weight's width in bits)
 WQ_BITS = _h("WQ_MIN_BITS", "WQ_MAX_BITS")
+WQ_MSE_STEPS, WQ_MSE_DEN = _h("WQ_MSE_STEPS", "WQ_MSE_DEN")   # MSE observer: candidate k scales the observed range by (DEN - k) / DEN
 USE_X3 = True            # route plain fp32 pointwise convs through the bf16 3x3-split GEMM
 LD_ALIGN = 16  # row stride of activation buffers is padded to 16 floats (64 B) -> 16-B/lane path
 
@@ -270,6 +271,31 @@ def wq_observe(w, axis, qmin, qmax):
     _need_gpu(w, qmin, qmax)
     o, c, i = _w_layout(w.shape, axis)
     _lib.call("fqss_wq_observe", _p(w.contiguous()), o, c, i, _p(qmin), _p(qmax), _stream())
+
+
+def wq_observe_mse(w, axis, qmin, qmax, n_bits, want=False):
+    """the MSE observer (include/fqss.h): per channel, the best of WQ_MSE_STEPS shrunken copies of the observed (min, max) by squared
+    weight error on the n_bits grid, written into qmin / qmax.  want=True: also (k int32 [C], err float64 [C, 2] = e_0, e_k)"""
+    _need_gpu(w, qmin, qmax)
+    o, c, i = _w_layout(w.shape, axis)
+    w = w.contiguous()
+    k = torch.empty(c, device=w.device, dtype=torch.int32) if want else None
+    err = torch.empty(c, 2, device=w.device, dtype=torch.float64) if want else None
+    _lib.call("fqss_wq_observe_mse", _p(w), o, c, i, _p(qmin), _p(qmax), int(n_bits), _p(k), _p(err), _stream())
+    return (k, err) if want else None
+
+
+def wq_error(w, axis, qmin, qmax, n_bits):
+    """(err, pow), float64 [C] each: the squared error of every channel of w on the n_bits grid of the given ranges (the forward's
+    arithmetic) and the channel's sum of squares"""
+    _need_gpu(w, qmin, qmax)
+    o, c, i = _w_layout(w.shape, axis)
+    w, qmin, qmax = w.contiguous(), qmin.contiguous(), qmax.contiguous()
+    err = torch.empty(c, device=w.device, dtype=torch.float64)
+    pw = torch.empty(c, device=w.device, dtype=torch.float64)
+    _lib.call("fqss_wq_error", _p(w), o, c, i, _p(qmin), _p(qmax), int(n_bits), _p(err), _p(pw),
+              _stream())
+    return err, pw
 
 
 def wq_fwd(w, axis, qmin, qmax, want_idx=False, n_bits=8):

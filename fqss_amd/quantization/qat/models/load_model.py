@@ -2,7 +2,7 @@
 import torch
 
 from ..qat_layers import LayerQ
-from ..qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize
+from ..qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize, check_weight_observer
 from ..qat_utils import check_lstm_quant
 from .convtasnetq import ConvTasNetQ
 from .dptnetq import DPTNetQ
@@ -44,6 +44,7 @@ def create_model(model_cfg):
 
 
 def quantize_model(model, quant_cfg):
+    weight_observer = check_weight_observer(quant_cfg.get("weight_observer"))
     if quant_cfg.get("qat", False):
         g = quant_cfg.get
         model.set_splitter_combiner(g("n_splitter", 1), g("n_combiner", 1))
@@ -57,6 +58,11 @@ def quantize_model(model, quant_cfg):
                              act_n_bits=g("act_n_bits", 8), inout_nl_quant=g("inout_nl_quant", False),
                              in_quant=g("in_quant", False), in_act_n_bits=g("in_act_n_bits", 8),
                              out_quant=g("out_quant", False), out_act_n_bits=g("out_act_n_bits", 8), **extra)
+        # what each weight quantizer's first call writes (minmax | mse): conv, transposed conv and conv2d layers, the attention
+        # projections and the LSTM matrices all carry a GradientWeightFakeQuantize, so one walk of the tree covers them
+        for m in model.modules():
+            if isinstance(m, GradientWeightFakeQuantize):
+                m.observer = weight_observer
         enable_observer(model, g("observer", False))
     return model
 

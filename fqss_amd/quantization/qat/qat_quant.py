@@ -7,6 +7,7 @@ quantization/qat/qat_quant.py; the arithmetic runs in the HIP kernels of csrc/fq
   linear_quantize                    qat_quant.py:125-147  -> fqss_actq_fwd/bwd, fqss_wq_fwd_bits/bwd_bits
   GradientActivationFakeQuantize     qat_quant.py:206-242  -> observer: fqss_actq_fwd(OBSERVE)+fqss_observer_ema
   GradientWeightFakeQuantize         qat_quant.py:350-381  -> fqss_wq_observe / fqss_wq_fwd_bits / fqss_wq_bwd_bits
+                                                            (`weight_observer: mse`: fqss_wq_observe_mse on the first call)
 
 Supported widths:
   * weights (`weight_n_bits`, GradientWeightFakeQuantize, linear_quantize(sym=True)): every integer from 2 to 8.  Width n
@@ -35,6 +36,16 @@ def ops_dp_qrow():
 
 
 WEIGHT_BITS = tuple(range(K.WQ_BITS[0], K.WQ_BITS[1] + 1))
+WEIGHT_OBSERVERS = ("minmax", "mse")
+
+
+def check_weight_observer(name):
+    """`model_cfg.quantization.weight_observer`: absent (None) or "minmax" -> today's observer, "mse" -> the range search"""
+    if name is None:
+        return WEIGHT_OBSERVERS[0]
+    if name not in WEIGHT_OBSERVERS:
+        raise ValueError(f"weight_observer must be {WEIGHT_OBSERVERS[0]!r} or {WEIGHT_OBSERVERS[1]!r}, got {name!r}")
+    return name
 
 
 def _check_weight_bits(n_bits):
@@ -160,7 +171,8 @@ class GradientActivationFakeQuantize(nn.Module):
 
 
 class GradientWeightFakeQuantize(nn.Module):
-    """Per-output-channel symmetric weight quantizer at n_bits = 2 to 8; the first call only records amax/amin."""
+    """Per-output-channel symmetric weight quantizer at n_bits = 2 to 8; the first call only records amax/amin (`observer` =
+    "minmax") or the best shrunken copy of that pair by squared weight error (`observer` = "mse")."""
 
     def __init__(self, gradient_based, weight_shape, n_bits=8, sym=True, ch_out_idx=0, scale_grad=False):
         super().__init__()
@@ -181,9 +193,19 @@ class GradientWeightFakeQuantize(nn.Module):
     def enable_observer(self, observer_mode):
         self.observer_mode = observer_mode
 
+    # what the first call writes into the ranges: "minmax" (the channel's amin / amax) or "mse" (the best of 81 shrunken copies of that
+    # pair by squared weight error on this quantizer's grid, fqss_wq_observe_mse).  A plain attribute, set by
+    # load_model.quantize_model from `weight_observer`; not part of the constructor or the state_dict.
+    observer = "minmax"
+
     def forward(self, x, w_param=None):
         if self.observer_mode:
-            K.wq_observe(x.detach(), self.axis, self.min_range.data, self.max_range.data)
+            if self.observer == "mse":
+                K.wq_observe_mse(x.detach(), self.axis, self.min_range.data, self.max_range.data, self.n_bits)
+            elif self.observer == "minmax":
+                K.wq_observe(x.detach(), self.axis, self.min_range.data, self.max_range.data)
+            else:
+                raise ValueError(f"weight observer {self.observer!r}: the choices are {WEIGHT_OBSERVERS[0]!r} and {WEIGHT_OBSERVERS[1]!r}")
             self.observer_mode = False
             return x
         pre = getattr(x, "_fqss_wq", None)

@@ -218,6 +218,43 @@ def weight_quantizer_owners(model):
     return out
 
 
+def weight_quantizer_pairs(model):
+    """weight_quantizer_owners (the integer export's list, left as it is) plus the two kinds it does not pair: the quantizer a TRAINABLE
+    residual decoder owns for its own weight (`weight_fake_quantize_dec` of the residual error block, train_res_dec=True: Sepformer,
+    HTDemucs) and EmbeddingQ's table -- every GradientWeightFakeQuantize of the tree with its weight"""
+    from .qat_quant import GradientWeightFakeQuantize
+    names = {id(p): n for n, p in model.named_parameters()}
+    out = list(weight_quantizer_owners(model))
+    for layer in model.modules():
+        wqm, dec = getattr(layer, "weight_fake_quantize_dec", None), getattr(layer, "residual_decoder", None)
+        if isinstance(wqm, GradientWeightFakeQuantize) and isinstance(getattr(dec, "weight", None), nn.Parameter):
+            out.append((wqm, dec.weight, names[id(dec.weight)]))
+        if isinstance(layer, QL.EmbeddingQ) and isinstance(layer.weight_fake_quantize, GradientWeightFakeQuantize):
+            out.append((layer.weight_fake_quantize, layer.embedding.weight, names[id(layer.embedding.weight)]))
+    return out
+
+
+def weight_quant_report(model):
+    """One row per quantized weight: {"name": parameter name, "n_bits", "channels", "sqnr_db": 10 log10(sum pow / sum err) of the weight on
+    its quantizer's present grid (fqss_wq_error: the forward's arithmetic, fp64 sums), "narrower": the share of channels whose range
+    max - min is narrower than the channel's observed amax - amin (what the MSE observer, or training, took off the min/max start)}.
+    A quantizer that has not observed yet reports its constructor ranges."""
+    import math
+    from ... import kernels as K
+    rows = []
+    for wqm, w, pname in weight_quantizer_pairs(model):
+        wd = w.detach()
+        qmin, qmax = wqm.min_range.detach(), wqm.max_range.detach()
+        err, pw = K.wq_error(wd, wqm.axis, qmin, qmax, wqm.n_bits)
+        lo, hi = torch.empty_like(qmin), torch.empty_like(qmax)
+        K.wq_observe(wd, wqm.axis, lo, hi)
+        e, p = float(err.sum()), float(pw.sum())
+        rows.append({"name": pname, "n_bits": int(wqm.n_bits), "channels": int(err.numel()),
+                     "sqnr_db": 10.0 * math.log10(p / e) if e > 0.0 and p > 0.0 else (math.inf if p > 0.0 else math.nan),
+                     "narrower": int(((qmax - qmin) < (hi - lo)).sum()) / int(err.numel())})
+    return rows
+
+
 def integer_state(model):
     """the model as integers: {"format", "weights": {parameter name: codes int8, delta [C], axis, min/max range}, "activations":
     {quantizer path: min, max, scale, zero_point}, "float": every other state_dict entry, "keys": the state_dict's key order}"""

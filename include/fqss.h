@@ -139,6 +139,27 @@ int fqss_wq_bwd_bits(const float* w, const float* g, float* gw, float* gmin, flo
                      int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax,
                      int accumulate, int n_bits, fqss_stream_t stream);
 
+/* MSE observer (opt-in, `weight_observer: mse`): what the FIRST call of a weight quantizer writes into its ranges, found by a search
+ * over FQSS_WQ_MSE_STEPS shrunken copies of the observed range.  For channel c of w [outer][C][inner] at width n_bits:
+ *   1. lo, hi = the channel's min / max, bit for bit what fqss_wq_observe writes;
+ *   2. for k = 0 .. FQSS_WQ_MSE_STEPS - 1:  r_k = (float)(FQSS_WQ_MSE_DEN - k) / (float)FQSS_WQ_MSE_DEN (IEEE fp32 division),
+ *      lo_k = r_k * lo, hi_k = r_k * hi (one fp32 rounding each; both ends scale, so the larger-magnitude side stays the larger and
+ *      the backward routes the range gradient as it would for min/max), delta_k = 2 max(|lo_k|, |hi_k|) / L,
+ *      q = clip(rint(w / delta_k), -2^(n-1), 2^(n-1) - 1) -- the arithmetic of fqss_wq_fwd_bits, operation for operation --
+ *      e_k = sum over the channel of ((double)w - (double)(delta_k * q))^2, accumulated in fp64 in a fixed order (no atomics:
+ *      two runs give the same bits);
+ *   3. the smallest k whose e_k is minimal wins (strict <: ties go to the wider range); qmin[c] = lo_k, qmax[c] = hi_k;
+ *   4. a channel whose max(|lo|, |hi|) is 0 or not finite gets k = 0, i.e. (lo, hi) as fqss_wq_observe writes them, without a search.
+ * k_out (optional, int [C]) receives k; err (optional, double [C][2]) receives e_0 and e_k of the chosen k.
+ * fqss_wq_error: err[c] = the same squared error for ANY given ranges, pow[c] = sum w^2 (both double [C]); 10 log10(pow / err) is the
+ * channel's SQNR on the training grid. */
+#define FQSS_WQ_MSE_STEPS 81
+#define FQSS_WQ_MSE_DEN 100
+int fqss_wq_observe_mse(const float* w, int64_t outer, int64_t C, int64_t inner, float* qmin, float* qmax, int n_bits, int* k_out,
+                        double* err, fqss_stream_t stream);
+int fqss_wq_error(const float* w, int64_t outer, int64_t C, int64_t inner, const float* qmin, const float* qmax, int n_bits,
+                  double* err, double* pow, fqss_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * multi-tensor forms of the per-quantizer small work (csrc/multi.hip): ONE launch each, driven by a
  * device table of int64 words the host builds once.
