@@ -273,6 +273,56 @@ __device__ __forceinline__ float fq_asym(float t, const QRange& r, float& c, flo
     return r.delta * c + r.lo;  // two roundings (mul, add): contraction is off
 }
 
+// de-quantised value of a code: two roundings (mul, add)
+__device__ __forceinline__ float dec(unsigned int c, const QRange& r) { return r.delta * (float)c + r.lo; }
+
+// ---- the per-element backward of the element-wise quantized layers (csrc/fused_q.hip k_ewq_bwd / k_ewq_chain_bwd; csrc/qgemm.hip:
+// the residual AddQ's backward in the epilogue of the dgrad that produces its gradient).  One definition, so that every caller
+// carries the same operation sequence and -- contraction off -- the same bits.
+// An operand that is the fake-quantized output of a pointwise conv (res / skip conv of a TCN block) can have THAT
+// layer's epilogue backward done by the add's kernel (cf. GnProducer): its gz goes to `out`, its partials to its own slots / bias.
+struct EwProducer {
+    const float* pz; int ld_pz;      // producer's pre-quant output (NULL: operand not fused)
+    int act; const float* slope;
+    double* gacc; float* gbias;      // gbias [C] nullable
+    float* out; int ld_out;          // the producer's gz
+};
+
+// PLAIN: no non-linearity anywhere (AddQ of the res / skip convs: the case of every launch of the ConvTasNet step).  These kernels are
+// VALU-issue bound: act_apply / act_bwd as identities and the per-element validity selects (a masked-out position already carries
+// gj = 0, which zeroes every sum it enters) were ~25 of the ~86 instructions per element.
+template <bool PLAIN>
+__device__ __forceinline__ float ew_producer_bwd(const EwProducer& P, const QRange& rp, float pslope, float pz, float gj, bool valid,
+                                                 float& p_du, float& p_out, float& p_slope, float& p_bias) {
+    const float t = PLAIN ? pz : act_apply(pz, P.act, pslope);
+    float pc, pu;
+    bool pin;
+    (void)fq_asym(t, rp, pc, pu, pin);
+    const float gt = pin ? div_by(gj * rp.delta, rp.delta, rp.inv) : 0.0f;
+    if constexpr (PLAIN) {      // gj == 0 where the position is masked out
+        p_du += gj * (pin ? (pc - pu) : pc);
+        p_out += pin ? 0.0f : gj;
+        p_bias += gt;
+        return gt;
+    } else {
+        p_du += valid ? gj * (pin ? (pc - pu) : pc) : 0.0f;          // (selects, not branches: fq.hip k_actq_bwd)
+        p_out += (valid && !pin) ? gj : 0.0f;
+        float gzj = act_bwd(pz, gt, P.act, pslope, valid, p_slope);
+        p_bias += valid ? gzj : 0.0f;
+        return gzj;
+    }
+}
+// the PLAIN layer's own quantizer on its sum z: dL/dz of the straight-through estimator for dL/dy = gj (0 where the position is
+// masked out: it then drops out of both range partials by itself)
+__device__ __forceinline__ float ew_plain_bwd(float z, const QRange& ry, float gj, float& p_du, float& p_out) {
+    float cq, u;
+    bool inr;
+    (void)fq_asym(z, ry, cq, u, inr);
+    p_du += gj * (inr ? (cq - u) : cq);
+    p_out += inr ? 0.0f : gj;
+    return inr ? div_by(gj * ry.delta, ry.delta, ry.inv) : 0.0f;
+}
+
 // The forward-only forms of fq_asym (these streaming kernels are VALU-issue bound: ~5 cycles per wave instruction and SIMD,
 // measured; every instruction per element counts): the clamped code alone, packed with v_cvt_pk_u8_f32 (exact: the code is an
 // integer in [0, 255]); the de-quantised value only where a caller stores it.

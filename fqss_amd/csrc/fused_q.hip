@@ -26,7 +26,6 @@ namespace fqss {
 constexpr int kGnSlots = 64;       // partial-sum slots per sample (one per stats workgroup)
 constexpr int kSlots = FQSS_GACC_SLOTS;
 
-__device__ __forceinline__ float dec(unsigned int c, const QRange& r) { return r.delta * (float)c + r.lo; }
 __device__ __forceinline__ void dec4(unsigned int w, const QRange& r, float (&v)[4]) {
     v[0] = dec(w & 255u, r);          // v_cvt_f32_ubyte0..3 + mul + add (two roundings, like the reference)
     v[1] = dec((w >> 8) & 255u, r);
@@ -1082,39 +1081,7 @@ __global__ __launch_bounds__(256) void k_ewq_fwd(const uint8_t* __restrict__ ac,
 }
 
 // backward: recompute z from the input codes; gz = STE(act') ; range/slope partials to the gacc slots
-// An operand that is the fake-quantized output of a pointwise conv (res / skip conv of a TCN block) can have THAT
-// layer's epilogue backward done here (cf. GnProducer): its gz goes to `out`, its partials to its own slots / bias.
-struct EwProducer {
-    const float* pz; int ld_pz;      // producer's pre-quant output (NULL: operand not fused)
-    int act; const float* slope;
-    double* gacc; float* gbias;      // gbias [C] nullable
-    float* out; int ld_out;          // the producer's gz
-};
-
-// PLAIN: no non-linearity anywhere (AddQ of the res / skip convs: the case of every launch of the ConvTasNet step).  These kernels are
-// VALU-issue bound: act_apply / act_bwd as identities and the per-element validity selects (a masked-out position already carries
-// gj = 0, which zeroes every sum it enters) were ~25 of the ~86 instructions per element.
-template <bool PLAIN>
-__device__ __forceinline__ float ew_producer_bwd(const EwProducer& P, const QRange& rp, float pslope, float pz, float gj, bool valid,
-                                                 float& p_du, float& p_out, float& p_slope, float& p_bias) {
-    const float t = PLAIN ? pz : act_apply(pz, P.act, pslope);
-    float pc, pu;
-    bool pin;
-    (void)fq_asym(t, rp, pc, pu, pin);
-    const float gt = pin ? div_by(gj * rp.delta, rp.delta, rp.inv) : 0.0f;
-    if constexpr (PLAIN) {      // gj == 0 where the position is masked out
-        p_du += gj * (pin ? (pc - pu) : pc);
-        p_out += pin ? 0.0f : gj;
-        p_bias += gt;
-        return gt;
-    } else {
-        p_du += valid ? gj * (pin ? (pc - pu) : pc) : 0.0f;          // (selects, not branches: fq.hip k_actq_bwd)
-        p_out += (valid && !pin) ? gj : 0.0f;
-        float gzj = act_bwd(pz, gt, P.act, pslope, valid, p_slope);
-        p_bias += valid ? gzj : 0.0f;
-        return gzj;
-    }
-}
+// (EwProducer, ew_producer_bwd, ew_plain_bwd: fqss_dev.h -- shared with the dgrad epilogue of csrc/qgemm.hip)
 
 constexpr int EWQ_NR = 2;    // rows of loads in flight per thread (x FQSS_EWQ_WAVES waves per SIMD; 8 x 2 first: 196 VGPRs; round 5, the fused
                              // residual-add launch alone, us: 8 x 2 24.4, 8 x 3 32.0, 4 x 3 24.9, 3 x 3 23.6, 2 x 3 22.0, 2 x 4 22.3, 1 x 3 21.4, 1 x 4 21.2 --
@@ -1164,17 +1131,14 @@ __global__ __launch_bounds__(256, FQSS_EWQ_WAVES) void k_ewq_bwd(const uint8_t* 
             float z = dec((in.wa >> (8 * e)) & 255u, ra);
             if (bc != nullptr) z = z + sb * dec((in.wb >> (8 * e)) & 255u, rb);
             else if (bf != nullptr) z = z + sb * bv[e];
-            const float t = PLAIN ? z : act_apply(z, act, slope);
-            float cq, u;
-            bool inr;
-            (void)fq_asym(t, ry, cq, u, inr);
-            const float gt = inr ? div_by(gj * ry.delta, ry.delta, ry.inv) : 0.0f;
             float gzj;
             if constexpr (PLAIN) {      // gj == 0 where the position is masked out: it drops out of every sum by itself
-                p_du += gj * (inr ? (cq - u) : cq);
-                p_out += inr ? 0.0f : gj;
-                gzj = gt;
+                gzj = ew_plain_bwd(z, ry, gj, p_du, p_out);
             } else {
+                float cq, u;
+                bool inr;
+                (void)fq_asym(act_apply(z, act, slope), ry, cq, u, inr);
+                const float gt = inr ? div_by(gj * ry.delta, ry.delta, ry.inv) : 0.0f;
                 p_du += valid ? gj * (inr ? (cq - u) : cq) : 0.0f;
                 p_out += (valid && !inr) ? gj : 0.0f;
                 gzj = act_bwd(z, gt, act, slope, valid, p_slope);

@@ -83,9 +83,6 @@ __device__ __forceinline__ void q_wait(QStage& st) {
                      : "memory");
 }
 
-// de-quantised value of a code: two roundings (mul, add), the form of fused_q.hip
-__device__ __forceinline__ float dec(unsigned int c, const QRange& r) { return r.delta * (float)c + r.lo; }
-
 struct QGemmArgs {
     // forward / dgrad: A = int8 weight codes [M][K] (k contiguous), B = per-batch [K][ldb] (n contiguous)
     // wgrad          : A = fp32 gz [M][lda] per batch (k = n contiguous), B = u8 codes [N][ldb] per batch
@@ -132,6 +129,16 @@ struct QGemmArgs {
     // fqss_frames_gather -- taps x the signal, written and read back -- is never made.  imp_cmax: last column group a load may start at.
     int imp_taps, imp_kw, imp_base, imp_row_step, imp_col_step, imp_cmax;
     float imp_inv_taps, imp_inv_kw;
+    // dgrad, ADDQ instance: the output g = W_q^T gz + addend is the gradient at the output of a residual AddQ y = fq(dec(a) + dec(b))
+    // whose b is the fresh output of a pointwise conv without activation (FqssAddqBwd, fqss.h); the add's backward and that conv's
+    // output-quantizer backward run on g in registers -- what k_ewq_bwd<true> computes from g in a launch of its own (fused_q.hip) --
+    // and g itself is never written.  One row tile only (tiles_m == 1): every g element is in exactly one lane of one workgroup.
+    const unsigned char* eq_a; const unsigned char* eq_b; int64_t eq_lda, eq_ldb;        // [batches][M][ld] u8 codes
+    const float *eq_amin, *eq_amax, *eq_bmin, *eq_bmax, *eq_qmin, *eq_qmax;
+    const float* eq_pz; int64_t eq_ldpz;              // the producer's pre-quant output
+    float* eq_ga; float* eq_pout; int64_t eq_ldga, eq_ldpout;   // dL/da (the add's gz) and the producer's gz
+    double* eq_gacc; double* eq_pgacc;                // range partials: slot 3 * workgroup of each
+    float* eq_bias_ws;                                // [workgroups][M] row sums of the producer's gz
 };
 
 // MODE 0 fwd (int8 A codes, u8 B codes)            1 dgrad (int8 A codes, fp32 B split3)
@@ -139,9 +146,11 @@ struct QGemmArgs {
 // The fp32 gradient operand of MODE 1 always goes in three exact bf16 pieces (a = h1 + h2 + h3, truncations): against fp64 the result
 // sits at 1.6e-7 .. 4.4e-7 of its norm (tests/test_gpu_kernels.py::test_gradient_gemms_exact_split).
 // GP is 3 except for MODE 3's six-product form; it stays a parameter because profiles and the benchmark key on the kernels' printed names.
-template <int MODE, int GP = 3, bool IMP = false>
-__global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
+// ADDQ (MODE 1): the residual AddQ's backward on the output tile instead of the store of g (QGemmArgs eq_*)
+template <int MODE, int GP = 3, bool IMP = false, bool ADDQ = false>
+__global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
     static_assert(!IMP || MODE == 1 || MODE == 3 || MODE == 4, "implicit convolution: float B operands");
+    static_assert(!ADDQ || (MODE == 1 && !IMP), "fused AddQ backward: the plain dgrad only");
     // MODE 4 (round 5): forward of a layer whose WEIGHT is on the int8 grid while its input is a plain float tensor (the frame-path
     // convolutions of HTDemucs): A = int8 weight codes, B = fp32 x in three exact bf16 pieces -- the loop of MODE 1 without its
     // delta_w scaling of the reduction rows -- and z = dw[co] * S + b[co] in the epilogue: three products per k instead of six
@@ -399,6 +408,23 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
     QRange ry1{}, ry2{};
     QRange rad1{}, rad2{}, rs1{}, rs2{};     // fused AddQ behind output 1 / 2: the other operand's range, the sum's range
     float qslope = 0.0f;
+    // ADDQ: ranges of the add's operands and of its own quantizer; per-thread partials of the two quantizers' range gradients
+    QRange era{}, erb{}, ery{};
+    const float *eq_ad = nullptr, *eq_pz = nullptr;
+    const unsigned char *eq_a = nullptr, *eq_b = nullptr;
+    float *eq_ga = nullptr, *eq_pout = nullptr;
+    unsigned eq_ldad = 0, eq_ldpz = 0, eq_lda = 0, eq_ldb = 0, eq_ldga = 0, eq_ldpout = 0;
+    float e_du = 0.f, e_out = 0.f, eb_du = 0.f, eb_out = 0.f;
+    if constexpr (ADDQ) {
+        const int64_t r0 = (int64_t)b * g.M;      // this sample's planes: uniform bases + 32-bit lane offsets (host: a plane < 2^32 B)
+        eq_ad = sgpr((const float*)C2b); eq_pz = sgpr(g.eq_pz + r0 * g.eq_ldpz); eq_a = sgpr(g.eq_a + r0 * g.eq_lda); eq_b = sgpr(g.eq_b + r0 * g.eq_ldb);
+        eq_ga = sgpr(g.eq_ga + r0 * g.eq_ldga); eq_pout = sgpr(g.eq_pout + r0 * g.eq_ldpout);
+        eq_ldad = sgpr((unsigned)g.ldc2); eq_ldpz = sgpr((unsigned)g.eq_ldpz); eq_lda = sgpr((unsigned)g.eq_lda); eq_ldb = sgpr((unsigned)g.eq_ldb);
+        eq_ldga = sgpr((unsigned)g.eq_ldga); eq_ldpout = sgpr((unsigned)g.eq_ldpout);
+        era = load_qrange(g.eq_amin, g.eq_amax);
+        erb = load_qrange(g.eq_bmin, g.eq_bmax);
+        ery = load_qrange(g.eq_qmin, g.eq_qmax);
+    }
     if (quant) {
         ry1 = load_qrange(g.qy_min1, g.qy_max1);
         ry2 = (g.Q2 != nullptr) ? load_qrange(g.qy_min2, g.qy_max2) : ry1;
@@ -435,6 +461,20 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
                         ad16 = *reinterpret_cast<const uint4*>(adp + ((int64_t)b * rows_o + orow) * ldad + ocol);
                 }
             }
+            // ADDQ: this lane's (row, 4 columns) groups of the tile -- the fork's addend, the add's two code words and the producer's
+            // z -- are requested one group ahead of their use, the first before the accumulators go through LDS.  Unconditional: a
+            // group outside the tensor reads a clamped one and is masked at use.
+            struct EqIn { float4 ad, pz; unsigned int wa, wb; } ecur{};
+            auto eq_load = [&](EqIn& in, int pass) {
+                const unsigned rc = min(rowt + pass * 8 + (lane >> 3), g.M - 1);
+                const unsigned cc = col < g.N ? col : 0;
+                in.ad = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (eq_ad != nullptr) in.ad = *reinterpret_cast<const float4*>(eq_ad + (rc * eq_ldad + cc));     // (workgroup-uniform)
+                in.pz = *reinterpret_cast<const float4*>(eq_pz + (rc * eq_ldpz + cc));
+                in.wa = *reinterpret_cast<const unsigned int*>(eq_a + (rc * eq_lda + cc));
+                in.wb = *reinterpret_cast<const unsigned int*>(eq_b + (rc * eq_ldb + cc));
+            };
+            if constexpr (ADDQ) eq_load(ecur, 0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rl = (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -453,6 +493,42 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
                 Tt[rl][lr] = v;
             }
             // same-wave LDS round trip: program order + the compiler's lgkmcnt waits are sufficient
+            if constexpr (ADDQ) {
+                // g = own product + addend, then do_group of k_ewq_bwd<true> with producer b fused (fused_q.hip), on registers.  A
+                // rolled loop: unrolled, the compiler interleaves the groups and does not fit 128 VGPRs.
+#pragma unroll 1
+                for (int pass = 0; pass < 4; ++pass) {
+                    const int rl = pass * 8 + (lane >> 3);
+                    const int row = rowt + rl;
+                    const float4 t = *reinterpret_cast<const float4*>(&Tt[rl][c4]);
+                    const EqIn in = ecur;
+                    eq_load(ecur, min(pass + 1, 3));
+                    const bool ok = row < g.M && col < g.N;
+                    const bool has_ad = eq_ad != nullptr;      // no addend: g is the product itself, as fqss_qpw_bwd_x writes it
+                    const float gv[4] = {has_ad ? t.x + in.ad.x : t.x, has_ad ? t.y + in.ad.y : t.y, has_ad ? t.z + in.ad.z : t.z,
+                                         has_ad ? t.w + in.ad.w : t.w};
+                    const float zb[4] = {in.pz.x, in.pz.y, in.pz.z, in.pz.w};
+                    float o[4], ob[4], brow = 0.f, unused = 0.f;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float gj = (ok && col + e < g.N) ? gv[e] : 0.0f;
+                        float z = dec((in.wa >> (8 * e)) & 255u, era);
+                        z = z + 1.0f * dec((in.wb >> (8 * e)) & 255u, erb);
+                        o[e] = ew_plain_bwd(z, ery, gj, e_du, e_out);
+                        ob[e] = ew_producer_bwd<true>(EwProducer{}, erb, 0.0f, zb[e], o[e], true, eb_du, eb_out, unused, brow);
+                    }
+                    if (ok) {
+                        *reinterpret_cast<float4*>(eq_ga + ((unsigned)row * eq_ldga + (unsigned)col)) = make_float4(o[0], o[1], o[2], o[3]);
+                        *reinterpret_cast<float4*>(eq_pout + ((unsigned)row * eq_ldpout + (unsigned)col)) = make_float4(ob[0], ob[1], ob[2], ob[3]);
+                    }
+                    // the producer's bias gradient: sum over the 8 lanes of the row (masked groups hold zeros), fixed DPP tree
+                    brow += dpp_get<0xB1>(brow);          // quad_perm:[1,0,3,2]
+                    brow += dpp_get<0x4E>(brow);          // quad_perm:[2,3,0,1]
+                    brow += dpp_get<0x141>(brow);         // row_half_mirror
+                    if ((lane & 7) == 0) rowc[wn][wm * 64 + mi * 32 + rl] = brow;
+                }
+                return;
+            }
             const QRange ry = tfirst ? ry1 : ry2;
 #pragma unroll
             for (int pass = 0; pass < 4; ++pass) {
@@ -536,6 +612,21 @@ __global__ __launch_bounds__(256, 2) void k_qgemm(QGemmArgs g) {
         } else {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) tile_epilogue(mi, std::true_type{});
+        }
+        if constexpr (ADDQ) {
+            // row sums of the producer's gz: the two column halves in a fixed order, one plain store per row and workgroup (summed
+            // over the workgroups by fqss_bias_ws_reduce: no atomics, the same bits every run)
+            __syncthreads();
+            if (tid < g.M) g.eq_bias_ws[(int64_t)panel * g.M + tid] = rowc[0][tid] + rowc[1][tid];
+            // range partials: fp32 over the wave, fp64 into the workgroup's own slot (k_ewq_bwd's tail)
+            const float du = wave_sum63(e_du), po = wave_sum63(e_out), bdu = wave_sum63(eb_du), bpo = wave_sum63(eb_out);
+            if (lane == 63) {
+                const double dmax = (double)du / 255.0, bdmax = (double)bdu / 255.0;
+                atomicAdd(&g.eq_gacc[3 * (int64_t)panel], (double)po - dmax);
+                atomicAdd(&g.eq_gacc[3 * (int64_t)panel + 1], dmax);
+                atomicAdd(&g.eq_pgacc[3 * (int64_t)panel], (double)bpo - bdmax);
+                atomicAdd(&g.eq_pgacc[3 * (int64_t)panel + 1], bdmax);
+            }
         }
         if constexpr (MODE == 0) {
             if (quant && g.stats != nullptr) {   // workgroup-uniform: one (sum c, sum c^2) slot per workgroup, plain stores
@@ -1176,9 +1267,13 @@ extern "C" int fqss_qpw_fwdq_add(const uint8_t* xc, const int8_t* wi, const floa
 
 static int qpw_bwd_x_impl(const char* who, const float* gz1, const float* gz2, const int8_t* wiT, const float* dw, float* gx, int B,
                           int Ci, int Co1, int Co2, int M, int64_t ld_gz1, int64_t ld_gz2, int64_t ld_gx, fqss_stream_t stream,
-                          const float* addend = nullptr, int64_t ld_add = 0) {
+                          const float* addend = nullptr, int64_t ld_add = 0, const FqssAddqBwd* aq = nullptr) {
     if (B == 0 || M == 0) return FQSS_OK;   // empty input: nothing to do (a 0-element tensor has a null data pointer)
     const int Co = Co1 + Co2;
+    if (aq != nullptr) {      // g is consumed in the epilogue: ga takes the place of gx in the checks below
+        gx = aq->ga;
+        ld_gx = aq->ld_ga;
+    }
     FQSS_REQUIRE(gz1 && wiT && dw && gx && (Co2 == 0 || gz2), "null tensor");
     FQSS_REQUIRE(B >= 0 && Ci > 0 && Co1 > 0 && Co2 >= 0 && M >= 0 && ld_gz1 >= M && ld_gx >= M, "bad shape");
     FQSS_REQUIRE(Co1 % 16 == 0 && Co2 % 16 == 0 && ld_gz1 % 4 == 0 && aligned16(gz1) && aligned16(wiT) && ld_gz1 >= ((M + 3) & ~3),
@@ -1193,6 +1288,22 @@ static int qpw_bwd_x_impl(const char* who, const float* gz1, const float* gz2, c
     // a thread reads exactly the four outputs it then writes.  Up to 1024 channels this is the one launch it always was.
     const int parts = (int)cdiv(Co, 1024);
     const int part = (int)(cdiv(cdiv(Co, parts), 16) * 16);
+    if (aq != nullptr) {
+        const int64_t m4 = ((int64_t)M + 3) & ~3ll;
+        FQSS_REQUIRE(Ci <= QBM && Co <= 1024, "fused AddQ backward: Ci <= 128 (one row tile) and Co <= 1024 (one part)");
+        FQSS_REQUIRE(aq->a && aq->b && aq->amin && aq->amax && aq->bmin && aq->bmax && aq->qmin && aq->qmax && aq->gacc && aq->pz &&
+                         aq->pgacc && aq->pout && aq->ga && aq->bias_ws, "fused AddQ backward: null pointer");
+        FQSS_REQUIRE(aq->ld_a % 16 == 0 && aq->ld_b % 16 == 0 && aq->ld_a >= M && aq->ld_b >= M && aligned16(aq->a) && aligned16(aq->b),
+                     "fused AddQ backward: code rows must be 16-B aligned");
+        FQSS_REQUIRE(aligned16(aq->pz) && aligned16(aq->pout) && aq->ld_pz % 4 == 0 && aq->ld_pout % 4 == 0 && aq->ld_pz >= m4 &&
+                         aq->ld_pout >= m4 && ld_gx >= m4, "fused AddQ backward: fp32 rows must be 16-B aligned and padded to 4");
+        FQSS_REQUIRE(addend == nullptr || (int64_t)Ci * ld_add < (1ll << 30), "fused AddQ backward: a sample's plane must stay below 2^30 elements");
+        FQSS_REQUIRE((int64_t)Ci * aq->ld_pz < (1ll << 30) && (int64_t)Ci * aq->ld_pout < (1ll << 30) &&
+                         (int64_t)Ci * ld_gx < (1ll << 30) && (int64_t)Ci * aq->ld_a < (1ll << 30) && (int64_t)Ci * aq->ld_b < (1ll << 30),
+                     "fused AddQ backward: a sample's plane must stay below 2^30 elements");
+        FQSS_REQUIRE(fqss_qpw_bwd_x_addq_wgs(B, M) <= FQSS_GACC_SLOTS, "fused AddQ backward: more workgroups than range-partial slots");
+        FQSS_REQUIRE(aq->bias_ws_floats >= fqss_qpw_bwd_x_addq_wgs(B, M) * Ci, "fused AddQ backward: bias workspace too small");
+    }
     for (int k0 = 0; k0 < Co; k0 += part) {
         const int kn = Co - k0 < part ? Co - k0 : part;
         QGemmArgs g{};
@@ -1207,10 +1318,23 @@ static int qpw_bwd_x_impl(const char* who, const float* gz1, const float* gz2, c
             g.C2 = const_cast<float*>(addend); g.ldc2 = ld_add; g.sC2b = (int64_t)Ci * ld_add;
         }
         g.tiles_n = (int)cdiv(M, QBN); g.tiles_m = (int)cdiv(Ci, QBM); g.batches = B;
-        hipLaunchKernelGGL((k_qgemm<1, 3>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
+        if (aq != nullptr) {
+            g.C = nullptr;
+            g.eq_a = aq->a; g.eq_b = aq->b; g.eq_lda = aq->ld_a; g.eq_ldb = aq->ld_b;
+            g.eq_amin = aq->amin; g.eq_amax = aq->amax; g.eq_bmin = aq->bmin; g.eq_bmax = aq->bmax; g.eq_qmin = aq->qmin; g.eq_qmax = aq->qmax;
+            g.eq_pz = aq->pz; g.eq_ldpz = aq->ld_pz; g.eq_ga = aq->ga; g.eq_ldga = aq->ld_ga; g.eq_pout = aq->pout; g.eq_ldpout = aq->ld_pout;
+            g.eq_gacc = aq->gacc; g.eq_pgacc = aq->pgacc; g.eq_bias_ws = aq->bias_ws;
+            hipLaunchKernelGGL((k_qgemm<1, 3, false, true>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0,
+                               (hipStream_t)stream, g);
+        } else {
+            hipLaunchKernelGGL((k_qgemm<1, 3>), dim3(xcd_grid((int64_t)g.tiles_n * B, g.tiles_m)), dim3(256), 0, (hipStream_t)stream, g);
+        }
     }
     return launch_status(who);
 }
+
+/* workgroups of fqss_qpw_bwd_x_addq (rows of its bias workspace, range-partial slots it fills) */
+extern "C" int64_t fqss_qpw_bwd_x_addq_wgs(int B, int M) { return (B > 0 && M > 0) ? (int64_t)B * cdiv(M, QBN) : 0; }
 
 extern "C" int fqss_qpw_bwd_x(const float* gz, const int8_t* wiT, const float* dw, float* gx, int B, int Ci, int Co,
                               int M, int64_t ld_gz, int64_t ld_gx, fqss_stream_t stream) {
@@ -1223,6 +1347,55 @@ extern "C" int fqss_qpw_bwd_x_add(const float* gz, const int8_t* wiT, const floa
                                   int M, int64_t ld_gz, int64_t ld_add, int64_t ld_gx, fqss_stream_t stream) {
     FQSS_REQUIRE(addend, "null addend");
     return qpw_bwd_x_impl("fqss_qpw_bwd_x_add", gz, nullptr, wiT, dw, gx, B, Ci, Co, 0, M, ld_gz, 0, ld_gx, stream, addend, ld_add);
+}
+
+/* fqss_qpw_bwd_x_add (addend NULL: fqss_qpw_bwd_x) whose output g is the gradient at the output of a residual AddQ: that add's backward
+ * and its producer's output-quantizer backward run in the epilogue (fqss.h FqssAddqBwd); g is not written */
+extern "C" int fqss_qpw_bwd_x_addq(const float* gz, const int8_t* wiT, const float* dw, const float* addend, int B, int Ci, int Co,
+                                   int M, int64_t ld_gz, int64_t ld_add, const FqssAddqBwd* aq, fqss_stream_t stream) {
+    FQSS_REQUIRE(aq, "null record");
+    return qpw_bwd_x_impl("fqss_qpw_bwd_x_addq", gz, nullptr, wiT, dw, nullptr, B, Ci, Co, 0, M, ld_gz, 0, 0, stream, addend, ld_add, aq);
+}
+
+// bias gradients from the per-workgroup row sums of fqss_qpw_bwd_x_addq, all layers of a step in one launch (the job table travels in
+// the kernel arguments, as k_qwgrad_group's): one workgroup per (layer, 32 channels), 8 threads per channel over the workspace rows
+// w = s, s + 8, ..., combined in slice order -- a fixed order, so the same bits every run
+constexpr int BWS_MAXJOBS = 32;
+struct BiasWsJobs { FqssBiasWsJob j[BWS_MAXJOBS]; };
+__global__ __launch_bounds__(256) void k_bias_ws_reduce(BiasWsJobs jobs) {
+    __shared__ double part[8][32];
+    const FqssBiasWsJob& J = jobs.j[blockIdx.x];
+    const int nwg = J.nwg, C = J.C;
+    const int c = blockIdx.y * 32 + (threadIdx.x & 31), s = threadIdx.x >> 5;
+    double v = 0.0;
+    if (c < C)
+        for (int w = s; w < nwg; w += 8) v += (double)J.ws[(int64_t)w * C + c];
+    part[s][threadIdx.x & 31] = v;
+    __syncthreads();
+    if (s == 0 && c < C) {
+        double sum = part[0][threadIdx.x];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) sum += part[k][threadIdx.x];
+        J.gbias[c] += (float)sum;
+    }
+}
+
+extern "C" int fqss_bias_ws_reduce(const FqssBiasWsJob* jobs, int njobs, fqss_stream_t stream) {
+    if (njobs == 0) return FQSS_OK;
+    FQSS_REQUIRE(jobs && njobs > 0, "bad job list");
+    for (int i = 0; i < njobs; ++i)
+        FQSS_REQUIRE(jobs[i].ws && jobs[i].gbias && jobs[i].nwg > 0 && jobs[i].C > 0, "bad job");
+    for (int j0 = 0; j0 < njobs; j0 += BWS_MAXJOBS) {
+        const int n = njobs - j0 < BWS_MAXJOBS ? njobs - j0 : BWS_MAXJOBS;
+        BiasWsJobs t{};
+        int cmax = 0;
+        for (int i = 0; i < n; ++i) {
+            t.j[i] = jobs[j0 + i];
+            if (t.j[i].C > cmax) cmax = t.j[i].C;
+        }
+        hipLaunchKernelGGL(k_bias_ws_reduce, dim3((unsigned)n, (unsigned)cdiv(cmax, 32)), dim3(256), 0, (hipStream_t)stream, t);
+    }
+    return launch_status("fqss_bias_ws_reduce");
 }
 
 extern "C" int fqss_qpw_bwd_x2(const float* gz1, const float* gz2, const int8_t* wiT, const float* dw, float* gx, int B, int Ci,

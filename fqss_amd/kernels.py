@@ -483,6 +483,49 @@ def qpw_bwd_x(gz, wc, add=None):
     return gx
 
 
+def qpw_bwd_x_addq_ok(B, Ci, Co, M):
+    """shapes fqss_qpw_bwd_x_addq serves: one row tile, one reduction part, a range-partial slot per workgroup"""
+    return Ci <= 128 and Co <= 1024 and 0 < _lib.query("fqss_qpw_bwd_x_addq_wgs", B, M) <= GACC_DOUBLES // 3
+
+
+def qpw_bwd_x_addq(gz, wc, add, ac, amin, amax, bc, bmin, bmax, qmin, qmax, gacc, pz, pgacc, bias_ws):
+    """qpw_bwd_x(gz, wc, add=add) (add may be None) whose result is the gradient at the output of the residual AddQ fq(dec(ac) + dec(bc)), bc the output
+    codes of a conv without activation with pre-quant output pz: -> (dL/da, that conv's gz), bit for bit qpw_bwd_x + ewq_bwd_p(prod_b);
+    the gradient itself is never written.  Range partials go to gacc / pgacc; bias_ws [workgroups * Ci] fp32 receives the conv's
+    per-workgroup bias sums (bias_ws_reduce adds them to the bias gradient)."""
+    assert wc.idxT is not None
+    gz, B, Co, M, ld_gz = _bcm(gz)
+    if ld_gz % 4 != 0 or gz.data_ptr() % 16 != 0:
+        c = empty_act(tuple(gz.shape), gz.device)
+        c.copy_(gz)
+        gz, ld_gz = c, rowmat(c)[2]
+    assert (B, wc.Ci, M) == tuple(ac.shape) == tuple(bc.shape) == tuple(pz.shape)
+    ld_add = 0
+    if add is not None:
+        assert tuple(add.shape) == (B, wc.Ci, M)
+        add, ld_add = _aligned_grad(add)
+    ga, pout = empty_act((B, wc.Ci, M), gz.device), empty_act((B, wc.Ci, M), gz.device)
+    r = _lib.FqssAddqBwd()
+    r.a, r.ld_a, r.amin, r.amax = _p(ac), rowmat(ac)[2], _p(amin), _p(amax)
+    r.b, r.ld_b, r.bmin, r.bmax = _p(bc), rowmat(bc)[2], _p(bmin), _p(bmax)
+    r.qmin, r.qmax, r.gacc = _p(qmin), _p(qmax), _p(gacc)
+    r.pz, r.ld_pz, r.pgacc = _p(pz), rowmat(pz)[2], _p(pgacc)
+    r.pout, r.ld_pout, r.ga, r.ld_ga = _p(pout), rowmat(pout)[2], _p(ga), rowmat(ga)[2]
+    r.bias_ws, r.bias_ws_floats = _p(bias_ws), bias_ws.numel()
+    _lib.call("fqss_qpw_bwd_x_addq", _p(gz), _p(wc.idxT), _p(wc.dw), _p(add), B, wc.Ci, Co, M, ld_gz, ld_add, _ref(r), _stream())
+    return ga, pout
+
+
+def bias_ws_reduce(jobs):
+    """jobs: [(bias_ws, gbias, workgroups, C)] -> gbias[c] += the sum over the workspace rows in a fixed order, every layer in one launch"""
+    n = len(jobs)
+    arr = (_lib.FqssBiasWsJob * n)()
+    for r, (ws, gbias, nwg, C) in zip(arr, jobs):
+        assert ws.numel() >= nwg * C and gbias.numel() >= C
+        r.ws, r.gbias, r.nwg, r.C = _p(ws), _p(gbias), nwg, C
+    _lib.call("fqss_bias_ws_reduce", arr, n, _stream())
+
+
 def qpw_bwd_w(gz, xc, qmin_x, qmax_x, gw):
     gz, B, Co, M, ld_gz = _bcm(gz)
     if ld_gz % 4 != 0 or gz.data_ptr() % 16 != 0:

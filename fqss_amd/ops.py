@@ -21,7 +21,7 @@ ACT_NONE, ACT_PRELU, ACT_RELU = K.ACT_NONE, K.ACT_PRELU, K.ACT_RELU
 
 class QCtx:
     """what the epilogue needs to know about the activation quantizer for ONE call (host-side only)"""
-    __slots__ = ("qmode", "qmin", "qmax", "obs_ws", "gacc", "owner", "idx", "carrier", "keep_out", "prod", "no_codes", "stats", "hand", "presum", "chain", "link")
+    __slots__ = ("qmode", "qmin", "qmax", "obs_ws", "gacc", "owner", "idx", "carrier", "keep_out", "prod", "no_codes", "stats", "hand", "presum", "chain", "link", "dlink")
 
     def __init__(self, qmode=Q_BYPASS, qmin=None, qmax=None, obs_ws=None, gacc=None, owner=None):
         self.qmode, self.qmin, self.qmax, self.obs_ws, self.gacc, self.owner = qmode, qmin, qmax, obs_ws, gacc, owner
@@ -35,6 +35,7 @@ class QCtx:
         self.presum = None      # _PreSum: the AddQ that consumes this output was already evaluated by the producing GEMM
         self.chain = False      # AddQ: the caller declares that the first operand is the previous add's output and has no other consumer
         self.link = None        # _ChainLink of this call's output (EwQ): the next add of the chain finds it on the tensor
+        self.dlink = None       # _AddLink of this call's output (EwQ, a residual add): see FUSE_ADD_DGRAD
 
 
 class ActCodes:
@@ -50,7 +51,7 @@ def tag_codes(y, q):
     """attach the codes produced by the epilogue of this call to its output tensor"""
     if q.idx is not None and not CODED:
         assert not q.carrier, "codes-only carriers need the coded dataflow"
-        q.idx = q.prod = q.stats = q.hand = q.presum = q.link = None          # un-fused reference dataflow (tests): consumers see plain fp32 tensors
+        q.idx = q.prod = q.stats = q.hand = q.presum = q.link = q.dlink = None          # un-fused reference dataflow (tests): consumers see plain fp32 tensors
     if q.idx is not None:
         y._fqss_q = ActCodes(q.idx, q.qmin.detach(), q.qmax.detach())
         y._fqss_carrier = q.carrier
@@ -65,6 +66,8 @@ def tag_codes(y, q):
             y._fqss_presum, q.presum = q.presum, None
         if q.link is not None:
             y._fqss_chain, q.link = q.link, None
+        if q.dlink is not None:
+            y._fqss_addlink, q.dlink = q.dlink, None
     return y
 
 
@@ -116,6 +119,55 @@ class _ChainLink:
         self.prev, self.ac, self.amin, self.amax, self.bc, self.bmin, self.bmax = prev, ac, amin, amax, bc, bmin, bmax
         self.qmin, self.qmax, self.q, self.prod_a, self.prod_b = qmin, qmax, q, prod_a, prod_b
         self.pre = self.dummy = None
+
+
+# The backward of a residual AddQ y = fq(a + b), b the fresh output of a conv without activation, in the epilogue of the data-gradient
+# GEMM that produces dL/dy (fqss_qpw_bwd_x_addq): when y feeds exactly a two-way fork whose branches are a quantized 1x1 conv and an
+# element-wise layer (the next TCN block: its conv1 and its own residual add), that conv's dgrad + the fork's addend IS dL/dy, and
+# the add's backward runs on it in registers -- dL/dy is never written, the add's own launch (k_ewq_bwd<true>) disappears.
+FUSE_ADD_DGRAD = True   # False: every residual add runs its backward as a launch of its own
+
+
+class _AddLink:
+    """A residual AddQ whose backward may run in the dgrad epilogue of the conv that consumes its output: what that kernel needs of
+    the add (left on the add's output by EwQ.forward), whether the consumer DECLARED that the output feeds nothing but its two-way
+    fork (declare_add_dgrad), and -- once the conv's backward has run -- the add's finished results (`pre`), which its own autograd
+    node then only hands on after checking that the gradient it received is the placeholder (`dummy`) the conv returned."""
+    __slots__ = ("ac", "amin", "amax", "bc", "bmin", "bmax", "qmin", "qmax", "q", "prod_b", "fork", "pre", "dummy")
+
+    def __init__(self, ac, amin, amax, bc, bmin, bmax, qmin, qmax, q, prod_b):
+        self.ac, self.amin, self.amax, self.bc, self.bmin, self.bmax = ac, amin, amax, bc, bmin, bmax
+        self.qmin, self.qmax, self.q, self.prod_b = qmin, qmax, q, prod_b
+        self.fork = self.pre = self.dummy = None
+
+
+def declare_add_dgrad(x, x_conv):
+    """The caller declares that `x` has exactly two consumers, the two branches of the fork2 that made `x_conv`: a quantized 1x1
+    conv on `x_conv` and element-wise layers on the other branch.  If x is the output of a residual AddQ that left an _AddLink, the
+    link is handed to the conv through its branch.  Not called across an ops.cut edge: the leaf carries no link."""
+    link = getattr(x, "_fqss_addlink", None)
+    fk = getattr(x_conv, "_fqss_fork", None)
+    if link is not None and fk is not None and x_conv is not x:
+        link.fork = fk[0]
+        x_conv._fqss_addlink = link
+
+
+def _add_dgrad_args(link, fk, gz, wc, other):
+    """the arguments of K.qpw_bwd_x_addq when conv (wc)'s dgrad may take the backward of the add behind `link`, else None"""
+    if link is None or not FUSE_ADD_DGRAD or DEFER is None or link.fork is not fk or link.pre is not None or link.q.gacc is None:
+        return None
+    pb = _producer_args(link.prod_b)
+    if pb is None or pb[1] != ACT_NONE or pb[4] is None or not hasattr(DEFER, "bias_ws"):
+        return None
+    B, C, M = link.ac.shape
+    if (other is not None and tuple(other.shape) != (B, C, M)) or wc.Ci != C or gz.dim() != 3 or not K.qpw_bwd_x_addq_ok(B, C, wc.Co, M):
+        return None
+    if other is None:
+        # the fork's other branch left nothing.  Its element-wise consumer runs its backward BEFORE this conv's whenever it receives a
+        # gradient at all (this conv's gz depends on it), so nothing will come: the product alone is the fork's gradient
+        if fk.other is not None or fk.other_branch is not None or fk.fused_branch is not None:
+            return None
+    return pb
 
 
 class _PreSum:
@@ -575,6 +627,7 @@ class LinearActQ(Function):
             ctx.prod = q.prod = _Producer(z, act, slope, L.slope_param, q, L.b_param, bias)
         ctx.x_shape = x.shape
         ctx.fork = getattr(x, "_fqss_fork", None) if ((ctx.wc is not None and ctx.wc.idxT is not None) or L.kind == "convtr") else None
+        ctx.dlink = getattr(x, "_fqss_addlink", None) if (ctx.fork is not None and ctx.wc is not None) else None
         ctx.save_for_backward(None if ((ctx.xq is not None and ctx.wc is not None) or ctx.xq_tr is not None) else x, w,
                               None if ctx.plain else z, slope)
         ctx.L, ctx.act, ctx.q, ctx.has_bias = L, act, q, bias is not None
@@ -608,7 +661,17 @@ class LinearActQ(Function):
         if ctx.needs_input_grad[0]:
             fk = ctx.fork
             other = fk[0].take(fk[1], ctx.x_shape) if (fk is not None and (ctx.wc is not None or L.kind == "convtr")) else None
-            if ctx.wc is not None and other is not None:
+            pb = _add_dgrad_args(ctx.dlink, fk[0], gz, ctx.wc, other) if (ctx.wc is not None and fk is not None) else None
+            if pb is not None:
+                # ... and the input is the output of a residual add that feeds this fork alone: that add's backward on the sum, in the
+                # same epilogue.  The add's node finds its results on the link; what travels to it is a placeholder, never read.
+                dl = ctx.dlink
+                dl.pre = K.qpw_bwd_x_addq(gz, ctx.wc, other, dl.ac, dl.amin, dl.amax, dl.bc, dl.bmin, dl.bmax, dl.qmin, dl.qmax, dl.q.gacc,
+                                          pb[0], pb[3], DEFER.bias_ws(pb[4], dl.ac.shape[0], dl.ac.shape[1], dl.ac.shape[2]))
+                gx = dl.dummy = fk[0].consumed = K.empty_act(tuple(ctx.x_shape), gz.device)
+                if other is None:
+                    fk[0].fused_branch = fk[1]          # (take() found nothing to add: Fork2.backward still passes this branch through)
+            elif ctx.wc is not None and other is not None:
                 gx = K.qpw_bwd_x(gz, ctx.wc, add=other)     # + the gradient of the fork's other branch: no separate sum pass
             elif L.kind == "convtr" and other is not None:
                 gx = K.frames_conv_fwd(gz, w.reshape(w.shape[0], 1, w.shape[2]), L.stride, add=other)   # decoder: same, in its dgrad
@@ -879,6 +942,10 @@ class EwQ(Function):
             if prev is not None and tuple(prev.ac.shape) != tuple(aq_.idx.shape):
                 prev = None
             ctx.link = q.link = _ChainLink(prev, aq_.idx, aq_.qmin, aq_.qmax, bq_.idx, bq_.qmin, bq_.qmax, qmin, qmax, q, ctx.prod_a, ctx.prod_b)
+        ctx.dlink = None
+        if (FUSE_ADD_DGRAD and not q.chain and ctx.prod_b is not None and ctx.prod_a is None and act == ACT_NONE and aq_.idx.dim() == 3
+                and q.gacc is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]):
+            ctx.dlink = q.dlink = _AddLink(aq_.idx, aq_.qmin, aq_.qmax, bq_.idx, bq_.qmin, bq_.qmax, qmin, qmax, q, ctx.prod_b)
         return _carrier(out) if q.carrier else out
 
     @staticmethod
@@ -895,6 +962,19 @@ class EwQ(Function):
                     ctx.prod_a.fused = True
                 g_slope, g_min, g_max = _flush_ranges(q, slope, ctx.sp, ctx.act)
                 return ga, gb, g_slope, g_min, g_max, None, None, None, None, None, None
+        dl = ctx.dlink
+        if dl is not None and dl.pre is not None:
+            # the dgrad of the conv that consumes this add's output already ran this backward (fqss_qpw_bwd_x_addq)
+            (ga, gb), dummy, dl.pre, dl.dummy = dl.pre, dl.dummy, None, None
+            if g.data_ptr() != dummy.data_ptr():
+                raise RuntimeError("fqss_amd.ops: a residual AddQ whose backward ran in its consumer's dgrad received a gradient that is "
+                                   "not the placeholder that dgrad returned -- its output has another consumer (declare_add_dgrad was "
+                                   "called wrongly)")
+            ctx.prod_b.fused = True
+            g_slope, g_min, g_max = _flush_ranges(q, slope, ctx.sp, ctx.act)
+            if ctx.fork_a is not None:
+                ctx.fork_a[0].leave(ga, ctx.fork_a[1])
+            return ga, gb, g_slope, g_min, g_max, None, None, None, None, None, None
         pa = _producer_args(ctx.prod_a) if ctx.needs_input_grad[0] else None
         pb = _producer_args(ctx.prod_b) if (ctx.has_b and ctx.needs_input_grad[1]) else None
         if (pa is not None or pb is not None) and bf is None and ac.dim() == 3:
@@ -1111,10 +1191,12 @@ class _ForkState:
     a further element-wise consumer of that branch whose backward runs AFTER the conv's keeps accumulating into `other`, which must not
     change what Fork2.backward subtracts); Fork2.backward then passes the fused branch's gradient through -- after checking that what
     was added really is the other branch's complete gradient."""
-    __slots__ = ("other", "other_branch", "fused_branch", "n_other", "taken", "n_taken")
+    __slots__ = ("other", "other_branch", "fused_branch", "n_other", "taken", "n_taken", "consumed")
 
     def __init__(self):
         self.other, self.other_branch, self.fused_branch, self.n_other, self.taken, self.n_taken = None, None, None, 0, None, 0
+        self.consumed = None    # the placeholder the fused branch returned when its dgrad also ran the backward of the AddQ in
+                                # front of the fork (_AddLink): the fork's gradient no longer exists, nothing can be added to it
 
     def leave(self, g, branch):
         """an element-wise consumer on `branch` hands over its input gradient"""
@@ -1147,6 +1229,7 @@ class Fork2(Function):
     def backward(ctx, g1, g2):
         fk = ctx.fk
         fb, other, n_other, n_left = fk.fused_branch, fk.taken, fk.n_taken, fk.n_other
+        consumed, fk.consumed = fk.consumed, None
         fk.fused_branch, fk.other, fk.other_branch, fk.n_other, fk.taken, fk.n_taken = None, None, None, 0, None, 0
         gs = (g1, g2)
         if fb is None:
@@ -1158,6 +1241,12 @@ class Fork2(Function):
         gf, go = gs[fb], gs[1 - fb]              # gf already holds (its own gradient + `other`)
         if go is None or (n_other == 1 and n_left == 1 and go.data_ptr() == other.data_ptr()):
             return gf, None                      # `other` WAS the opposite branch's complete gradient (fqss_qpw_bwd_x_add)
+        if consumed is not None and other is None and n_left == 0:
+            return gf, None                      # no element-wise consumer left anything: `go` is autograd's materialised zero
+        if consumed is not None:
+            raise RuntimeError("fqss_amd.ops: the input of this fork is a residual AddQ whose backward already ran in the dgrad of the "
+                               "fork's conv branch, but the other branch has a further consumer whose gradient that dgrad did not see "
+                               "(declare_add_dgrad was called wrongly)")
         # the opposite branch had further consumers -- before or AFTER the conv's backward took its snapshot -- and autograd summed all
         # of them into `go`: add what the epilogue missed (go - the snapshot that was added)
         return K.axpby(K.axpby(gf, go, 1.0), other, -1.0), None

@@ -41,6 +41,9 @@ class ConvBlock(nn.Module):
         """-> (x + res_conv(f), skip_conv(f)); skip_sum / skip_add: the running skip sum and the Add layer the caller applies to
         (skip_sum, <second output>) next -- known here so that both adds can run in the res | skip GEMM's epilogue"""
         x_blk, x_res = ops.fork2(x)
+        # x feeds shared_block's conv1 and self.add, nothing else: when x is the previous block's residual add, conv1's dgrad may run
+        # that add's backward in its epilogue
+        ops.declare_add_dgrad(x, x_blk)
         f = self.shared_block(x_blk)
         # one GEMM for both (quantizing phase, graph mode); `residual` is consumed only by self.add below and `skip_out`
         # only by the skip sum of MaskGenerator.forward (or dropped): their AddQ backward also runs these convs'

@@ -162,8 +162,17 @@ def build(dev, sets=3):
     g_wr = 4.0 * (12 * 3 + 1) * NH * NB
     case("k_qwgrad_group", "student weight gradients of 25 quantized 1x1 convs in one launch (12 x (128->512 + res|skip pair) + 512->128; fp32 gz x u8 codes)",
          "hbm", 2, g_rd, g_wr, 4.0 * (12 * ((NH + NB) + (NH + 2 * NB)) + (NH + NB)) * n, grouped, flops=(12 * 3 + 1) * fl)
-    case("k_qgemm<1>", "student dgrad of 128->512 (int8 W^T x fp32 gz)", "hbm", 24, 4.0 * NH * n, 4.0 * NB * n, 4.0 * (NH + NB) * n,
+    case("k_qgemm<1>", "student dgrad of 128->512 (int8 W^T x fp32 gz): the first block's conv1", "hbm", 1, 4.0 * NH * n, 4.0 * NB * n, 4.0 * (NH + NB) * n,
          lambda i: K.qpw_bwd_x(gz_h[i % sets], wc_up), flops=fl)
+    # the conv1 dgrad of blocks 1 .. 23 also runs the backward of the residual AddQ in front of its block and of that add's res conv
+    # (ops.FUSE_ADD_DGRAD): + the fork's addend, the add's two code planes and the res conv's z in; dL/da and the res conv's gz out instead
+    # of gx (SURVEY convention: the dgrad's own boundary tensors + the 20 B per element the separate k_ewq_bwd launch carried)
+    aq_gacc, aq_pgacc = torch.zeros(K.GACC_DOUBLES, dtype=torch.float64, device=dev), torch.zeros(K.GACC_DOUBLES, dtype=torch.float64, device=dev)
+    aq_ws = torch.empty(K._lib.query("fqss_qpw_bwd_x_addq_wgs", B, M) * NB, device=dev)
+    case("k_qgemm<1>", "student dgrad of 128->512 + the fork sum + the residual AddQ backward with its res conv's output-quantizer backward", "hbm", 23,
+         (4.0 * NH + 10.0 * NB) * n, 8.0 * NB * n, 4.0 * (NH + NB) * n + 20.0 * NB * n,
+         lambda i: K.qpw_bwd_x_addq(gz_h[i % sets], wc_up, gz_b[i % sets], xc_b[i % sets], lo, hi, xc_b2[i % sets], lo, hi, lo, hi, aq_gacc,
+                                    z_b[i % sets], aq_pgacc, aq_ws), flops=fl)
     case("k_qgemm<1>", "student dgrad of the res|skip pair (K = 128+128 -> 512)", "hbm", 24, 8.0 * NB * n, 4.0 * NH * n, 4.0 * (NH + 2 * NB) * n,
          lambda i: K.qpw_bwd_x2(gz_b[i % sets], gz_b2[i % sets], pc), flops=2 * fl)
     stq = K.new_stats("qpw", B, NH, M, dev)
@@ -201,10 +210,8 @@ def build(dev, sets=3):
         return K.dwq_bwd(xc_h[i % sets], lo, hi, w_dw, b_dw, gz_h[i % sets], 4, 4, 1, slope, lo, hi, gacc, gbb, gw_dw, after=after, before=before)
     case("k_dwq_bwd<3, GA, GB>", "depthwise + PReLU + fake-quant backward + the apply pass of the gLN behind it + the rows pass of the gLN in front, "
          "C=512 (fp32 g + 2 x codes in, fp32 gx out)", "hbm", 24, 6.0 * NH * n, 4.0 * NH * n, 28.0 * NH * n, dwq_bwd_gn)
-    pgb_a, pgb_b = torch.zeros(NB, device=dev), torch.zeros(NB, device=dev)
-    case("k_ewq_bwd", "AddQ backward with BOTH operands' conv output-quantizer backward fused (residual add), C=128", "hbm", 24, 14.0 * NB * n, 8.0 * NB * n,
-         20.0 * NB * n, lambda i: K.ewq_bwd_p(xc_b[i % sets], lo, hi, xc_b2[i % sets], lo, hi, 1.0, gz_b[i % sets], 0, None, lo, hi, gacc, NB,
-                                               prod_a=(z_b[i % sets], 0, None, pgacc, pgb_a), prod_b=(z_b2[i % sets], 0, None, pgacc2, pgb_b)))
+    # (k_ewq_bwd<true>, the residual add's backward as a launch of its own -- 23 per step until every one of them moved into a conv1 dgrad
+    # epilogue, see the k_qgemm<1> cases -- is no longer launched by the cfg-2 step and has no case: 0 launches per step)
     # round 5: the 23 AddQ of the skip sum run their backward as ONE launch (k_ewq_chain_bwd): the gradient stays in registers from the top
     # level to the bottom; per level two code words + the skip conv's z in, that conv's gz out (every level on buffers of its own: 0.9 GB,
     # nothing may be served from the Infinity Cache twice)

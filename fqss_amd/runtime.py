@@ -428,6 +428,9 @@ class QuantTables:
         self.wgrad_queue = K.WgradQueue() if grouped else None
         # ... and of the row-major linears of the dual-path / transformer models (csrc/gemm_x3.hip k_gemm_x3_wq_multi)
         self.row_wgrad_queue = K.RowWgradQueue() if grouped else None
+        # bias gradients of the res convs whose output-quantizer backward ran in a dgrad epilogue (ops.FUSE_ADD_DGRAD): per layer a
+        # workspace of per-workgroup row sums, reduced for all layers of a backward segment in ONE launch of finish_backward
+        self._bias_ws, self._bias_jobs = {}, []
         # ---- per-segment views of the two finish tables (descriptor 15 = first block is renumbered per table) -----------------
         self.seg_tables = None
         if segments is not None and len(segments) > 1:
@@ -454,6 +457,17 @@ class QuantTables:
             self.wgrad_queue.jobs = []        # (a backward that never reached finish_backward leaves nothing behind)
         if self.row_wgrad_queue is not None:
             self.row_wgrad_queue.jobs = []
+        self._bias_jobs = []
+
+    def bias_ws(self, gbias, B, C, M):
+        """the workspace that fqss_qpw_bwd_x_addq fills for the layer whose bias gradient is `gbias`; queued for finish_backward"""
+        nwg = K._lib.query("fqss_qpw_bwd_x_addq_wgs", B, M)
+        key = (gbias.data_ptr(), nwg, C)
+        ws = self._bias_ws.get(key)
+        if ws is None:
+            ws = self._bias_ws[key] = torch.empty(nwg * C, dtype=torch.float32, device=gbias.device)
+        self._bias_jobs.append((ws, gbias, nwg, C))
+        return ws
 
     def finish_backward(self, seg=None):
         """after autograd (of backward segment `seg`, or of the whole network): weight STE/range gradients from the dL/dW_q arena,
@@ -464,6 +478,9 @@ class QuantTables:
             self.wgrad_queue.flush()
         if self.row_wgrad_queue is not None:
             self.row_wgrad_queue.flush()
+        if self._bias_jobs:
+            K.bias_ws_reduce(self._bias_jobs)
+            self._bias_jobs = []
         if self.det is not None:
             self.det.finish(1)      # FQSS_DETERMINISTIC=1: the depthwise / frame-path weight gradients' integer sums -> the dL/dW_q arena
         if seg is None or self.seg_tables is None:

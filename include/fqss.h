@@ -289,6 +289,33 @@ int fqss_qpw_bwd_w(const float* gz, const uint8_t* xc, const float* qmin_x, cons
 /* fqss_qpw_bwd_x + an addend of the output's shape in the epilogue (gradient of the other branch of a residual fork) */
 int fqss_qpw_bwd_x_add(const float* gz, const int8_t* wiT, const float* dw, const float* addend, float* gx, int B, int Ci,
                        int Co, int M, int64_t ld_gz, int64_t ld_add, int64_t ld_gx, fqss_stream_t stream);
+/* fqss_qpw_bwd_x_add (addend NULL: fqss_qpw_bwd_x, the fork's other branch carries no gradient) whose result g = W_q^T gz + addend is the gradient at the output of a residual AddQ y = fq_q(dec_a(a) + dec_b(b))
+ * with b the fresh output of a pointwise conv without activation (the res conv of the TCN block in front; `self.add(x_res, residual)`,
+  * reference convtasnetq.py:41): the add's backward and that conv's output-quantizer backward run on g in
+ * the GEMM's epilogue, element for element the arithmetic of fqss_ewq_bwd_p (no activation, sb = 1, operand a without a producer), and
+ * g itself is neither written nor read back.  ga [B][Ci][ld_ga] = dL/da (the add's gz), pout = the conv's gz: the bits of
+ * fqss_qpw_bwd_x_add + fqss_ewq_bwd_p.  Range partials go to slot 3 * workgroup of gacc / pgacc (FQSS_GACC_SLOTS x 3 doubles each).
+ * The conv's bias gradient is NOT accumulated with atomics: every workgroup stores its Ci row sums to bias_ws
+ * [fqss_qpw_bwd_x_addq_wgs(B, M)][Ci], and fqss_bias_ws_reduce adds their sum, taken in a fixed order, to the bias gradient -- once per
+ * step for all layers (`jobs` is a HOST array, copied into the launch; two jobs of one call must not share gbias).
+ * Serves Ci <= 128 and Co <= 1024; anything else is refused. */
+typedef struct {
+    const uint8_t* a; int64_t ld_a; const float *amin, *amax;      /* codes [B][Ci][ld_a] and range of the add's first operand */
+    const uint8_t* b; int64_t ld_b; const float *bmin, *bmax;      /* ... of its second operand = the conv's output codes */
+    const float *qmin, *qmax; double* gacc;                        /* the add's own quantizer */
+    const float* pz; int64_t ld_pz; double* pgacc;                 /* the conv's pre-quant output z and its quantizer's slots */
+    float* pout; int64_t ld_pout;                                  /* out: the conv's gz */
+    float* ga; int64_t ld_ga;                                      /* out: dL/da */
+    float* bias_ws; int64_t bias_ws_floats;                        /* out: per-workgroup row sums of pout */
+} FqssAddqBwd;
+int64_t fqss_qpw_bwd_x_addq_wgs(int B, int M);
+int fqss_qpw_bwd_x_addq(const float* gz, const int8_t* wiT, const float* dw, const float* addend, int B, int Ci, int Co,
+                        int M, int64_t ld_gz, int64_t ld_add, const FqssAddqBwd* aq, fqss_stream_t stream);
+typedef struct FqssBiasWsJob {
+    const float* ws; float* gbias;      /* [nwg][C] row sums; [C] gradient, accumulated */
+    int32_t nwg, C;
+} FqssBiasWsJob;
+int fqss_bias_ws_reduce(const FqssBiasWsJob* jobs, int njobs, fqss_stream_t stream);
 int fqss_qpw_fwd2(const uint8_t* xc, const int8_t* wi, const float* dw, const float* rw, const float* bias1,
                   const float* bias2, const float* qmin_x, const float* qmax_x, float* z1, float* z2, int B,
                   int Ci, int Co1, int Co2, int M, int64_t ld_xc, int64_t ld_z1, int64_t ld_z2,
