@@ -2,7 +2,7 @@
 // batch 2, 1 s ... plumbing, no GPU"; reference train.py:31: device = "cpu" if use_cpu).  Plain C++ (g++, OpenMP), host pointers, the
 // `stream` argument is ignored, every call is synchronous.  It serves the entry points the UN-FUSED ConvTasNet QAT step uses (the
 // per-layer kernels that the G1 layer fixtures pin: KDTrainStep(coded=False, batched_quantizers=False) with the module-path teacher)
-// and, of the evaluation side, the SDR (fqss_sdr) and the batched chunked path (fqss_splitter2_rows, fqss_chunk_gather,
+// and, of the evaluation side, the SDR (fqss_sdr), the STOI (fqss_stoi) and the batched chunked path (fqss_splitter2_rows, fqss_chunk_gather,
 // fqss_sisnr_chunks, fqss_infer_ola_chunks);
 // anything else is absent from this library and fqss_amd/_lib.py raises.  Arithmetic: the same op sequences as the HIP kernels
 // (fp32, one IEEE operation per operator: built with -ffp-contract=off; IEEE division; round-half-even), reductions in fp64.
@@ -1273,6 +1273,136 @@ int fqss_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles,
         double coh = 0.0;
         for (int i = 0; i < F; ++i) coh += b[i] * x[i];
         db[p] = (ok && std::isfinite(coh)) ? 10.0 * log10(coh / (1.0 - coh)) : (double)NAN;
+    }
+    return FQSS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ short-time objective intelligibility
+// include/fqss.h, fqss_stoi: the six steps in straight fp64 loops (a direct DFT over the 256 non-zero samples of a frame); the workspace
+// has the HIP library's size rule and is not used
+static int64_t stoi_gcd(int64_t a, int64_t b) { return b == 0 ? a : stoi_gcd(b, a % b); }
+static bool stoi_ratio_ok(int up, int down) { return up >= 1 && down >= 1 && up <= 65536 && down <= 65536 && stoi_gcd(up, down) == 1; }
+static bool stoi_shape_ok(int P, int64_t L, int up, int down) {
+    return P >= 1 && P <= 32767 && L >= 1 && stoi_ratio_ok(up, down) && L <= ((int64_t)1 << 37) / up;
+}
+static const int kStoiLo[16] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
+
+int64_t fqss_stoi_ws_doubles(int P, int64_t L, int up, int down) {
+    if (!stoi_shape_ok(P, L, up, down)) return 0;
+    const int64_t Lp = (L * up + down - 1) / down, NF = Lp > 256 ? (Lp - 256 + 127) / 128 : 0;
+    const int64_t Tmax = NF > 1 ? NF - 1 : 0, Smax = NF > 30 ? NF - 30 : 0;
+    return (int64_t)P * ((up == down ? 0 : 2 * Lp) + NF + (NF + 2) / 2 + 2 * 15 * Tmax + Smax);
+}
+
+int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
+              int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, fqss_stream_t) {
+    REQUIRE(est && ref && taps && ws && d, "null pointer");
+    REQUIRE(stoi_ratio_ok(up, down), "up / down not in 1..65536 or not reduced");
+    REQUIRE(stoi_shape_ok(P, L, up, down) && ld_e >= L && ld_r >= L, "bad shape (1 <= P <= 32767, 1 <= L <= 2^37 / up, ld >= L)");
+    REQUIRE(n_taps >= 1 && (n_taps & 1) && (up != down || n_taps == 1), "n_taps even, or not 1 at up = down = 1");
+    REQUIRE(n_taps <= 1023 && 255 * (int64_t)down + n_taps <= 1022 * (int64_t)up, "resampler outside what one workgroup stages");
+    REQUIRE(ws_doubles >= fqss_stoi_ws_doubles(P, L, up, down), "workspace shorter than fqss_stoi_ws_doubles");
+    const double EPS = 2.220446049250313e-16, PI = 3.14159265358979323846, CLIP = 1.0 + pow(10.0, 15.0 / 20.0);
+    const int64_t Lp = (L * up + down - 1) / down, NF = Lp > 256 ? (Lp - 256 + 127) / 128 : 0, Lh = (n_taps - 1) / 2;
+    std::vector<double> w(256), cs(512), sn(512);
+    for (int t = 0; t < 256; ++t) w[t] = 0.5 - 0.5 * cos(2.0 * PI * (double)(t + 1) / 257.0);
+    for (int j = 0; j < 512; ++j) {
+        cs[j] = cos(2.0 * PI * (double)j / 512.0);
+        sn[j] = sin(2.0 * PI * (double)j / 512.0);
+    }
+    for (int p = 0; p < P; ++p) {
+        std::vector<double> sig[2];      // 0: clean, 1: estimate, at 10 kHz
+        for (int s = 0; s < 2; ++s) {
+            const float* src = s == 0 ? ref + p * ld_r : est + p * ld_e;
+            sig[s].assign((size_t)Lp, 0.0);
+            if (up == down) {
+                for (int64_t i = 0; i < L; ++i) sig[s][i] = (double)src[i];
+                continue;
+            }
+#pragma omp parallel for schedule(static)
+            for (int64_t n = 0; n < Lp; ++n) {
+                const int64_t m = n * down + Lh;
+                double acc = 0.0;
+                for (int64_t k = m % up; k < n_taps; k += up) {      // u[m - k] is a sample only where up divides m - k
+                    const int64_t i = (m - k) / up;
+                    if (k <= m && i < L) acc += taps[k] * (double)src[i];
+                }
+                sig[s][n] = acc;
+            }
+        }
+        std::vector<double> e((size_t)NF);
+        std::vector<int64_t> kept;
+        double emax = -INFINITY;
+        for (int64_t f = 0; f < NF; ++f) {
+            double ss = 0.0;
+            for (int t = 0; t < 256; ++t) {
+                const double v = w[t] * sig[0][f * 128 + t];
+                ss += v * v;
+            }
+            e[f] = 20.0 * log10(sqrt(ss) + EPS);
+            emax = fmax(emax, e[f]);
+        }
+        for (int64_t f = 0; f < NF; ++f)
+            if (emax - 40.0 - e[f] < 0.0) kept.push_back(f);
+        const int64_t K = (int64_t)kept.size(), T = K > 0 ? K - 1 : 0;
+        if (T < 30) {
+            d[p] = 1e-5;
+            continue;
+        }
+        std::vector<double> tob[2];
+        for (int s = 0; s < 2; ++s) {
+            std::vector<double> sil((size_t)((K - 1) * 128 + 256), 0.0);
+            for (int64_t j = 0; j < K; ++j)
+                for (int t = 0; t < 256; ++t) sil[j * 128 + t] += w[t] * sig[s][kept[j] * 128 + t];
+            tob[s].assign((size_t)(15 * T), 0.0);
+#pragma omp parallel for schedule(static)
+            for (int64_t m = 0; m < T; ++m) {
+                double fr[256], pw[257];
+                for (int t = 0; t < 256; ++t) fr[t] = w[t] * sil[m * 128 + t];
+                for (int b = kStoiLo[0]; b < kStoiLo[15]; ++b) {
+                    double re = 0.0, im = 0.0;
+                    for (int t = 0; t < 256; ++t) {
+                        re += fr[t] * cs[(b * t) & 511];
+                        im -= fr[t] * sn[(b * t) & 511];
+                    }
+                    pw[b] = re * re + im * im;
+                }
+                for (int k = 0; k < 15; ++k) {
+                    double acc = 0.0;
+                    for (int b = kStoiLo[k]; b < kStoiLo[k + 1]; ++b) acc += pw[b];
+                    tob[s][k * T + m] = sqrt(acc);
+                }
+            }
+        }
+        double total = 0.0;
+        for (int64_t m = 30; m <= T; ++m)
+            for (int k = 0; k < 15; ++k) {
+                const double *x = &tob[0][k * T + m - 30], *y = &tob[1][k * T + m - 30];
+                double xx = 0.0, yy = 0.0, yp[30], xc[30], mx = 0.0, my = 0.0, nx = 0.0, ny = 0.0, dot = 0.0;
+                for (int c = 0; c < 30; ++c) {
+                    xx += x[c] * x[c];
+                    yy += y[c] * y[c];
+                }
+                const double scale = sqrt(xx) / (sqrt(yy) + EPS);
+                for (int c = 0; c < 30; ++c) {
+                    yp[c] = fmin(y[c] * scale, x[c] * CLIP);
+                    mx += x[c];
+                    my += yp[c];
+                }
+                mx /= 30.0;
+                my /= 30.0;
+                for (int c = 0; c < 30; ++c) {
+                    xc[c] = x[c] - mx;
+                    yp[c] -= my;
+                    nx += xc[c] * xc[c];
+                    ny += yp[c] * yp[c];
+                }
+                nx = sqrt(nx) + EPS;
+                ny = sqrt(ny) + EPS;
+                for (int c = 0; c < 30; ++c) dot += (xc[c] / nx) * (yp[c] / ny);
+                total += dot;
+            }
+        d[p] = total / (15.0 * (double)(T - 29));
     }
     return FQSS_OK;
 }

@@ -2855,6 +2855,48 @@ def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):
     return db
 
 
+STOI_RATES = (8000, 10000, 16000)
+_stoi_taps = {}
+
+
+def stoi_taps(fs, device):
+    """(taps fp64 on `device`, up, down) of fqss_stoi's resampler to 10 kHz (pystoi's resample_oct, see include/fqss.h): computed by the
+    host in fp64, cached per rate and device"""
+    import math
+    import numpy as np
+    key = (int(fs), str(device))
+    if key not in _stoi_taps:
+        g = math.gcd(10000, int(fs))
+        up, down = 10000 // g, int(fs) // g
+        if up == down:
+            h = np.ones(1)
+        else:
+            fc = 1.0 / (2.0 * max(up, down))
+            half = int(math.ceil((60.0 - 8.0) / (28.714 * fc / 10.0)))
+            h = np.kaiser(2 * half + 1, 0.1102 * (60.0 - 8.7)) * (2.0 * up * fc * np.sinc(2.0 * fc * np.arange(-half, half + 1)))
+            h = up * (h / h.sum())
+        _stoi_taps[key] = (torch.from_numpy(h).to(device), up, down)
+    return _stoi_taps[key]
+
+
+def stoi(est, ref, fs):
+    """est, ref [P, L] (rows may be pitched views; ref = the clean signals) sampled at `fs` -> short-time objective intelligibility of
+    each pair, fp64 [P]: pystoi.stoi(clean, estimate, fs, extended=False) restated, see fqss_stoi in include/fqss.h; 1e-5 where fewer
+    than 30 spectral frames are left.  Rates served: 8000, 10000, 16000 Hz"""
+    if int(fs) != fs or int(fs) not in STOI_RATES:
+        raise NotImplementedError(f"stoi: sample rate {fs} Hz is not served (resampler tap tables exist for {STOI_RATES} only)")
+    _need_gpu(est, ref)
+    est, P, L, ld_e = as_rowmat(est)
+    ref, P2, L2, ld_r = as_rowmat(ref)
+    assert (P, L) == (P2, L2), "stoi: shape mismatch"
+    taps, up, down = stoi_taps(fs, est.device)
+    n_ws = _lib.query("fqss_stoi_ws_doubles", P, L, up, down)
+    ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
+    d = torch.empty(P, device=est.device, dtype=torch.float64)
+    _lib.call("fqss_stoi", _p(est), _p(ref), _p(taps), taps.numel(), _p(ws), n_ws, _p(d), P, L, ld_e, ld_r, up, down, _stream())
+    return d
+
+
 def infer_ola(chunk, mp, out, sum_weight, start, n, seg):
     """out[d, c, start:start+n] += w * sign_d * chunk[src_d, c, :n]; sum_weight[start:start+n] += w  (triangular w over `seg`)"""
     _need_gpu(chunk, out, sum_weight)

@@ -2,8 +2,8 @@
 
 `preprocess` = global max-normalise + MSB/LSB floor-quantised channels (HIP: fqss_minmax + fqss_splitter2),
 `postprocess` = `x0 + x1 * 2^-8` (HIP: fqss_axpby).  The evaluation helpers of the reference's process.py run on the device too:
-chunked overlap-add inference with per-chunk source re-ordering, SI-SNR (fqss_sisnr_matrix) and SDR (fqss_sdr) of
-`metric_evaluation`.  STOI is the one metric left out (pystoi is third party and absent: reported as NaN).
+chunked overlap-add inference with per-chunk source re-ordering, SI-SNR (fqss_sisnr_matrix), SDR (fqss_sdr) and STOI (fqss_stoi) of
+`metric_evaluation`.  STOI is opt-in (`with_stoi=True`; pystoi is third party and absent: restated, NaN by default).
 """
 import torch
 
@@ -156,24 +156,38 @@ def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):
                  load_diag=load_diag)
 
 
-def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000, with_sdr=True):
+def stoi(est, ref, sample_rate):
+    """Short-time objective intelligibility between matching rows of est / ref [..., L] sampled at `sample_rate` (torchmetrics'
+    ShortTimeObjectiveIntelligibility(fs)(preds=est, target=ref) = pystoi.stoi(ref, est, fs), third party: the published definition
+    restated, see fqss_stoi in include/fqss.h; process.py:147).  Leading dimensions are flattened to pairs; returns fp64 [pairs] on the
+    device.  Rates served: 8000, 10000, 16000 Hz."""
+    return K.stoi(est.reshape(-1, est.shape[-1]), ref.reshape(-1, ref.shape[-1]), sample_rate)
+
+
+def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000, with_sdr=True, with_stoi=False):
     """(SI-SNR, SDR, STOI) averaged over the sources (process.py:127-154): every estimate is paired with the target of its best SI-SNR
-    (first maximum) and both metrics are taken on that pair.  The pairing stays on the device (first-maximum index + gather) and all
+    (first maximum) and the metrics are taken on that pair.  The pairing stays on the device (first-maximum index + gather) and all
     pairs go through one fqss_sdr launch.  A silent matched target makes that pair's SDR, and so the mean, NaN, as numpy.mean does in
-    the reference.  with_sdr=False leaves the SDR slot NaN (val.py's mixture baseline uses the SI-SNR slot only).  STOI (pystoi: its
-    own resampler and band matrices, third party and absent) is reported as NaN."""
+    the reference.  with_sdr=False leaves the SDR slot NaN (val.py's mixture baseline uses the SI-SNR slot only).  with_stoi=True fills
+    the STOI slot with the mean fqss_stoi of the same pairs at `sample_rate` (one more launch sequence, the same single read-back);
+    by default it stays NaN, as it was while pystoi -- third party and absent -- had no restatement here."""
     S = clean_waveforms.shape[0]
     est, clean = sep_waveform.reshape(S, -1), clean_waveforms.reshape(S, -1)
     db = K.sisnr_matrix(est, clean)
     best = db.max(dim=1, keepdim=True).values
-    if not with_sdr:
+    if not with_sdr and not with_stoi:
         return best.mean().item(), float("nan"), float("nan")
     cols = torch.arange(S, device=db.device).expand(S, S)
     first = torch.where(db == best, cols, S).min(dim=1).values          # the first maximum, as the reference's strict `>` scan
     first = torch.where(first < S, first, 0)                            # (a row of NaN: the scan keeps index 0)
-    sdr_db = K.sdr(est, clean[first])
-    sisnr, sdr_mean = torch.stack([best.mean().double(), sdr_db.mean()]).tolist()
-    return sisnr, sdr_mean, float("nan")
+    matched = clean[first]
+    means = [best.mean().double()]
+    if with_sdr:
+        means.append(K.sdr(est, matched).mean())
+    if with_stoi:
+        means.append(K.stoi(est, matched, sample_rate).mean())
+    means = torch.stack(means).tolist()                                 # the one read-back
+    return means[0], means[1] if with_sdr else float("nan"), means[-1] if with_stoi else float("nan")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -3,8 +3,9 @@
 set and report SI-SDR, its improvement over the unprocessed mixture, and SDR (fqss_sdr: torchmetrics' SignalDistortionRatio
 restated).  `dataset_cfg.name: librimix` walks `testing_cfg.test_dir` as val.py:28-92 does (mix_clean | mix_both | mix_single,
 s1..s3; whole utterances, resampled on the device); `synthetic` evaluates seeded two-speaker mixtures.  STOI (pystoi: third party,
-absent) is printed as nan.  MUSDB needs the `musdb` package (absent): refused.  `val()` returns (SI-SDR, improvement); the SDR of
-the run is in the printed result line."""
+absent) is printed as nan unless `testing_cfg.stoi: true` asks for fqss_stoi, the restated definition, at the utterance's rate.
+MUSDB needs the `musdb` package (absent): refused.  `val()` returns (SI-SDR, improvement); the SDR and the STOI of the run are in
+the printed result line."""
 import argparse
 import glob
 import os
@@ -25,21 +26,26 @@ def argument_handler():
     return p.parse_args()
 
 
+SYNTHETIC_RATE = 8000      # the synthetic mixtures stand in for the 8 kHz configs
+
+
 def val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, device):
     n_srcs = model_cfg.get("n_src", 1)
     n, L = testing_cfg.get("n_items", 4), int(testing_cfg.get("length_samples", 32000))
-    sisdr = sisdr_imp = sdr = 0.0
+    with_stoi = bool(testing_cfg.get("stoi", False))
+    sisdr = sisdr_imp = sdr = stoi = 0.0
     for i in range(n):
         mix, clean = synth_batch(1, L, seed=10_000 + i, device=device)
         mix_wav, clean_wavs = mix[0], clean[0]                         # [1, L], [S, L]
         wavs = model_infer(model, mix_wav, n_srcs=n_srcs, segment=testing_cfg.get("segment_samples", None),
                            overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs)
-        s, d, _ = metric_evaluation(wavs, clean_wavs)
+        s, d, st = metric_evaluation(wavs, clean_wavs, sample_rate=SYNTHETIC_RATE, with_stoi=with_stoi)
         base = K.sisnr_matrix(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous())
         sisdr += s
         sisdr_imp += s - torch.diagonal(base).mean().item()
         sdr += d
-    return sisdr / n, sisdr_imp / n, sdr / n
+        stoi += st
+    return sisdr / n, sisdr_imp / n, sdr / n, stoi / n
 
 
 def read_librimix(folder, n_spks=1, noisy=False):
@@ -78,21 +84,24 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
                 x = K.resample(x, fs, int(fs * ratio))
             return x[:1].unsqueeze(0), x[1:].unsqueeze(0)
 
-    sisdr = sisdr_imp = sdr = 0.0
+    with_stoi = bool(testing_cfg.get("stoi", False))
+    rate = int(int(dataset_cfg.get("sample_rate", 16000)) * ratio)       # the utterance's rate after resampling (val.py:83 passes fs too)
+    sisdr = sisdr_imp = sdr = stoi = 0.0
     for i, (mix, clean) in enumerate(Prefetcher(_Utterances(), [[k] for k in range(n)], device, depth=1)):
         mix_wav, clean_wavs = mix[0], clean[0]
         wavs = model_infer(model, mix_wav, n_srcs=n_srcs, segment=testing_cfg.get("segment_samples", None),
                            overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs,
                            chunk_batch=testing_cfg.get("chunk_batch"))
-        s, d, _ = metric_evaluation(wavs, clean_wavs)
+        s, d, st = metric_evaluation(wavs, clean_wavs, sample_rate=rate, with_stoi=with_stoi)
         # val.py:86: the sources as estimates, the mixture as target; only its SI-SNR is used
         base, _, _ = metric_evaluation(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous(), with_sdr=False)
         sisdr += s
         sisdr_imp += s - base
         sdr += d
+        stoi += st
         if (i % 500 == 0 and i > 0) or i == 1:
             print("SI-SDR={:0.3f},SI-SDR-imp={:0.3f},SDR={:0.3f}".format(sisdr / (i + 1), sisdr_imp / (i + 1), sdr / (i + 1)))
-    return sisdr / n, sisdr_imp / n, sdr / n
+    return sisdr / n, sisdr_imp / n, sdr / n, stoi / n
 
 
 def val(argv=None):
@@ -111,14 +120,14 @@ def val(argv=None):
         "No support for splitter/combiner with non QAT model."
     dataset_cfg, testing_cfg = conf["dataset_cfg"], conf.get("testing_cfg", {})
     if dataset_cfg["name"] == "librimix":
-        sisnr, imp, sdr = val_librimix(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
+        sisnr, imp, sdr, stoi = val_librimix(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "synthetic":
-        sisnr, imp, sdr = val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
+        sisnr, imp, sdr, stoi = val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "musdbhq":
         raise NotImplementedError("dataset musdbhq: val.py:95-178 reads MUSDB18-HQ through the third-party `musdb` package (absent here)")
     else:
         assert False, "Dataset {} is not supported!".format(dataset_cfg["name"])
-    print("SI-SDR={:0.2f},SI-SDR-imp={:0.2f},SDR={:0.2f},STOI={:0.3f}".format(sisnr, imp, sdr, float("nan")))
+    print("SI-SDR={:0.2f},SI-SDR-imp={:0.2f},SDR={:0.2f},STOI={:0.3f}".format(sisnr, imp, sdr, stoi))
     return sisnr, imp
 
 

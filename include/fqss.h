@@ -1246,6 +1246,40 @@ int64_t fqss_sdr_ws_doubles(int P, int64_t L, int filter_length);
 int fqss_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t L, int64_t ld_e, int64_t ld_r,
              int filter_length, int zero_mean, double load_diag, fqss_stream_t stream);
 
+/* Short-time objective intelligibility of the evaluation side (csrc/stoi.hip; process.metric_evaluation, process.py:129-152:
+ * torchmetrics' ShortTimeObjectiveIntelligibility(fs)(preds = estimate, target = clean) = pystoi.stoi(clean, estimate, fs,
+ * extended=False) of Taal et al. 2011 -- third party and absent).  The steps below were restated from memory of the published
+ * package; the kernels are pinned to THIS statement and to an independent fp64 checker (tests/helpers_stoi.py), parity with the
+ * pystoi package itself is not pinned by anything.  P pairs est[p][:L], ref[p][:L] (row strides ld_e, ld_r >= L; ref is the clean
+ * signal x, est the processed one y).  All arithmetic is fp64 on the fp32 inputs, EPS = 2^-52.
+ *  1. Resampling to 10 kHz by up / down = 10000 / fs REDUCED (1 / 1: none; 5 / 4 for 8 kHz; 5 / 8 for 16 kHz), pystoi's
+ *     resample_oct = scipy.signal.resample_poly(x, up, down, window = h / sum(h)): the host passes taps[n_taps] =
+ *     up * h / sum(h) in fp64, n_taps = 2 Lh + 1, where with fc = 1 / (2 max(up, down)): Lh = ceil((60 - 8) / (28.714 fc / 10)),
+ *     h[t] = kaiser(2 Lh + 1, beta = 0.1102 (60 - 8.7))[t + Lh] * 2 up fc sinc(2 fc t), t = -Lh .. Lh (365 taps at 8 kHz, 581 at 16 kHz).
+ *     L' = ceil(L up / down) samples: out[n] = sum_k taps[k] u[n down + Lh - k], u = the signal zero-stuffed by `up`, zero outside
+ *     (the terms in increasing k).  At up = down = 1: n_taps = 1, taps is not read, L' = L.
+ *  2. Silent frames.  w = hanning(258)[1:-1] (256 points: w[t] = 0.5 - 0.5 cos(2 pi (t + 1) / 257)); frames start at i = 0, 128, ...
+ *     with i < L' - 256, strictly (a frame ending exactly at the last sample is dropped); e_i = 20 log10(||w * x_frame_i|| + EPS) on
+ *     the clean signal only; a frame is kept iff max(e) - 40 - e_i < 0.  Both signals are rebuilt by overlap-add of their kept
+ *     windowed frames at hop 128: (K - 1) 128 + 256 samples for K kept frames.
+ *  3. Spectra.  Frames again by the same strict rule: T = K - 1 of them; each times w again, zero-padded to 512, real DFT, 257 bins.
+ *  4. Third-octave bands.  Bin b is at 10000 b / 512 Hz; the edges 150 * 2^((2k -+ 1) / 6) of band k = 0 .. 14 snap to the nearest bin
+ *     (first minimum of the squared distance): lo = 7 9 11 14 17 22 27 34 43 55 69 87 109 138 174, hi_k = lo_(k+1), hi_14 = 219.
+ *     x_tob[k][m] = sqrt(sum of |X_m[b]|^2 over lo_k <= b < hi_k), y_tob likewise.
+ *  5. Segments.  For m = 30 .. T, the 30 columns m - 30 .. m - 1 of every band: y' = min(y * (||x|| / (||y|| + EPS)),
+ *     x * (1 + 10^(15/20))) with the norms over the 30 columns; the 30-column means are subtracted from x and y'; each is divided by
+ *     (its norm + EPS); d = sum over bands, segments and columns of x * y' / (15 (T - 29)).
+ *  6. T < 30 (no frame at all included): d = 1e-5, as pystoi warns and returns.
+ * d [P] fp64 on the device.  ws: at least fqss_stoi_ws_doubles(P, L, up, down) doubles, ws_doubles its size; it need not be
+ * initialised and holds K: nothing is read back by the host.  No floating-point atomics and fixed summation orders: d is the same bit
+ * for bit from run to run.  Refused with FQSS_EINVAL: P < 1 (or above 32767), L < 1 (or L up above 2^37), ld < L, a short workspace, a null
+ * pointer, up / down not in 1..65536 or not reduced, n_taps even, n_taps != 1 at up = down = 1, and a resampler outside what one workgroup stages
+ * (n_taps > 1023 or 255 down + n_taps > 1022 up: 8 and 16 kHz are far inside, 44.1 kHz -- 31 947 taps -- is not served).
+ * fqss_stoi_ws_doubles returns 0 for arguments fqss_stoi refuses. */
+int64_t fqss_stoi_ws_doubles(int P, int64_t L, int up, int down);
+int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
+              int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, fqss_stream_t stream);
+
 /* Affine (scale, zero-point) form of the learned quantizers for the true-integer export (csrc/export_q.hip; SURVEY.md §8(f) rank 3;
  * replaces torch.fake_quantize_per_tensor_affine / per_channel_affine inside TorchWeightFakeQuantize / TorchActivationFakeQuantize /
  * TorchDymActivationFakeQuantize, qat_quant.py:15-72).  x viewed as [outer][C][inner]; scale / zp [C] on the device (C = 1: per
