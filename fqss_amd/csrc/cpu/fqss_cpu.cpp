@@ -1492,4 +1492,198 @@ int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S
     return FQSS_OK;
 }
 
+// include/fqss.h, fqss_aq_hist / fqss_aq_mse_search: the histogram-MSE activation observer in straight fp64 loops.  The workspace has the
+// layout of the HIP library's (csrc/aq_mse.hip AqLayout), so that kernels.aq_mse_search reads b, vals and e(i, j) from either.
+namespace {
+constexpr int kAqBins = FQSS_AQ_HIST_BINS, kAqRows = FQSS_AQ_MSE_MAX_ROWS, kAqMaxM = FQSS_AQ_MSE_MAX_BINS, kAqN = FQSS_AQ_MSE_N;
+struct AqLayout {
+    int64_t hdr, rows, cum, b, vals, err, total;
+};
+inline AqLayout aq_layout(int T) {
+    AqLayout w;
+    w.hdr = 0;
+    w.rows = 16;
+    w.cum = w.rows + 2 * kAqRows;
+    w.b = w.cum + (int64_t)T * (kAqBins + 1);
+    w.vals = w.b + kAqMaxM;
+    w.err = w.vals + kAqMaxM;
+    w.total = w.err + kAqN * kAqN;
+    return w;
+}
+inline bool aq_finite(float v) { return std::isfinite(v); }
+inline int aq_guess(double v, double lo, double span) {
+    const double f = (v - lo) / span * (double)kAqBins;
+    return f >= (double)kAqBins ? kAqBins - 1 : (f > 0.0 ? (int)f : 0);
+}
+inline int aq_bin(double v, double lo, double span, double step) {
+    int k = aq_guess(v, lo, span);
+    if (v < lo + (double)k * step) {
+        k = k > 0 ? k - 1 : 0;
+    } else if (k < kAqBins - 1 && v >= lo + (double)(k + 1) * step) {
+        k += 1;
+    }
+    return k;
+}
+inline double aq_cum_at(double b, double lo, double hi, const double* c) {
+    if (b < lo) return 0.0;
+    if (b >= hi) return c[kAqBins];
+    const double span = hi - lo, step = span / (double)kAqBins;
+    int k = aq_guess(b, lo, span);
+    for (int r = 0; r < 4 && k > 0 && b < lo + (double)k * step; ++r) k -= 1;
+    for (int r = 0; r < 4 && k < kAqBins - 1 && b >= lo + (double)(k + 1) * step; ++r) k += 1;
+    const double e0 = lo + (double)k * step, e1 = k == kAqBins - 1 ? hi : lo + (double)(k + 1) * step;
+    const double slope = (c[k + 1] - c[k]) / (e1 - e0);
+    return slope * (b - e0) + c[k];
+}
+}  // namespace
+
+int64_t fqss_aq_mse_ws_bytes(int T) {
+    if (T < 1 || T > kAqRows) return 0;
+    return aq_layout(T).total * (int64_t)sizeof(double);
+}
+
+int64_t fqss_aq_mse_ws_offset(int T, int what) {
+    if (T < 1 || T > kAqRows) return -1;
+    const AqLayout L = aq_layout(T);
+    switch (what) {
+        case FQSS_AQ_WS_HDR: return L.hdr;
+        case FQSS_AQ_WS_ROWS: return L.rows;
+        case FQSS_AQ_WS_CUM: return L.cum;
+        case FQSS_AQ_WS_B: return L.b;
+        case FQSS_AQ_WS_VALS: return L.vals;
+        case FQSS_AQ_WS_ERR: return L.err;
+    }
+    return -1;
+}
+
+int fqss_aq_hist_rows(const float* x, int64_t rows, int64_t cols, int64_t ld, uint32_t* obs_ws, uint32_t* hist_row, float* rng_row,
+                      fqss_stream_t) {
+    REQUIRE(x && obs_ws && hist_row && rng_row, "null pointer");
+    REQUIRE(rows >= 1 && cols >= 1 && ld >= cols && rows < ((int64_t)1 << 32) && cols < ((int64_t)1 << 32) && rows * cols < ((int64_t)1 << 32),
+            "bad shape (rows, cols >= 1, ld >= cols, rows * cols < 2^32)");
+    const float lo32 = ord2f(obs_ws[0]), hi32 = ord2f(obs_ws[1]);
+    obs_ws[0] = 0xFFFFFFFFu;
+    obs_ws[1] = 0u;
+    if (!aq_finite(lo32) || !aq_finite(hi32)) {
+        rng_row[0] = rng_row[1] = NAN;
+        return FQSS_OK;
+    }
+    rng_row[0] = lo32;
+    rng_row[1] = hi32;
+    double lo = (double)lo32, hi = (double)hi32;
+    if (lo == hi) {
+        lo -= 0.5;
+        hi += 0.5;
+    }
+    const double span = hi - lo, step = span / (double)kAqBins;
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t i = 0; i < cols; ++i) hist_row[aq_bin((double)x[r * ld + i], lo, span, step)] += 1u;
+    return FQSS_OK;
+}
+
+int fqss_aq_hist(const float* x, int64_t n, uint32_t* obs_ws, uint32_t* hist_row, float* rng_row, fqss_stream_t stream) {
+    REQUIRE(x && obs_ws && hist_row && rng_row, "null pointer");
+    REQUIRE(n >= 1 && n < ((int64_t)1 << 32), "n outside 1 .. 2^32 - 1");
+    return fqss_aq_hist_rows(x, 1, n, n, obs_ws, hist_row, rng_row, stream);
+}
+
+int fqss_aq_mse_search(const uint32_t* hist, const float* rng, int T, int n_bits, double* ws, float* qmin, float* qmax, int* ij_out,
+                       double* err_out, fqss_stream_t) {
+    REQUIRE(hist && rng && ws && qmin && qmax, "null pointer");
+    REQUIRE(T >= 1 && T <= kAqRows, "T outside 1 .. 64");
+    REQUIRE(n_bits == 8, "n_bits must be 8 (the activation grid of the fused kernels)");
+    const AqLayout L = aq_layout(T);
+    double bmin = INFINITY, bmax = -INFINITY, w = INFINITY;
+    int nv = 0;
+    for (int t = 0; t < kAqRows; ++t) ws[L.rows + 2 * t] = ws[L.rows + 2 * t + 1] = NAN;
+    for (int t = 0; t < T; ++t) {
+        double* c = ws + L.cum + (int64_t)t * (kAqBins + 1);
+        uint64_t s = 0;
+        c[0] = 0.0;
+        for (int k = 0; k < kAqBins; ++k) {
+            s += hist[(int64_t)t * kAqBins + k];
+            c[k + 1] = (double)s;
+        }
+        if (!aq_finite(rng[2 * t]) || !aq_finite(rng[2 * t + 1])) continue;
+        double lo = (double)rng[2 * t], hi = (double)rng[2 * t + 1];
+        if (lo == hi) {
+            lo -= 0.5;
+            hi += 0.5;
+        }
+        ws[L.rows + 2 * t] = lo;
+        ws[L.rows + 2 * t + 1] = hi;
+        nv += 1;
+        bmin = std::fmin(bmin, lo);
+        bmax = std::fmax(bmax, hi);
+        w = std::fmin(w, (hi - lo) / (double)kAqBins);
+    }
+    double Md = std::ceil(((bmax + w) - bmin) / w);
+    if (!(Md <= (double)kAqMaxM)) {
+        w = (bmax - bmin) / (double)(kAqMaxM - 1);
+        Md = std::fmin(std::ceil(((bmax + w) - bmin) / w), (double)kAqMaxM);
+    }
+    if (!(Md >= 2.0) || nv == 0) Md = 2.0;
+    const int M = (int)Md, K = M - 1;
+    ws[L.hdr + 0] = bmin;
+    ws[L.hdr + 1] = bmax;
+    ws[L.hdr + 2] = w;
+    ws[L.hdr + 3] = Md;
+    ws[L.hdr + 4] = (double)nv;
+    double* b = ws + L.b;
+    double* vals = ws + L.vals;
+    double* err = ws + L.err;
+#pragma omp parallel for
+    for (int m = 0; m < M; ++m) {
+        const double b0 = bmin + (double)m * w;
+        b[m] = b0;
+        if (m >= M - 1) continue;
+        const double b1 = bmin + (double)(m + 1) * w;
+        double acc = 0.0;
+        for (int t = 0; t < T; ++t) {
+            const double lo = ws[L.rows + 2 * t], hi = ws[L.rows + 2 * t + 1];
+            if (lo != lo) continue;
+            const double* c = ws + L.cum + (int64_t)t * (kAqBins + 1);
+            acc += aq_cum_at(b1, lo, hi, c) - aq_cum_at(b0, lo, hi, c);
+        }
+        vals[m] = acc;
+    }
+    if (nv == 0) {
+        if (ij_out) ij_out[0] = ij_out[1] = -1;
+        if (err_out) *err_out = NAN;
+        return FQSS_OK;
+    }
+    double sum = 0.0;
+    for (int m = 0; m < K; ++m) sum += vals[m];
+    const double b0 = b[0], bl = b[K - 1];
+    const double delta = 0.5 * (bl - b0) / (double)kAqN;
+#pragma omp parallel for
+    for (int ij = 0; ij < kAqN * kAqN; ++ij) {
+        const int i = ij / kAqN, j = ij % kAqN;
+        const double mn = b0 + delta * (double)i, mx = bl - delta * (double)j;
+        const double D = (mx - mn) / 255.0;
+        double acc = 0.0;
+        for (int m = 0; m < K; ++m) {
+            const double c = std::fmin(std::fmax(std::nearbyint((b[m] - mn) / D), 0.0), 255.0);
+            const double d = b[m] - (D * c + mn);
+            acc += (d * d) * vals[m];
+        }
+        err[ij] = acc / sum;
+    }
+    double best = INFINITY;
+    int idx = 0;
+    for (int ij = 0; ij < kAqN * kAqN; ++ij)
+        if (err[ij] < best) {
+            best = err[ij];
+            idx = ij;
+        }
+    *qmin = (float)(b0 + delta * (double)(idx / kAqN));
+    *qmax = (float)(bl - delta * (double)(idx % kAqN));
+    if (ij_out) {
+        ij_out[0] = idx / kAqN;
+        ij_out[1] = idx % kAqN;
+    }
+    if (err_out) *err_out = best;
+    return FQSS_OK;
+}
+
 }  // extern "C"

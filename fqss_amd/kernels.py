@@ -298,6 +298,78 @@ def wq_error(w, axis, qmin, qmax, n_bits):
     return err, pw
 
 
+# ------------------------------------------------------------------ histogram-MSE activation observer (csrc/aq_mse.hip)
+AQ_HIST_BINS, AQ_MSE_MAX_ROWS, AQ_MSE_MAX_BINS, AQ_MSE_N = _h("AQ_HIST_BINS", "AQ_MSE_MAX_ROWS", "AQ_MSE_MAX_BINS", "AQ_MSE_N")
+
+
+def aq_hist(x, obs_ws, hist_row, rng_row):
+    """one observation of the MSE observer (include/fqss.h, fqss_aq_hist): the 512-bin histogram of x over the (min, max) the preceding
+    OBSERVE launch left in obs_ws, added into hist_row (int32 [512], zero on entry); rng_row (fp32 [2]) = that pair; obs_ws is reset.
+    A row matrix with padded rows (an activation buffer, a crop of one) is read in place (fqss_aq_hist_rows); only a layout that is
+    neither dense nor a row matrix is gathered first."""
+    _need_gpu(x, rng_row)
+    if hist_row.dtype != torch.int32 or hist_row.numel() != AQ_HIST_BINS or not hist_row.is_contiguous() or rng_row.numel() != 2:
+        raise _lib.FqssError("aq_hist: hist_row is int32 [512] (contiguous), rng_row fp32 [2]")
+    if obs_ws.dtype != torch.int32 or obs_ws.numel() != 2 or not obs_ws.is_contiguous() or obs_ws.device != x.device:
+        raise _lib.FqssError("aq_hist: obs_ws is int32 [2] (the ordered-uint min / max words) on x's device")
+    x = x.detach()
+    if x.is_contiguous():
+        _lib.call("fqss_aq_hist", _p(x), x.numel(), _p(obs_ws), _p(hist_row), _p(rng_row), _stream())
+        return
+    rm = rowmat(x) or _rowmat_collapsed(x)
+    if rm is None:
+        x = x.contiguous()
+        rm = (1, x.numel(), x.numel())
+    _lib.call("fqss_aq_hist_rows", _p(x), rm[0], rm[1], rm[2], _p(obs_ws), _p(hist_row), _p(rng_row), _stream())
+
+
+class AqMseResult:
+    """what fqss_aq_mse_search left in its workspace, as views (tests, tools): M, b [M], vals [M - 1], err [100, 100]; ij int32 [2], best
+    float64 [1]"""
+    __slots__ = ("ws", "T", "ij", "best")
+
+    def __init__(self, ws, T, ij, best):
+        self.ws, self.T, self.ij, self.best = ws, T, ij, best
+
+    def _off(self):
+        """offsets of (b, vals, err) in the workspace, asked of the library that filled it"""
+        return tuple(_lib.query("fqss_aq_mse_ws_offset", self.T, _lib.CONSTANTS["FQSS_AQ_WS_" + w]) for w in ("B", "VALS", "ERR"))
+
+    @property
+    def M(self):
+        return int(self.ws[_lib.query("fqss_aq_mse_ws_offset", self.T, _lib.CONSTANTS["FQSS_AQ_WS_HDR"]) + 3])
+
+    @property
+    def b(self):
+        return self.ws[self._off()[0]:self._off()[0] + self.M]
+
+    @property
+    def vals(self):
+        return self.ws[self._off()[1]:self._off()[1] + self.M - 1]
+
+    @property
+    def err(self):
+        return self.ws[self._off()[2]:self._off()[2] + AQ_MSE_N * AQ_MSE_N].view(AQ_MSE_N, AQ_MSE_N)
+
+
+def aq_mse_search(hist, rng, qmin, qmax, n_bits=8, want=False):
+    """merge the T recorded histograms (hist int32 [T, 512], rng fp32 [T, 2]) and search the 100 x 100 shrunken ranges for the smallest
+    quantization error (include/fqss.h, fqss_aq_mse_search); the winner is written into qmin / qmax.  want=True: an AqMseResult"""
+    _need_gpu(rng, qmin, qmax)
+    T = hist.shape[0]
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[1] != AQ_HIST_BINS or not hist.is_contiguous() \
+            or tuple(rng.shape) != (T, 2) or not rng.is_contiguous():
+        raise _lib.FqssError("aq_mse_search: hist is int32 [T, 512], rng fp32 [T, 2], both contiguous")
+    nbytes = _lib.query("fqss_aq_mse_ws_bytes", T)
+    if nbytes <= 0:
+        raise _lib.FqssError(f"aq_mse_search: T = {T} outside 1 .. {AQ_MSE_MAX_ROWS}")
+    ws = torch.empty(nbytes // 8, device=hist.device, dtype=torch.float64)
+    ij = torch.empty(2, device=hist.device, dtype=torch.int32) if want else None
+    best = torch.empty(1, device=hist.device, dtype=torch.float64) if want else None
+    _lib.call("fqss_aq_mse_search", _p(hist), _p(rng), T, int(n_bits), _p(ws), _p(qmin), _p(qmax), _p(ij), _p(best), _stream())
+    return AqMseResult(ws, T, ij, best) if want else None
+
+
 def wq_fwd(w, axis, qmin, qmax, want_idx=False, n_bits=8):
     """n_bits: the weight width, 2..8 (codes in [-2^(n-1), 2^(n-1) - 1], always stored as int8)"""
     _need_gpu(w, qmin, qmax)

@@ -21,7 +21,7 @@ ACT_NONE, ACT_PRELU, ACT_RELU = K.ACT_NONE, K.ACT_PRELU, K.ACT_RELU
 
 class QCtx:
     """what the epilogue needs to know about the activation quantizer for ONE call (host-side only)"""
-    __slots__ = ("qmode", "qmin", "qmax", "obs_ws", "gacc", "owner", "idx", "carrier", "keep_out", "prod", "no_codes", "stats", "hand", "presum", "chain", "link", "dlink")
+    __slots__ = ("qmode", "qmin", "qmax", "obs_ws", "gacc", "owner", "idx", "carrier", "keep_out", "prod", "no_codes", "stats", "hand", "presum", "chain", "link", "dlink", "out")
 
     def __init__(self, qmode=Q_BYPASS, qmin=None, qmax=None, obs_ws=None, gacc=None, owner=None):
         self.qmode, self.qmin, self.qmax, self.obs_ws, self.gacc, self.owner = qmode, qmin, qmax, obs_ws, gacc, owner
@@ -36,6 +36,7 @@ class QCtx:
         self.chain = False      # AddQ: the caller declares that the first operand is the previous add's output and has no other consumer
         self.link = None        # _ChainLink of this call's output (EwQ): the next add of the chain finds it on the tensor
         self.dlink = None       # _AddLink of this call's output (EwQ, a residual add): see FUSE_ADD_DGRAD
+        self.out = None         # OBSERVE, owner.wants_output only (the MSE observer): the fp32 output of this call, for after_forward
 
 
 class ActCodes:
@@ -444,7 +445,15 @@ def _epilogue_fwd(z, act, slope, q):
         q.carrier = FAST and not q.keep_out
         out, q.idx = K.actq_fwd(z, act, slope, q.qmode, q.qmin, q.qmax, q.obs_ws, want_idx=True, write_out=not q.carrier)
         return _carrier(out) if q.carrier else out
-    return K.actq_fwd(z, act, slope, q.qmode, q.qmin, q.qmax, q.obs_ws)
+    return keep_observed(q, K.actq_fwd(z, act, slope, q.qmode, q.qmin, q.qmax, q.obs_ws))
+
+
+def keep_observed(q, out):
+    """behind an OBSERVE launch: leave its fp32 output on the context when the owner histograms what it observes
+    (GradientActivationFakeQuantize_MSE.after_forward consumes and clears it); the EMA quantizer never asks"""
+    if q.qmode == Q_OBSERVE and getattr(q.owner, "wants_output", False):
+        q.out = out
+    return out
 
 
 def _fuse_out_quant(q):

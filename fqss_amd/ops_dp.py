@@ -477,7 +477,7 @@ class MhaCore(Function):
                 parts.append(blk)
             aqs[i].after_forward(qs[i])
         qd = K.unary_fwd(parts[0], K.UNARY_DIVS, scale)
-        q = K.actq_fwd(qd, ops.ACT_NONE, None, qs[3].qmode, qs[3].qmin, qs[3].qmax, qs[3].obs_ws) if qs[3].qmode != ops.Q_BYPASS else qd
+        q = ops.keep_observed(qs[3], K.actq_fwd(qd, ops.ACT_NONE, None, qs[3].qmode, qs[3].qmin, qs[3].qmax, qs[3].obs_ws)) if qs[3].qmode != ops.Q_BYPASS else qd
         aqs[3].after_forward(qs[3])
         # the two quantizers whose outputs the reference throws away: observers only
         obs = [None, None]
@@ -794,7 +794,7 @@ class GluActQ(Function):
 
     @staticmethod
     def forward(ctx, x, qmin, qmax, q):
-        y = K.gluq_fwd(x, q.qmode, q.qmin, q.qmax, q.obs_ws)
+        y = ops.keep_observed(q, K.gluq_fwd(x, q.qmode, q.qmin, q.qmax, q.obs_ws))
         q.carrier, q.idx = False, None
         ctx.save_for_backward(x)
         ctx.q = q
@@ -1128,7 +1128,7 @@ class MhaCoreX(Function):
                 parts.append(blk)
             aqs[i].after_forward(qs[i])
         qd = K.unary_fwd(parts[0], K.UNARY_DIVS, scale)
-        q = K.actq_fwd(qd, ops.ACT_NONE, None, qs[3].qmode, qs[3].qmin, qs[3].qmax, qs[3].obs_ws) if qs[3].qmode != ops.Q_BYPASS else qd
+        q = ops.keep_observed(qs[3], K.actq_fwd(qd, ops.ACT_NONE, None, qs[3].qmode, qs[3].qmin, qs[3].qmax, qs[3].obs_ws)) if qs[3].qmode != ops.Q_BYPASS else qd
         aqs[3].after_forward(qs[3])
         obs = [None, None]
         for i in (4, 5):

@@ -2,7 +2,7 @@
 import torch
 
 from ..qat_layers import LayerQ
-from ..qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize, check_weight_observer
+from ..qat_quant import GradientActivationFakeQuantize, GradientWeightFakeQuantize, check_act_observer, check_weight_observer, use_mse_act_observer
 from ..qat_utils import check_lstm_quant
 from .convtasnetq import ConvTasNetQ
 from .dptnetq import DPTNetQ
@@ -45,6 +45,12 @@ def create_model(model_cfg):
 
 def quantize_model(model, quant_cfg):
     weight_observer = check_weight_observer(quant_cfg.get("weight_observer"))
+    # how the activation quantizers find their ranges in the first 50 calls (minmax: EMA of min / max | mse: histograms + range search)
+    act_obs = check_act_observer(quant_cfg.get("act_observer"))
+    if act_obs == "mse" and quant_cfg.get("qat", False) and not isinstance(model, ConvTasNetQ):
+        raise NotImplementedError(f"act_observer: mse serves ConvTasNetQ only: {type(model).__name__} observes attention logits / "
+                                  "probabilities and recurrence steps inside kernels that never materialise them, so there is no "
+                                  "tensor to histogram")
     if quant_cfg.get("qat", False):
         g = quant_cfg.get
         model.set_splitter_combiner(g("n_splitter", 1), g("n_combiner", 1))
@@ -58,6 +64,8 @@ def quantize_model(model, quant_cfg):
                              act_n_bits=g("act_n_bits", 8), inout_nl_quant=g("inout_nl_quant", False),
                              in_quant=g("in_quant", False), in_act_n_bits=g("in_act_n_bits", 8),
                              out_quant=g("out_quant", False), out_act_n_bits=g("out_act_n_bits", 8), **extra)
+        if act_obs == "mse":
+            use_mse_act_observer(model)     # beside the weight observers' walk below: one place covers every layer kind
         # what each weight quantizer's first call writes (minmax | mse): conv, transposed conv and conv2d layers, the attention
         # projections and the LSTM matrices all carry a GradientWeightFakeQuantize, so one walk of the tree covers them
         for m in model.modules():

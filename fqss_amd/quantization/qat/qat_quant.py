@@ -6,6 +6,8 @@ quantization/qat/qat_quant.py; the arithmetic runs in the HIP kernels of csrc/fq
 
   linear_quantize                    qat_quant.py:125-147  -> fqss_actq_fwd/bwd, fqss_wq_fwd_bits/bwd_bits
   GradientActivationFakeQuantize     qat_quant.py:206-242  -> observer: fqss_actq_fwd(OBSERVE)+fqss_observer_ema
+  GradientActivationFakeQuantize_MSE qat_quant.py:245-326  -> observer: fqss_actq_fwd(OBSERVE)+fqss_aq_hist per call, fqss_aq_mse_search
+                                                            at the end of call 50 (`act_observer: mse`; csrc/aq_mse.hip)
   GradientWeightFakeQuantize         qat_quant.py:350-381  -> fqss_wq_observe / fqss_wq_fwd_bits / fqss_wq_bwd_bits
                                                             (`weight_observer: mse`: fqss_wq_observe_mse on the first call)
 
@@ -20,6 +22,8 @@ Supported widths:
 Deliberate differences (documented in DESIGN.md):
   * no host syncs: the reference does `.item()` + `assert max >= min` on every training forward
     (qat_quant.py:235-238); here nothing reads device memory from the host.
+  * the MSE activation observer searches at the END of its 50th call (the reference: at the start of the 51st; call 50 does not read the
+    ranges), its histogram edges are fp64 (numpy: fp32 for fp32 input) and its merged grid is capped at 65536 points (include/fqss.h).
   * asymmetric (sym=False on weights, sym=True on activations) and scale_grad=True quantizers raise NotImplementedError: no
     FQSS config reaches them.
 """
@@ -45,6 +49,18 @@ def check_weight_observer(name):
         return WEIGHT_OBSERVERS[0]
     if name not in WEIGHT_OBSERVERS:
         raise ValueError(f"weight_observer must be {WEIGHT_OBSERVERS[0]!r} or {WEIGHT_OBSERVERS[1]!r}, got {name!r}")
+    return name
+
+
+ACT_OBSERVERS = ("minmax", "mse")
+
+
+def check_act_observer(name):
+    """`model_cfg.quantization.act_observer`: absent (None) or "minmax" -> the 50-call EMA of min / max, "mse" -> the histogram search"""
+    if name is None:
+        return ACT_OBSERVERS[0]
+    if name not in ACT_OBSERVERS:
+        raise ValueError(f"act_observer must be {ACT_OBSERVERS[0]!r} or {ACT_OBSERVERS[1]!r}, got {name!r}")
     return name
 
 
@@ -170,6 +186,48 @@ class GradientActivationFakeQuantize(nn.Module):
         return ops.tag_codes(y, q)
 
 
+class GradientActivationFakeQuantize_MSE(GradientActivationFakeQuantize):
+    """The same quantizer with the reference's histogram observer (qat_quant.py:245-326): each of the first 50 calls adds a 512-bin
+    histogram of the tensor it observes (fqss_aq_hist, behind the fused OBSERVE launch that finds the tensor's min / max); the end of
+    call 50 merges them and takes the best of 100 x 100 shrunken (min, max) pairs by quantization error (fqss_aq_mse_search).  No EMA:
+    the ranges stay (-0.5, 0.5) until the search.  Same parameters and state_dict keys as the EMA quantizer; the histograms live in
+    persistent=False buffers, freed by the search."""
+
+    wants_output = True       # ops.keep_observed: the OBSERVE launch leaves its fp32 output on the QCtx for after_forward
+
+    def __init__(self, gradient_based, n_bits=8, sym=False, scale_grad=False):
+        super().__init__(gradient_based, n_bits=n_bits, sym=sym, scale_grad=scale_grad)
+        self.hist_n_bins = K.AQ_HIST_BINS
+        self.register_buffer("_hist", None, persistent=False)
+        self.register_buffer("_hist_rng", None, persistent=False)
+        self.set_scratch(True)
+
+    def set_scratch(self, present):
+        """allocate (zero counts, void rows) or free the [max_observations, 512] histograms and their [max_observations, 2] ranges"""
+        if not present:
+            self._hist = self._hist_rng = None
+        elif self._hist is None:
+            dev = self.min_range.device
+            self._hist = torch.zeros(self.max_observations, self.hist_n_bins, dtype=torch.int32, device=dev)
+            self._hist_rng = torch.full((self.max_observations, 2), float("nan"), dtype=torch.float32, device=dev)
+
+    def after_forward(self, q):
+        if q.qmode != ops.Q_OBSERVE:
+            return
+        out, q.out = q.out, None
+        if out is None:
+            raise RuntimeError("GradientActivationFakeQuantize_MSE: this call observed without handing over its output (the layer's "
+                               "OBSERVE launch does not materialise the tensor it observes); act_observer: mse cannot serve it")
+        t = self.n_iter - 1
+        if self._hist is None or not 0 <= t < self._hist.shape[0] or self._hist.shape[0] > K.AQ_MSE_MAX_ROWS:
+            raise RuntimeError(f"GradientActivationFakeQuantize_MSE: no histogram row for observation {t + 1} "
+                               f"(max_observations = {self.max_observations}, at most {K.AQ_MSE_MAX_ROWS})")
+        K.aq_hist(out, self._obs_ws, self._hist[t], self._hist_rng[t])
+        if self.n_iter == self.max_observations:
+            K.aq_mse_search(self._hist[:self.n_iter], self._hist_rng[:self.n_iter], self.min_range.data, self.max_range.data, self.n_bits)
+            self.set_scratch(False)
+
+
 class GradientWeightFakeQuantize(nn.Module):
     """Per-output-channel symmetric weight quantizer at n_bits = 2 to 8; the first call only records amax/amin (`observer` =
     "minmax") or the best shrunken copy of that pair by squared weight error (`observer` = "mse")."""
@@ -235,6 +293,23 @@ def get_activation_quantizer(gradient_based=True, nl=False, n_bits=8):
     if nl:
         raise NotImplementedError("mu-law (inout_nl_quant) quantizer: unreachable from the FQSS configs (load_model.py:61)")
     return GradientActivationFakeQuantize(gradient_based, n_bits=n_bits)
+
+
+def use_mse_act_observer(model):
+    """`act_observer: mse`: every GradientActivationFakeQuantize of a freshly quantized model (no call yet) is replaced, in place in its
+    parent, by a GradientActivationFakeQuantize_MSE built from the same arguments; a quantizer two parents share stays shared"""
+    new = {}
+    for parent in list(model.modules()):
+        for name, child in list(parent.named_children()):
+            if type(child) is GradientActivationFakeQuantize:
+                if child.n_iter != 0:
+                    raise RuntimeError("use_mse_act_observer: the model has already observed")
+                if id(child) not in new:
+                    q = GradientActivationFakeQuantize_MSE(child.min_range.requires_grad, n_bits=child.n_bits).to(child.min_range.device)
+                    q.observer_mode, q.never_called = child.observer_mode, child.never_called
+                    new[id(child)] = q
+                setattr(parent, name, new[id(child)])
+    return model
 
 
 def get_weight_quantizer(gradient_based=True, weight_shape=(1, 1, 1), n_bits=8, ch_out_idx=0):

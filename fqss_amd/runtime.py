@@ -713,6 +713,10 @@ class KDTrainStep:
             raise RuntimeError(f"KDTrainStep.state_dict: {self.pending + int(self._open)} micro-batch(es) of an accumulation window are "
                                "pending; call flush() first (their gradients are not part of the stored state)")
         aqs, wqs = self._quantizers()
+        if self._world() > 1 and any(getattr(m, "wants_output", False) and m.observing() for _, m in aqs):
+            raise NotImplementedError("KDTrainStep.state_dict: inside the observer phase of act_observer: mse every rank holds its own "
+                                      "histograms, which no file carries at world > 1; write the checkpoint after the first "
+                                      f"{aqs[0][1].max_observations} steps (README, \"MSE activation observer\")")
         c = lambda t: t.detach().cpu().clone()
         held = {id(p) for p in self.arena.params}
         rank_ranges = None
@@ -750,6 +754,9 @@ class KDTrainStep:
         if rr is not None and int(sd["world"]) != self._world():
             raise ValueError(f"KDTrainStep.load_state_dict: this state was written at world size {int(sd['world'])} while the ranks still "
                              f"held their own observer ranges; it resumes at that world size only, not at {self._world()}")
+        for n, m in aqs:
+            if getattr(m, "wants_output", False):       # MSE observer: its histograms travel inside the observer phase and are gone after it
+                m.set_scratch(f"{n}._hist" in sd["buffers"])
         buffers, frozen = dict(self.model.named_buffers()), {n: p for n, p in self.model.named_parameters()}
         for kind, have, want in (("buffers", buffers, sd["buffers"]), ("frozen parameters", frozen, sd["frozen"])):
             bad = [n for n, t in want.items() if n not in have or have[n].shape != t.shape]

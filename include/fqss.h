@@ -1280,6 +1280,62 @@ int64_t fqss_stoi_ws_doubles(int P, int64_t L, int up, int down);
 int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
               int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, fqss_stream_t stream);
 
+/* Histogram-MSE activation observer (csrc/aq_mse.hip; GradientActivationFakeQuantize_MSE, qat_quant.py:245-326 of the reference, which runs
+ * np.histogram, merge_hist and the 100 x 100 search of mse_minmax_range on the host).  The statement is that algorithm in fp64 with two
+ * deviations: the edges are fp64 (numpy makes fp32 edges for fp32 input) and the merged grid is capped at FQSS_AQ_MSE_MAX_BINS points.
+ *
+ * fqss_aq_hist records ONE observation: x, n fp32 values (1 <= n < 2^32); obs_ws, the ordered-uint (min, max) the preceding OBSERVE launch
+ * wrote; hist_row, FQSS_AQ_HIST_BINS uint32 counts, ZERO on entry; rng_row, 2 fp32.
+ *  1. lo, hi = the decoded obs_ws pair; rng_row = (lo, hi).  lo or hi not finite: the row is VOID, rng_row = (NaN, NaN), no counts (the
+ *     reference raises there).
+ *  2. lo == hi: the edges run over (lo - 0.5, hi + 0.5), as np.histogram does.
+ *  3. Edges, fp64: step = (hi - lo) / 512, E[k] = lo + k * step for k < 512, E[512] = hi.
+ *  4. x goes to the k with E[k] <= x < E[k + 1]; the last bin is closed on the right.  numpy's floor((x - lo) / (hi - lo) * 512) (512 -> 511)
+ *     is the first guess only: it is lowered by one where x < E[k] and raised by one where x >= E[k + 1] and k < 511, as numpy does.
+ *  5. obs_ws is left at {0xFFFFFFFF, 0} (as fqss_observer_ema leaves it).
+ * Integer atomics only: the counts are the same bits every run and on any stream.  x outside [lo, hi] (an obs_ws that is not x's own)
+ * is counted in the nearest end bin.
+ * fqss_aq_hist_rows is the same observation over the rows * cols values of a row matrix x[r * ld + c] (ld >= cols, 1 <= rows * cols < 2^32;
+ * any alignment): the padded activation buffers are histogrammed in place.  fqss_aq_hist(x, n, ...) is its rows = 1, cols = n.
+ *
+ * fqss_aq_mse_search merges T rows (1 <= T <= FQSS_AQ_MSE_MAX_ROWS; hist [T][512] uint32, rng [T][2] fp32) and searches the ranges; n_bits
+ * must be 8.  Every row uses the edges E_t of steps 2-3 over its own (lo_t, hi_t).
+ *  Merge (merge_hist): over the non-void rows bmin = min lo_t, bmax = max hi_t, w = min_t (hi_t - lo_t) / 512 (after step 2's widening);
+ *   M = ceil(((bmax + w) - bmin) / w) points b[m] = bmin + m * w.  M > FQSS_AQ_MSE_MAX_BINS (or not finite): w = (bmax - bmin) / 65535 and
+ *   M = min(ceil(((bmax + w) - bmin) / w), 65536) -- the reference would allocate the array.  vals[m] = sum over the non-void rows, in
+ *   increasing t, of C_t(b[m + 1]) - C_t(b[m]), m < M - 1, where C_t is np.interp over (E_t, c_t), c_t the exact integer cumulative
+ *   counts: 0 for b < lo_t, the row's total for b >= hi_t, else slope * (b - E_t[k]) + c_t[k] with E_t[k] <= b < E_t[k + 1] and
+ *   slope = (c_t[k + 1] - c_t[k]) / (E_t[k + 1] - E_t[k]).
+ *  Search (mse_minmax_range, N = FQSS_AQ_MSE_N = 100) over the K = M - 1 left edges b[0 .. K - 1] and their weights:
+ *   delta = 0.5 * (b[K - 1] - b[0]) / 100; candidate (i, j): mn = b[0] + delta * i, mx = b[K - 1] - delta * j, D = (mx - mn) / 255,
+ *   y = D * clip(rint((b - mn) / D), 0, 255) + mn (rint: half to even, torch.round), err = (sum (b - y)^2 * vals) / sum vals.  The first
+ *   strict minimum in (i, j) lexical order wins (ties go to the smaller 100 i + j; a NaN error never wins; no winner: (0, 0)).
+ *  Outputs, all on the device: *qmin = (float)mn, *qmax = (float)mx, ij_out (nullable) = {i, j}, err_out (nullable) = the winning error.
+ *  All rows void: qmin / qmax are left untouched, ij_out = {-1, -1}, err_out = NaN.
+ * Every candidate's sum is taken in a fixed order (a fixed stride over the lanes of one wave, the tile order, the fixed DPP tree) and no
+ * floating-point atomic is used: the same bits every run.  ws: fqss_aq_mse_ws_bytes(T) bytes (0 for a T outside 1..64), 16-B aligned, need
+ * not be initialised; it keeps b, vals and the error table e(i, j) for the caller's tests.  fqss_aq_mse_ws_offset(T, what) says where, in
+ * doubles from the start of ws: what = FQSS_AQ_WS_HDR (bmin, bmax, w, M, number of non-void rows), _ROWS ([64][2]: lo_t, hi_t, NaN = void),
+ * _CUM ([T][513] cumulative counts), _B ([65536]), _VALS ([65536]), _ERR ([100][100]); -1 for a T or a `what` it does not know.  Both
+ * libraries answer from the one layout function their kernels use. */
+#define FQSS_AQ_HIST_BINS 512
+#define FQSS_AQ_MSE_MAX_ROWS 64
+#define FQSS_AQ_MSE_MAX_BINS 65536
+#define FQSS_AQ_MSE_N 100
+int fqss_aq_hist(const float* x, int64_t n, uint32_t* obs_ws, uint32_t* hist_row, float* rng_row, fqss_stream_t stream);
+int fqss_aq_hist_rows(const float* x, int64_t rows, int64_t cols, int64_t ld, uint32_t* obs_ws, uint32_t* hist_row, float* rng_row,
+                      fqss_stream_t stream);
+int fqss_aq_mse_search(const uint32_t* hist, const float* rng, int T, int n_bits, double* ws, float* qmin, float* qmax, int* ij_out,
+                       double* err_out, fqss_stream_t stream);
+int64_t fqss_aq_mse_ws_bytes(int T);
+#define FQSS_AQ_WS_HDR 0
+#define FQSS_AQ_WS_ROWS 1
+#define FQSS_AQ_WS_CUM 2
+#define FQSS_AQ_WS_B 3
+#define FQSS_AQ_WS_VALS 4
+#define FQSS_AQ_WS_ERR 5
+int64_t fqss_aq_mse_ws_offset(int T, int what);
+
 /* Affine (scale, zero-point) form of the learned quantizers for the true-integer export (csrc/export_q.hip; SURVEY.md §8(f) rank 3;
  * replaces torch.fake_quantize_per_tensor_affine / per_channel_affine inside TorchWeightFakeQuantize / TorchActivationFakeQuantize /
  * TorchDymActivationFakeQuantize, qat_quant.py:15-72).  x viewed as [outer][C][inner]; scale / zp [C] on the device (C = 1: per
