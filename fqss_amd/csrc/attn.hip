@@ -16,11 +16,9 @@
 // min / max of the logits and of the probabilities for exactly that purpose.
 #include <stdlib.h>
 
-#include "fqss_dev.h"
+#include "fqss_mfma.h"
 
 namespace fqss {
-
-typedef float f32x16a __attribute__((ext_vector_type(16)));
 
 template <int HD>
 __device__ __forceinline__ float dot_row(const float (&q)[HD], const float* __restrict__ k) {
@@ -236,11 +234,11 @@ __global__ __launch_bounds__(256) void k_attn_bwd_mfma(const float* __restrict__
     // ---- loop A: the wave owns query tile `it`: dQ_it = sum_jt dS K_jt, via the transposed logits tile T = K_jt Q_it^T
     for (int it = blockIdx.y * 4 + wave; it < NT; it += 4 * gridDim.y) {
         const float m_c = Ms[it * 32 + c], il_c = Is[it * 32 + c], D_c = Ds[it * 32 + c];
-        f32x16a dq;
+        f32x16 dq;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[r] = 0.f;
         for (int jt = 0; jt < NT; ++jt) {
-            f32x16a T, dPt;
+            f32x16 T, dPt;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { T[r] = 0.f; dPt[r] = 0.f; }
 #pragma unroll
@@ -269,11 +267,11 @@ __global__ __launch_bounds__(256) void k_attn_bwd_mfma(const float* __restrict__
     // ---- loop B: the wave owns key tile `jt`: dK_jt = sum_it dS^T Q_it, dV_jt = sum_it P^T dO_it, via S = Q_it K_jt^T
     for (int jt = blockIdx.y * 4 + wave; jt < NT; jt += 4 * gridDim.y) {
         const bool jv = jt * 32 + c < L;
-        f32x16a dk, dv;
+        f32x16 dk, dv;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dk[r] = 0.f; dv[r] = 0.f; }
         for (int it = 0; it < NT; ++it) {
-            f32x16a S, dP;
+            f32x16 S, dP;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
 #pragma unroll
@@ -332,7 +330,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd_mfma(const float* __restrict__
     for (int it = blockIdx.y * 4 + wave; it < NT; it += 4 * gridDim.y) {
         float m = -INFINITY, mn = INFINITY;
         for (int jt = 0; jt < NT; ++jt) {
-            f32x16a T;
+            f32x16 T;
 #pragma unroll
             for (int r = 0; r < 16; ++r) T[r] = 0.f;
 #pragma unroll
@@ -347,11 +345,11 @@ __global__ __launch_bounds__(256) void k_attn_fwd_mfma(const float* __restrict__
         m = fmaxf(m, __shfl_xor(m, 32, 64));
         mn = fminf(mn, __shfl_xor(mn, 32, 64));
         float l = 0.f;
-        f32x16a acc;
+        f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         for (int jt = 0; jt < NT; ++jt) {
-            f32x16a T;
+            f32x16 T;
 #pragma unroll
             for (int r = 0; r < 16; ++r) T[r] = 0.f;
 #pragma unroll

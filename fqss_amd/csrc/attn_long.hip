@@ -16,7 +16,7 @@
 // reference runs two quantizers on them and discards the results (qat_layers.py:907-909).
 #include <stdlib.h>
 
-#include "fqss_dev.h"
+#include "fqss_mfma.h"
 
 namespace fqss {
 
@@ -234,7 +234,6 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv(const float* __restric
 // registers; a workgroup (4 waves = 128 queries) streams 32-key K / V tiles through LDS.  Scores are computed TRANSPOSED,
 // T = K_tile Q^T: lane (c, half) holds query c and 16 of the 32 keys, so the row max / sum of the online softmax are in-lane
 // reductions plus one exchange between the lane halves, and exp(T - m) is already the A operand of O += P V_tile.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ int tile_row(int r, int lk) { return (r & 3) + 8 * (r >> 2) + 4 * lk; }     // row of accumulator register r
 
 // a 32-row tile of one head moves global -> registers -> LDS in two steps, so the loads of tile t+1 are in flight while tile t is
@@ -531,7 +530,6 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_mfma(const float* __re
     }
 }
 
-
 // ------------------------------------------------------------------------------------------------------------------
 // The same three passes on the bf16 matrix cores (16x the fp32 MFMA rate): every fp32 operand -- q, k, v, dO, and the probabilities
 // and dS computed in between -- is split EXACTLY into three bf16 pieces (8 mantissa bits each) and the six partial products above
@@ -543,12 +541,9 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_mfma(const float* __re
 //     k-step s, i.e. exp(T - m) (and dS) in registers ARE the A operands of the second product, as in the fp32 form;
 //   * the lane's own row (q; k / v in the dk/dv pass; dO) is the B operand, split once into registers;
 //   * the B operand of the second product (V, K, dO, Q as [row = k][d = n]) comes out of the same planes through the transposing
-//     LDS read ds_read_tr16_b64 (the idiom of csrc/qgemm.hip).
+//     LDS read ds_read_tr16_b64 (fqss_mfma.h).
 // Needs 16-B aligned rows (float4 global loads); the fp32-MFMA kernels above remain for everything else.
 // ------------------------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 // Workgroups are handed to the 8 XCDs round-robin by linear id; every XCD has its own 4 MB L2.  With blockIdx.x = query block the 27
 // blocks that stream the SAME K / V of a head land on 8 different L2s, and 32 heads x 1.8 MB do not fit any of them: PMC showed 4.7x the
 // algorithmic bytes fetched (profiles/r03_pmc_traffic_cfg345.txt).  Remapped: linear id l -> XCD l % 8, slot l / 8; the heads h with
@@ -567,7 +562,6 @@ __device__ __forceinline__ void al_block(int& bx, int& by) {
 
 __device__ __forceinline__ int krow(int r, int lk) { return 16 * (r >> 3) + 8 * lk + (r & 7); }
 __device__ __forceinline__ int kappa(int c) { return (c & 16) + 8 * ((c >> 2) & 1) + (c & 3) + 4 * ((c >> 3) & 1); }
-__device__ __forceinline__ float al_trunc(float f) { return __uint_as_float(__float_as_uint(f) & 0xFFFF0000u); }
 
 // exp(x) for x <= 0 (a logit minus the row maximum) as v_exp_f32(x log2 e): the rounding of the product is |x| 2^-24 relative in the
 // result, far below the fp32 noise of the dot products; -inf -> 0
@@ -576,33 +570,13 @@ __device__ __forceinline__ float al_exp(float x) { return __builtin_amdgcn_exp2f
 struct Frag3 {
     bf16x8 p[3];      // head, middle, tail
 };
-// 8 fp32 values -> three bf16x8 (v_perm picks the high halves of two fp32 words = truncation; the remainders are exact)
+// 8 fp32 values -> three bf16x8
 __device__ __forceinline__ Frag3 split8(const float (&x)[8]) {
-    union { bf16x8 v; unsigned int w[4]; } h, m, l;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = x[2 * q], b = x[2 * q + 1];
-        const float ar = a - al_trunc(a), br = b - al_trunc(b);
-        const float al = ar - al_trunc(ar), bl = br - al_trunc(br);
-        h.w[q] = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-        m.w[q] = __builtin_amdgcn_perm(__float_as_uint(br), __float_as_uint(ar), 0x07060302u);
-        l.w[q] = __builtin_amdgcn_perm(__float_as_uint(bl), __float_as_uint(al), 0x07060302u);
-    }
     Frag3 f;
-    f.p[0] = h.v; f.p[1] = m.v; f.p[2] = l.v;
+    split3_pack8(x, f.p[0], f.p[1], f.p[2]);
     return f;
 }
 
-// the six products, smallest first: (A piece, B piece) = l.h, h.l, m.m, m.h, h.m, h.h
-#define FQSS_X3_PRODUCTS(ACC, A, B)                                                                   \
-    do {                                                                                                \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16((A).p[2], (B).p[0], ACC, 0, 0, 0);               \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16((A).p[0], (B).p[2], ACC, 0, 0, 0);               \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16((A).p[1], (B).p[1], ACC, 0, 0, 0);               \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16((A).p[1], (B).p[0], ACC, 0, 0, 0);               \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16((A).p[0], (B).p[1], ACC, 0, 0, 0);               \
-        ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16((A).p[0], (B).p[0], ACC, 0, 0, 0);               \
-    } while (0)
 
 // a 32-row tile of one head: global (float4, rows clamped into the operand) -> registers -> three bf16 planes in LDS
 template <int HD>
@@ -629,14 +603,7 @@ struct Tile3 {
             const float x[4] = {ok ? v[u].x : 0.f, ok ? v[u].y : 0.f, ok ? v[u].z : 0.f, ok ? v[u].w : 0.f};
             unsigned int w[3][2];
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float a = x[2 * q], c = x[2 * q + 1];
-                const float ar = a - al_trunc(a), cr = c - al_trunc(c);
-                const float al = ar - al_trunc(ar), cl = cr - al_trunc(cr);
-                w[0][q] = __builtin_amdgcn_perm(__float_as_uint(c), __float_as_uint(a), 0x07060302u);
-                w[1][q] = __builtin_amdgcn_perm(__float_as_uint(cr), __float_as_uint(ar), 0x07060302u);
-                w[2][q] = __builtin_amdgcn_perm(__float_as_uint(cl), __float_as_uint(al), 0x07060302u);
-            }
+            for (int q = 0; q < 2; ++q) split3_pack2(x[2 * q], x[2 * q + 1], w[0][q], w[1][q], w[2][q]);
 #pragma unroll
             for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(&pl[p][j][d]) = make_uint2(w[p][0], w[p][1]);
         }
@@ -664,16 +631,11 @@ __device__ __forceinline__ Frag3 frag_rows(const unsigned short (*pl)[32][LD], i
 // B operand of a second product: B[k = tile row 16 ks + 8 lh + 0..7][n = d0 + (lane & 31)] through the transposing read
 template <int LD>
 __device__ __forceinline__ Frag3 frag_cols(const unsigned short (*pl)[32][LD], int ks, int d0, int lane) {
-    const int gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-    const int kr = ks * 16 + 8 * (gq >> 1) + tq, nc = d0 + 16 * (gq & 1) + 4 * tp;
+    const TrLane tl = tr_lane(lane);
+    const int kr = ks * 16 + tl.kr(), nc = tl.nc(d0);
     Frag3 f;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
-        union { bf16x8 v; s16x4 h[2]; } u;
-        u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&pl[p][kr][nc]));
-        u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&pl[p][kr + 4][nc]));
-        f.p[p] = u.v;
-    }
+    for (int p = 0; p < 3; ++p) f.p[p] = lds_read_tr_bf16x8(pl[p], kr, nc);
     return f;
 }
 // the lane's own row as a B operand: x[16 ks + 8 lk + 0..7]
@@ -731,7 +693,7 @@ __global__ __launch_bounds__(256) void k_attn_long_fwd_x3(const float* __restric
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) ka[ks] = frag_rows<LD>(Kp, kap, ks, lk);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) FQSS_X3_PRODUCTS(T0, ka[ks], qb[ks]);
+        for (int ks = 0; ks < KS; ++ks) x3_products(T0, ka[ks].p, qb[ks].p);
         if (nj < 32) {                                // the last tile: padding keys leave the softmax
 #pragma unroll
             for (int r = 0; r < 16; ++r) T0[r] = krow(r, lk) < nj ? T0[r] : -INFINITY;
@@ -786,7 +748,7 @@ __global__ __launch_bounds__(256) void k_attn_long_fwd_x3(const float* __restric
 #pragma unroll
             for (int nd = 0; nd < ND; ++nd) {
                 const Frag3 vb = frag_cols<LD>(Vp, s2, 32 * nd, lane);
-                FQSS_X3_PRODUCTS(acc[nd], pa[s2], vb);
+                x3_products(acc[nd], pa[s2].p, vb.p);
             }
     }
     l += __shfl_xor(l, 32, 64);
@@ -875,8 +837,8 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_q_x3(const float* __restr
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const Frag3 ka = frag_rows<LD>(Kp, kap, ks, lk), va = frag_rows<LD>(Vp, kap, ks, lk);
-            FQSS_X3_PRODUCTS(T0, ka, qb[ks]);
-            FQSS_X3_PRODUCTS(U0, va, gb[ks]);
+            x3_products(T0, ka.p, qb[ks].p);
+            x3_products(U0, va.p, gb[ks].p);
         }
         if (nj < 32) {
 #pragma unroll
@@ -898,7 +860,7 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_q_x3(const float* __restr
 #pragma unroll
             for (int nd = 0; nd < ND; ++nd) {
                 const Frag3 kb = frag_cols<LD>(Kp, s2, 32 * nd, lane);
-                FQSS_X3_PRODUCTS(acc[nd], da[s2], kb);
+                x3_products(acc[nd], da[s2].p, kb.p);
             }
     }
     if (lk == 0 && live) dsum[(int64_t)bh * g.Lq + i_own] = D;
@@ -969,8 +931,8 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_x3(const float* __rest
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const Frag3 qa = frag_rows<LD>(Qp, kap, ks, lk), ga = frag_rows<LD>(Gp, kap, ks, lk);
-            FQSS_X3_PRODUCTS(T0, qa, kb[ks]);
-            FQSS_X3_PRODUCTS(U0, ga, vb[ks]);
+            x3_products(T0, qa.p, kb[ks].p);
+            x3_products(U0, ga.p, vb[ks].p);
         }
         Frag3 pa[2], da[2];
 #pragma unroll
@@ -990,8 +952,8 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_x3(const float* __rest
 #pragma unroll
             for (int nd = 0; nd < ND; ++nd) {
                 const Frag3 gr = frag_cols<LD>(Gp, s2, 32 * nd, lane), qr = frag_cols<LD>(Qp, s2, 32 * nd, lane);
-                FQSS_X3_PRODUCTS(av[nd], pa[s2], gr);
-                FQSS_X3_PRODUCTS(ak[nd], da[s2], qr);
+                x3_products(av[nd], pa[s2].p, gr.p);
+                x3_products(ak[nd], da[s2].p, qr.p);
             }
     }
 #pragma unroll
@@ -1006,7 +968,6 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_x3(const float* __rest
         }
     }
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // CODED operands (the student in its quantizing phase): q, k, v arrive as the 8-bit codes of their quantizers, x = delta c + lo
@@ -1049,7 +1010,7 @@ __device__ __forceinline__ bf16x8 codes_to_bf(uint2 w) {
     codes_to_f(w, c);
     union { bf16x8 v; unsigned int u[4]; } r;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) r.u[q] = __builtin_amdgcn_perm(__float_as_uint(c[2 * q + 1]), __float_as_uint(c[2 * q]), 0x07060302u);
+    for (int q = 0; q < 4; ++q) r.u[q] = pack_bf2(c[2 * q], c[2 * q + 1]);
     return r.v;
 }
 
@@ -1084,12 +1045,9 @@ __device__ __forceinline__ bf16x8 frag_rows1(const unsigned short (*pl)[LD], int
 }
 template <int LD>
 __device__ __forceinline__ bf16x8 frag_cols1(const unsigned short (*pl)[LD], int ks, int d0, int lane) {
-    const int gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-    const int kr = ks * 16 + 8 * (gq >> 1) + tq, nc = d0 + 16 * (gq & 1) + 4 * tp;
-    union { bf16x8 v; s16x4 h[2]; } u;
-    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&pl[kr][nc]));
-    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&pl[kr + 4][nc]));
-    return u.v;
+    const TrLane tl = tr_lane(lane);
+    const int kr = ks * 16 + tl.kr(), nc = tl.nc(d0);
+    return lds_read_tr_bf16x8(pl, kr, nc);
 }
 // the lane's own query row from its codes: (dq' c + lo_q) * dk, split in three (the same operations in the forward and in the dq pass)
 __device__ __forceinline__ Frag3 own_q_scaled(const unsigned char* __restrict__ row, int ks, int lk, const QRange rq, float dk) {
@@ -1426,7 +1384,7 @@ __global__ __launch_bounds__(256) void k_attn_long_bwd_kv_c(const unsigned char*
             for (int nd = 0; nd < ND; ++nd) {
                 const Frag3 gr = frag_cols<LD>(Gp, s2, 32 * nd, lane);
                 const bf16x8 qr = frag_cols1<LD>(Qp, s2, 32 * nd, lane);
-                FQSS_X3_PRODUCTS(av[nd], pa[s2], gr);
+                x3_products(av[nd], pa[s2].p, gr.p);
                 FQSS_X3_A3_B1(ak[nd], da[s2], qr);
             }
     }

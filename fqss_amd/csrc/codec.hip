@@ -10,7 +10,7 @@
 // ResidualErrorBlock (qat_layers.py:1028-1039, 1189-1192); F.conv_transpose1d of ConvTr1dDecoderQ /
 // ResidualErrorBlock (qat_layers.py:1330-1341, 1194-1202) and their autograd.
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
-#include "fqss_dev.h"
+#include "fqss_mfma.h"
 
 namespace fqss {
 
@@ -257,17 +257,6 @@ __global__ __launch_bounds__(256) void k_ola_convtr_fwd(const void* __restrict__
     }
 }
 
-
-// the four codes of a word de-quantised like csrc/fused_q.hip's dec4 (delta * c + min in two roundings)
-__device__ __forceinline__ void ola_dec4(unsigned int w, const QRange& r, float (&v)[4]) {
-    v[0] = r.delta * (float)(w & 255u) + r.lo;
-    v[1] = r.delta * (float)((w >> 8) & 255u) + r.lo;
-    v[2] = r.delta * (float)((w >> 16) & 255u) + r.lo;
-    v[3] = r.delta * (float)(w >> 24) + r.lo;
-}
-
-typedef float f32x4m __attribute__((ext_vector_type(4)));
-
 // The (16, 8) decoder on the fp32 matrix cores: frames x taps = sum over channels of x[c][frame] * w[c][tap] as v_mfma_f32_16x16x4_f32
 // steps of four channels (bit for bit a k-ordered fmaf chain).  A lane owns FOUR consecutive frames of one channel -- one float4, or four
 // codes in one dword -- and they feed four accumulator tiles (tile j = frames mb + 4 i + j, i = 0 .. 15), so the operand row is read
@@ -294,9 +283,9 @@ __global__ __launch_bounds__(256) void k_ola_mfma16(const void* __restrict__ x_,
     if (MODE == 1) rx = load_qrange(qmin, qmax);
     const int cw = ((C + 15) / 16) * 4;               // channels per wave, a multiple of the MFMA's 4
     const int c_beg = wave * cw, c_end = min(C, c_beg + cw);
-    f32x4m acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = f32x4m{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t xb = (int64_t)n * C * ld_x + mld, fb = (MODE == 2) ? (int64_t)(n / NS) * C * ld_f + mld : 0;
     for (int c0 = c_beg; c0 < c_end; c0 += 4 * U) {
         float4 xa[U], xf2[U];
@@ -315,7 +304,7 @@ __global__ __launch_bounds__(256) void k_ola_mfma16(const void* __restrict__ x_,
             const bool cok = c0 + 4 * u + lk < c_end;  // channels past this wave's range contribute zeros
             float v[4];
             if (MODE == 1) {
-                ola_dec4(xc[u], rx, v);
+                dec4(xc[u], rx, v);
             } else {
                 v[0] = xa[u].x; v[1] = xa[u].y; v[2] = xa[u].z; v[3] = xa[u].w;
                 if (MODE == 2) {
@@ -377,11 +366,11 @@ __global__ __launch_bounds__(256) void k_frames_wgrad_mfma(const void* __restric
     const int mbeg = blockIdx.z * mchunk, mend = min(M, mbeg + mchunk);
     QRange ra{0.f, 1.f, 1.f};
     if (CODED) ra = load_qrange(qmin, qmax);
-    f32x4m acc[TC][NT];
+    f32x4 acc[TC][NT];
 #pragma unroll
     for (int t = 0; t < TC; ++t)
 #pragma unroll
-        for (int u = 0; u < NT; ++u) acc[t][u] = f32x4m{0.f, 0.f, 0.f, 0.f};
+        for (int u = 0; u < NT; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* sn = sig + (int64_t)n * sig_ns;     // (one input channel of a [N][Ci][T] signal: sig_ns = Ci T, gw rows Ci K apart)
     int64_t arow[TC];
 #pragma unroll
@@ -398,7 +387,7 @@ __global__ __launch_bounds__(256) void k_frames_wgrad_mfma(const void* __restric
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     float d[4];
-                    ola_dec4(wq[q], ra, d);
+                    dec4(wq[q], ra, d);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) av[t][4 * q + e] = d[e];
                 }

@@ -26,13 +26,6 @@ namespace fqss {
 constexpr int kGnSlots = 64;       // partial-sum slots per sample (one per stats workgroup)
 constexpr int kSlots = FQSS_GACC_SLOTS;
 
-__device__ __forceinline__ void dec4(unsigned int w, const QRange& r, float (&v)[4]) {
-    v[0] = dec(w & 255u, r);          // v_cvt_f32_ubyte0..3 + mul + add (two roundings, like the reference)
-    v[1] = dec((w >> 8) & 255u, r);
-    v[2] = dec((w >> 16) & 255u, r);
-    v[3] = dec(w >> 24, r);
-}
-
 // ---------------------------------------------------------------------------------------------
 // codes -> fp32
 // ---------------------------------------------------------------------------------------------
@@ -1235,7 +1228,6 @@ __global__ __launch_bounds__(256, FQSS_EWQ_WAVES) void k_ewq_bwd(const uint8_t* 
         }
     }
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // The backward of a CHAIN of AddQ layers in one launch (round 5): out_l = fq_l(dec(out_{l-1}) + dec(b_l)), l = 0 .. n-1, where each

@@ -18,11 +18,9 @@
 #include <stdlib.h>
 
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
-#include "fqss_dev.h"
+#include "fqss_mfma.h"
 
 namespace fqss {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct GemmArgs {
     const float* A;
@@ -231,8 +229,6 @@ __global__ __launch_bounds__(256) void k_gemm_f32(GemmArgs g) {
             }
         }
 }
-
-static inline int64_t rup4(int64_t v) { return (v + 3) & ~(int64_t)3; }
 
 // a_kc / b_kc: which dimension of the operand is contiguous in memory
 static int launch_gemm(const GemmArgs& g, bool a_kc, bool b_kc, bool atomic, int batch, hipStream_t s, const char* what) {

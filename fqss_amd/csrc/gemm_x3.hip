@@ -17,12 +17,9 @@
 #include <type_traits>
 
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
-#include "fqss_dev.h"
+#include "fqss_mfma.h"
 
 namespace fqss {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct GemmArgs3 {
     const float* A;
@@ -65,15 +62,6 @@ struct GemmArgs3 {
 // 61 KB for a 128 x 128 float tile pair = two workgroups per CU; 49 KB lets a third one in.
 constexpr int XBK = 32, XLDK = 32;
 __device__ __forceinline__ int xsw(int row, int k) { return (((k >> 3) ^ (row >> 2)) & 3) * 8 + (k & 7); }
-
-__device__ __forceinline__ unsigned short x_bf(float f) { return (unsigned short)(__float_as_uint(f) >> 16); }
-__device__ __forceinline__ float x_tr(float f) { return __uint_as_float(__float_as_uint(f) & 0xFFFF0000u); }
-__device__ __forceinline__ void x_split3(float g, unsigned short& b1, unsigned short& b2, unsigned short& b3) {
-    const float h1 = x_tr(g), r1 = g - h1, h2 = x_tr(r1), r2 = r1 - h2;   // exact: each piece has <= 8 significant bits
-    b1 = x_bf(h1);
-    b2 = x_bf(h2);
-    b3 = x_bf(r2);
-}
 
 // ROWS = rows of this operand's tile (64 or 128); KC = the k dimension is the contiguous one in memory
 // sr = stride between rows, sk = stride along k; r0 / nrows: first row of the tile and the operand's row count
@@ -124,7 +112,7 @@ struct TileIO {
                 if (sc_ != nullptr) { e[0] *= sv_.x; e[1] *= sv_.y; e[2] *= sv_.z; e[3] *= sv_.w; }
                 unsigned short h[3][4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) x_split3((rv && k0_ + k + q < kend_) ? e[q] : 0.f, h[0][q], h[1][q], h[2][q]);
+                for (int q = 0; q < 4; ++q) split3((rv && k0_ + k + q < kend_) ? e[q] : 0.f, h[0][q], h[1][q], h[2][q]);
 #pragma unroll
                 for (int s = 0; s < 3; ++s)
                     *reinterpret_cast<uint2*>(&pl[s][r][xsw(r, k)]) = make_uint2((unsigned)h[s][0] | ((unsigned)h[s][1] << 16), (unsigned)h[s][2] | ((unsigned)h[s][3] << 16));
@@ -142,7 +130,7 @@ struct TileIO {
                 for (int q = 0; q < 4; ++q) {
                     const float t = (rv && k0_ + kb * 4 + q < kend_) ? e[q][rr] : 0.f;
                     rs_[rr] += t;
-                    x_split3(t, h[0][q], h[1][q], h[2][q]);
+                    split3(t, h[0][q], h[1][q], h[2][q]);
                 }
 #pragma unroll
                 for (int s = 0; s < 3; ++s)
@@ -268,7 +256,7 @@ struct TileIOQ {
             for (int q = 0; q < 4; ++q) {
                 const unsigned int byte = (v[q] >> (8 * rr)) & 0xFFu;
                 const float f = SIGNED ? (float)(int)(signed char)byte : (float)byte;
-                h[q] = (rv && k0_ + kb * 4 + q < kend_) ? x_bf(f) : (unsigned short)0;
+                h[q] = (rv && k0_ + kb * 4 + q < kend_) ? bf_bits(f) : (unsigned short)0;
             }
             *reinterpret_cast<uint2*>(&pl[0][rb * 4 + rr][xsw(rb * 4 + rr, kb * 4)]) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
         }
@@ -380,16 +368,17 @@ __device__ __forceinline__ void x3_body(GemmArgs3 g, const int bx, const int by,
                         bfr[p][ni] = *reinterpret_cast<const bf16x8*>(&Bs[p][wn * (32 * NI) + ni * 32 + lr][xsw(lr, kstep * 16 + 8 * lh)]);
                 }
             }
-            // smallest partial products first: l.h, h.l, m.m, m.h, h.m, h.h   (coded B: l.c, m.c, h.c)
+            // smallest partial products first: the six of fqss_mfma.h   (coded B: l.c, m.c, h.c)
             constexpr int NPROD = BQ ? 3 : 6;
-            constexpr int IA[6] = {2, BQ ? 1 : 0, BQ ? 0 : 1, 1, 0, 0}, IB[6] = {0, BQ ? 0 : 2, BQ ? 0 : 1, 0, 1, 0};
 #pragma unroll
-            for (int sp = 0; sp < NPROD; ++sp)
+            for (int sp = 0; sp < NPROD; ++sp) {
+                const int ia = BQ ? 2 - sp : kX3A[sp], ib = BQ ? 0 : kX3B[sp];
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[IA[sp]][mi], bfr[IB[sp]][ni], acc[mi][ni], 0, 0, 0);
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ia][mi], bfr[ib][ni], acc[mi][ni], 0, 0, 0);
+            }
         }
         __syncthreads();
         if (kt + 1 < nkt_r) {
@@ -541,15 +530,13 @@ __global__ __launch_bounds__(256) void k_gemm_x3_wq_multi(X3WMulti m) {
     x3_body<false, false, true, MI, NI, 1>(g, bx, by, bz);
 }
 
-static inline int64_t rup4x(int64_t v) { return (v + 3) & ~(int64_t)3; }
-
 // true when the 16-B vector loads of k_gemm_x3 are legal for this problem
 static bool x3_ok(const GemmArgs3& g, bool a_kc, bool b_kc, bool atomic) {
     bool ok = aligned16(g.A) && aligned16(g.B);
-    if (a_kc) ok = ok && g.sAk == 1 && g.sAi % 4 == 0 && g.sAi >= rup4x(g.K);
-    else      ok = ok && g.sAi == 1 && g.sAk % 4 == 0 && g.sAk >= rup4x(g.M);
-    if (b_kc) ok = ok && g.sBk == 1 && g.sBj % 4 == 0 && g.sBj >= rup4x(g.K);
-    else      ok = ok && g.sBj == 1 && g.sBk % 4 == 0 && g.sBk >= rup4x(g.N);
+    if (a_kc) ok = ok && g.sAk == 1 && g.sAi % 4 == 0 && g.sAi >= rup4(g.K);
+    else      ok = ok && g.sAi == 1 && g.sAk % 4 == 0 && g.sAk >= rup4(g.M);
+    if (b_kc) ok = ok && g.sBk == 1 && g.sBj % 4 == 0 && g.sBj >= rup4(g.K);
+    else      ok = ok && g.sBj == 1 && g.sBk % 4 == 0 && g.sBk >= rup4(g.N);
     if (atomic) ok = ok && g.kchunk % XBK == 0;
     return ok;
 }

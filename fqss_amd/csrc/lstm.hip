@@ -134,39 +134,6 @@ __global__ __launch_bounds__(1024) void k_lstm_fwd(const float* __restrict__ pre
         if (step + u < S) one_step(step + u, pf[u]);
 }
 
-// Gate non-linearities of the H = 128 forward: ONE short dependent chain for both kinds (a step's critical path runs through it
-// twice: gate, then tanh(c)), fp32-grade results.  e = 2^t on v_exp_f32 with t = -x log2(e) (sigmoid) or -2 |x| log2(e) (tanh), the
-// rounding of that product and of the constant carried as a first-order factor (1 + t_lo ln 2) folded into the FMAs that form
-// 1 +- e; the quotient n / (1 + e) (n = 1: sigmoid, n = 1 - e: tanh) as v_rcp_f32 and one residual correction; tanh below |x| = 0.36,
-// where 1 - e cancels, is x + x^3 P(x^2) (P: the degree-3 interpolant of (tanh(sqrt u) / sqrt u - 1) / u on the Chebyshev nodes of
-// [0, 0.36^2], 2.3e-9 relative in exact arithmetic).  Arguments are clamped to +-87 (the results there are already 0 / 1 / +-1 to
-// fp32).  Measured against float64 (tools/lstm_gate_err.py, tests/test_gpu_dptnet.py::test_lstm_gate_functions): sigmoid <= 3.5 ulp
-// (<= 1.5 for x > 0), tanh <= 2.6 ulp, either within 1.0e-7 of the exact value -- v_exp_f32 itself is good to ~1.5 ulp.
-__device__ __forceinline__ float gate_fn(float x, bool th) {
-    const float a = fabsf(x);
-    const float z = __builtin_amdgcn_fmed3f(th ? a : x, -87.0f, 87.0f);
-    const float kh = th ? -2.8853900432586669921875f : -1.44269502162933349609375f;      // fl(-2 log2 e), fl(-log2 e)
-    const float kl = th ? -3.851925849e-08f : -1.925962925e-08f;                             // the constants' own rounding
-    const float t = kh * z;
-    const float tl = fmaf(kl, z, fmaf(kh, z, -t));
-    const float e = __builtin_amdgcn_exp2f(t);
-    const float corr = fmaf(tl, 0.693147182464599609375f, 1.0f);
-    const float d = fmaf(e, corr, 1.0f);
-    const float n = th ? fmaf(-e, corr, 1.0f) : 1.0f;
-    const float r = __builtin_amdgcn_rcpf(d);
-    float q = n * r;
-    q = fmaf(fmaf(-d, q, n), r, q);
-    // v_med3_f32 returns min3 when an input is NaN: the clamp above would launder a NaN pre-activation into sigmoid ~ 1.7e-38.  A NaN
-    // must stay a NaN (libm's did): one v_cmp_u + v_cndmask off the critical chain
-    if (!th) return (x != x) ? x : q;
-    const float u = a * a;
-    float p = fmaf(u, 0.019728317856788635f, -0.0537986196577549f);
-    p = fmaf(u, p, 0.13332897424697876f);
-    p = fmaf(u, p, -0.3333333134651184f);
-    const float small = fmaf(a * u, p, a);
-    return copysignf(a < 0.36f ? small : q, x);
-}
-
 __global__ void k_lstm_gate_fn(const float* __restrict__ x, float* __restrict__ sg, float* __restrict__ th, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {

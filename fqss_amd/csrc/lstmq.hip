@@ -38,30 +38,7 @@ enum { Q_IH = 0, Q_HH, Q_ADD0, Q_SIG0, Q_SIG1, Q_SIG2, Q_TANH0, Q_TANH1, Q_MUL0,
 struct LstmqRanges { const float* p[2][kNQ][2]; };   // [direction][quantizer][min, max] device scalars
 struct LstmqGaccs { double* p[2][kNQ]; };            // [direction][quantizer] FQSS_GACC_SLOTS x 3 doubles
 
-// the gate functions of the H = 128 float forward (lstm.hip gate_fn, verbatim: what fqss_lstm_gate_fn evaluates)
-__device__ __forceinline__ float gate_fn(float x, bool th) {
-    const float a = fabsf(x);
-    const float z = __builtin_amdgcn_fmed3f(th ? a : x, -87.0f, 87.0f);
-    const float kh = th ? -2.8853900432586669921875f : -1.44269502162933349609375f;
-    const float kl = th ? -3.851925849e-08f : -1.925962925e-08f;
-    const float t = kh * z;
-    const float tl = fmaf(kl, z, fmaf(kh, z, -t));
-    const float e = __builtin_amdgcn_exp2f(t);
-    const float corr = fmaf(tl, 0.693147182464599609375f, 1.0f);
-    const float d = fmaf(e, corr, 1.0f);
-    const float n = th ? fmaf(-e, corr, 1.0f) : 1.0f;
-    const float r = __builtin_amdgcn_rcpf(d);
-    float q = n * r;
-    q = fmaf(fmaf(-d, q, n), r, q);
-    if (!th) return (x != x) ? x : q;
-    const float u = a * a;
-    float p = fmaf(u, 0.019728317856788635f, -0.0537986196577549f);
-    p = fmaf(u, p, 0.13332897424697876f);
-    p = fmaf(u, p, -0.3333333134651184f);
-    const float small = fmaf(a * u, p, a);
-    return copysignf(a < 0.36f ? small : q, x);
-}
-
+// (the gate functions are those of the H = 128 float forward: gate_fn of fqss_dev.h, what fqss_lstm_gate_fn evaluates)
 __device__ __forceinline__ float fq(float t, const QRange& r) {
     float c, u;
     bool inr;

@@ -27,14 +27,9 @@
 #include <type_traits>
 
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
-#include "fqss_dev.h"
+#include "fqss_mfma.h"
 
 namespace fqss {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // block tile 128(m) x 64(n) x 32(k): 4 waves as 2x2, each 64x32 (2 MFMA 32x32x16 tiles).  The narrow N tile keeps
 // LDS/VGPR use low enough for 3-4 workgroups per CU, whose load / MFMA / store phases then overlap each other
@@ -45,31 +40,12 @@ constexpr int LDN = 96;    // bf16 per row of an n-contiguous image (64 + 32 pad
 constexpr int LDT = 36;    // fp32 per row of the epilogue staging tile (32 + 4 pad, 16-B aligned rows)
 constexpr int WGRAD_BLOCKS = 256;   // one workgroup per CU: the fp32 atomics of the epilogue cost ~20 ns per workgroup-tile, more slices lose
 
-__device__ __forceinline__ unsigned short f2bf_trunc(float f) { return (unsigned short)(__float_as_uint(f) >> 16); }
-__device__ __forceinline__ float bf_trunc(float f) { return __uint_as_float(__float_as_uint(f) & 0xFFFF0000u); }
-
-// exact 3-way split g = b1 + b2 + b3 (each bf16-representable)
-__device__ __forceinline__ void split3(float g, unsigned short& b1, unsigned short& b2, unsigned short& b3) {
-    const float h1 = bf_trunc(g);
-    const float r1 = g - h1;
-    const float h2 = bf_trunc(r1);
-    const float r2 = r1 - h2;
-    b1 = f2bf_trunc(h1);
-    b2 = f2bf_trunc(h2);
-    b3 = f2bf_trunc(r2);
-}
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct QStage {          // one k-tile of global loads of one thread (which members are live depends on the mode)
     f32x4 a[4];          // MODE 0/1: a[0] reinterpreted as 16 int8 codes; MODE 3: 16 fp32
     f32x4 b[2];          // MODE 1/3: 8 fp32
     u32x2 bq;            // MODE 0: 8 u8 codes
     int kch;             // IMP dgrad: the channel (reduction row / taps) of this thread's B row -- the index of its delta_w
 };
-__device__ __forceinline__ void q_load16(f32x4& d, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory"); }
-__device__ __forceinline__ void q_load8(u32x2& d, const void* p) { asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(d) : "v"(p) : "memory"); }
 template <int MODE, int N>
 __device__ __forceinline__ void q_wait(QStage& st) {
     if constexpr (MODE == 0)
@@ -224,11 +200,11 @@ __global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
     const int64_t gldb1 = sgpr(g.ldb), gldb2 = (MODE == 0) ? gldb1 : sgpr(g.ldb2);
     auto load_tiles = [&](QStage& st, int k0) {
         if constexpr (ACODES) {
-            q_load16(st.a[0], (const signed char*)g.A + (int64_t)a_row_c * g.lda + min(k0 + a_k, g.K - 16));
+            gload16(st.a[0], (const signed char*)g.A + (int64_t)a_row_c * g.lda + min(k0 + a_k, g.K - 16));
         } else {
             const float* A = (const float*)g.A + (int64_t)b * g.sAb + (int64_t)a_row_c * g.lda;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) q_load16(st.a[q], A + min(k0 + a_k + 4 * q, g.K - 4));
+            for (int q = 0; q < 4; ++q) gload16(st.a[q], A + min(k0 + a_k + 4 * q, g.K - 4));
         }
         const int kk = min(k0 + bk_row, g.K - 1);
         if constexpr (IMP) {
@@ -245,17 +221,17 @@ __global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
             st.kch = ci;
             const float* Bp = (const float*)gB1 + (int64_t)ci * gldb1 + (g.imp_base + th * g.imp_row_step + tw * g.imp_col_step);
             const int c0 = min(j0 + bk_n, g.imp_cmax);               // (4-B aligned 16-B requests: a tap's shift breaks the alignment)
-            q_load16(st.b[0], Bp + c0);
-            q_load16(st.b[1], Bp + c0 + 4);
+            gload16(st.b[0], Bp + c0);
+            gload16(st.b[1], Bp + c0 + 4);
         } else if constexpr (MODE == 0) {
             const unsigned char* Bp = (const unsigned char*)gB1 + (int64_t)kk * gldb1;
-            q_load8(st.bq, Bp + min(j0 + bk_n, (int)gldb1 - 8));   // groups past the row (columns >= N) re-read its tail
+            gload8(st.bq, Bp + min(j0 + bk_n, (int)gldb1 - 8));   // groups past the row (columns >= N) re-read its tail
         } else {
             const bool h1 = kk < g.K1;
             const int ldk = (int)(h1 ? gldb1 : gldb2);              // row length (multiple of 4, >= N): clamp inside the row;
             const float* Bp = (const float*)(h1 ? gB1 : gB2) + (int64_t)(h1 ? kk : kk - g.K1) * ldk;
-            q_load16(st.b[0], Bp + min(j0 + bk_n, ldk - 4));        // a clamped group only feeds output columns >= N
-            q_load16(st.b[1], Bp + min(j0 + bk_n + 4, ldk - 4));
+            gload16(st.b[0], Bp + min(j0 + bk_n, ldk - 4));        // a clamped group only feeds output columns >= N
+            gload16(st.b[1], Bp + min(j0 + bk_n + 4, ldk - 4));
         }
     };
 
@@ -271,8 +247,8 @@ __global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
                 const unsigned int byte = (w[q] >> (8 * e)) & 0xFFu;
                 f[e] = zero ? 0.0f : (is_signed ? (float)(int)(signed char)byte : (float)byte);
             }
-            o[2 * q] = __builtin_amdgcn_perm(__float_as_uint(f[1]), __float_as_uint(f[0]), 0x07060302u);
-            o[2 * q + 1] = __builtin_amdgcn_perm(__float_as_uint(f[3]), __float_as_uint(f[2]), 0x07060302u);
+            o[2 * q] = pack_bf2(f[0], f[1]);
+            o[2 * q + 1] = pack_bf2(f[2], f[3]);
         }
 #pragma unroll
         for (int h = 0; h < NW / 2; ++h)
@@ -291,14 +267,14 @@ __global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
                 float t = do_scale ? scale * v[q][e] : v[q][e];
                 if (zero) t = 0.0f;
                 h0[e] = t;
-                r1[e] = t - bf_trunc(t);
-                r2[e] = r1[e] - bf_trunc(r1[e]);
+                r1[e] = bf_rem(t);
+                r2[e] = bf_rem(r1[e]);
             }
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {   // bf16 pairs: v_perm picks the high halves of two fp32 words
-                o1[2 * q + e] = __builtin_amdgcn_perm(__float_as_uint(h0[2 * e + 1]), __float_as_uint(h0[2 * e]), 0x07060302u);
-                o2[2 * q + e] = __builtin_amdgcn_perm(__float_as_uint(r1[2 * e + 1]), __float_as_uint(r1[2 * e]), 0x07060302u);
-                o3[2 * q + e] = __builtin_amdgcn_perm(__float_as_uint(r2[2 * e + 1]), __float_as_uint(r2[2 * e]), 0x07060302u);
+            for (int e = 0; e < 2; ++e) {
+                o1[2 * q + e] = pack_bf2(h0[2 * e], h0[2 * e + 1]);
+                o2[2 * q + e] = pack_bf2(r1[2 * e], r1[2 * e + 1]);
+                o3[2 * q + e] = pack_bf2(r2[2 * e], r2[2 * e + 1]);
             }
         }
 #pragma unroll
@@ -332,8 +308,7 @@ __global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
 
     // ---------------------------------------------------------------- main loop
     const int nkt = (kend - kbeg + QBK - 1) / QBK;
-    // lane geometry of the transposed read: 16-lane group gq reads a 4(k) x 16(n) block
-    const int gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
+    const TrLane tl = tr_lane(lane);
     auto compute_tile = [&]() {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -341,22 +316,16 @@ __global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
             for (int sp = 0; sp < NA * NB; ++sp) {
                 // smallest pieces first: (3,3) ... (1,1) so that the large products are added last
                 const int ia = (NA == 3) ? 2 - (sp / NB) : 0, ib = (NB > 1) ? NB - 1 - (sp % NB) : 0;
-                // SIX: m.l, l.m and l.l lie below 2^-24 of the product (under the fp32 rounding of the sum), as csrc/gemm_x3.hip
+                // SIX: m.l, l.m and l.l lie below 2^-24 of the product (under the fp32 rounding of the sum): the six of fqss_mfma.h,
+                // walked here in this loop's own order (l.h, m.m, m.h, h.l, h.m, h.h -- not kX3A / kX3B's, which would re-order the sum)
                 if (SIX && ia + ib >= 3) continue;
                 bf16x8 af[2], bfr;
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
                     af[mi] = *reinterpret_cast<const bf16x8*>(&As[ia][wm * 64 + mi * 32 + lr][ks * 16 + 8 * lh]);
                 {
-                    // B[k = 8h + j][col r]: two transposed 4x16 block reads (rows 8h+0..3 and 8h+4..7)
-                    const int kr = ks * 16 + 8 * (gq >> 1) + tq;
-                    const int nc = wn * 32 + 16 * (gq & 1) + 4 * tp;
-                    union { bf16x8 v; s16x4 h[2]; } u;
-                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (s16x4 __attribute__((address_space(3)))*)(&Bs[ib][kr][nc]));
-                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (s16x4 __attribute__((address_space(3)))*)(&Bs[ib][kr + 4][nc]));
-                    bfr = u.v;
+                    const int kr = ks * 16 + tl.kr(), nc = tl.nc(wn * 32);
+                    bfr = lds_read_tr_bf16x8(Bs[ib], kr, nc);
                 }
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
@@ -646,19 +615,6 @@ __global__ __launch_bounds__(256, ADDQ ? 4 : 2) void k_qgemm(QGemmArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// Load rings are hand-scheduled: the compiler sinks plain loads next to their first use (draining the ring to
-// vmcnt(0) every chunk), so the loads are issued through asm and retired with an explicit s_waitcnt that
-// carries the stage's registers as in/out operands (every use of the data is ordered after the wait).
-__device__ __forceinline__ void wg_load16(f32x4& d, const void* p) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void wg_load16(u32x4& d, const void* p) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
-}
-
-// ---------------------------------------------------------------------------------------------------
 // wgrad, LDS-tiled (round 2): the round-1 register-direct kernel (each lane loading its MFMA fragments straight from HBM) was VALU-issue bound (PMC: 47 % of wave time issuing, 39 % stalled
 // on issue; ~5 cycles per wave instruction and SIMD): every wave splits its own gz fragment and converts its own code fragments,
 // so inside a 2 x 2 workgroup each gz value is split twice and each code converted twice.  Here the workgroup converts a
@@ -720,8 +676,8 @@ __global__ __launch_bounds__(512, 1) void k_qwgrad2(QGemmArgs g) {
     auto load = [&](W2Stage& st, int s) {
         const int k = kbeg + s * W2_TK;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) wg_load16(st.a[i], Ap[i] + min(k + ac, ka_last));
-        wg_load16(st.b, Bp + min(k + bc, kb_last));
+        for (int i = 0; i < 2; ++i) gload16(st.a[i], Ap[i] + min(k + ac, ka_last));
+        gload16(st.b, Bp + min(k + bc, kb_last));
     };
     float rs_part[2] = {0.f, 0.f};
     auto convert_store = [&](W2Stage& st, int s) {
@@ -735,13 +691,13 @@ __global__ __launch_bounds__(512, 1) void k_qwgrad2(QGemmArgs g) {
             rs_part[i] += (x[0] + x[1]) + (x[2] + x[3]);
             uint32_t o1[2], o2[2], o3[2];
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
+            for (int e = 0; e < 2; ++e) {      // (pair by pair: split3_pack4's order of the same operations schedules differently here)
                 const float a0 = x[2 * e], a1 = x[2 * e + 1];
-                const float r0 = a0 - bf_trunc(a0), r1 = a1 - bf_trunc(a1);
-                o1[e] = __builtin_amdgcn_perm(__float_as_uint(a1), __float_as_uint(a0), 0x07060302u);
-                const float s0 = r0 - bf_trunc(r0), s1 = r1 - bf_trunc(r1);
-                o2[e] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
-                o3[e] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
+                const float r0 = bf_rem(a0), r1 = bf_rem(a1);
+                o1[e] = pack_bf2(a0, a1);
+                const float s0 = bf_rem(r0), s1 = bf_rem(r1);
+                o2[e] = pack_bf2(r0, r1);
+                o3[e] = pack_bf2(s0, s1);
             }
             const int row = ar + 32 * i;
             *reinterpret_cast<uint2*>(&As[buf][0][row][ac]) = make_uint2(o1[0], o1[1]);
@@ -752,11 +708,9 @@ __global__ __launch_bounds__(512, 1) void k_qwgrad2(QGemmArgs g) {
             uint32_t o[8];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const uint32_t w = st.b[q];
-                const float f0 = (float)(w & 0xFFu), f1 = (float)((w >> 8) & 0xFFu);
-                const float f2 = (float)((w >> 16) & 0xFFu), f3 = (float)(w >> 24);
-                o[2 * q] = __builtin_amdgcn_perm(__float_as_uint(f1), __float_as_uint(f0), 0x07060302u);
-                o[2 * q + 1] = __builtin_amdgcn_perm(__float_as_uint(f3), __float_as_uint(f2), 0x07060302u);
+                const uint2 c = codes4_to_bf(st.b[q]);
+                o[2 * q] = c.x;
+                o[2 * q + 1] = c.y;
             }
             *reinterpret_cast<uint4*>(&Bs[buf][br][bc]) = make_uint4(o[0], o[1], o[2], o[3]);
             *reinterpret_cast<uint4*>(&Bs[buf][br][bc + 8]) = make_uint4(o[4], o[5], o[6], o[7]);
@@ -919,9 +873,9 @@ __device__ __forceinline__ void wgr_segment(const WGroupArgs& ga, const WJob& J,
     struct Stage { f32x4 a[2]; u32x4 b[NBF]; };
     auto load = [&](Stage& st) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) wg_load16(st.a[i], Ap[i] + min(lk + ac, ka_last));
+        for (int i = 0; i < 2; ++i) gload16(st.a[i], Ap[i] + min(lk + ac, ka_last));
 #pragma unroll
-        for (int f = 0; f < NBF; ++f) wg_load16(st.b[f], Brow[f] + boff + min(lk + bc, kb_last));
+        for (int f = 0; f < NBF; ++f) gload16(st.b[f], Brow[f] + boff + min(lk + bc, kb_last));
         lk += W2_TK;
         if (lk >= spb * W2_TK) {       // next batch (clamped: stages behind the range are requested but never used)
             lk = 0;
@@ -952,13 +906,13 @@ __device__ __forceinline__ void wgr_segment(const WGroupArgs& ga, const WJob& J,
             rs_part[i] += (x[0] + x[1]) + (x[2] + x[3]);
             uint32_t o1[2], o2[2], o3[2];
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
+            for (int e = 0; e < 2; ++e) {      // (pair by pair: split3_pack4's order of the same operations schedules differently here)
                 const float a0 = x[2 * e], a1 = x[2 * e + 1];
-                const float r0 = a0 - bf_trunc(a0), r1 = a1 - bf_trunc(a1);
-                o1[e] = __builtin_amdgcn_perm(__float_as_uint(a1), __float_as_uint(a0), 0x07060302u);
-                const float q0 = r0 - bf_trunc(r0), q1 = r1 - bf_trunc(r1);
-                o2[e] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(r0), 0x07060302u);
-                o3[e] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
+                const float r0 = bf_rem(a0), r1 = bf_rem(a1);
+                o1[e] = pack_bf2(a0, a1);
+                const float s0 = bf_rem(r0), s1 = bf_rem(r1);
+                o2[e] = pack_bf2(r0, r1);
+                o3[e] = pack_bf2(s0, s1);
             }
             const int row = ar + 32 * i;
             *reinterpret_cast<uint2*>(&As[buf][0][row][ac]) = make_uint2(o1[0], o1[1]);
@@ -970,11 +924,9 @@ __device__ __forceinline__ void wgr_segment(const WGroupArgs& ga, const WJob& J,
             uint32_t o[8];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const uint32_t w = st.b[f][q];
-                const float f0 = (float)(w & 0xFFu), f1 = (float)((w >> 8) & 0xFFu);
-                const float f2 = (float)((w >> 16) & 0xFFu), f3 = (float)(w >> 24);
-                o[2 * q] = __builtin_amdgcn_perm(__float_as_uint(f1), __float_as_uint(f0), 0x07060302u);
-                o[2 * q + 1] = __builtin_amdgcn_perm(__float_as_uint(f3), __float_as_uint(f2), 0x07060302u);
+                const uint2 c = codes4_to_bf(st.b[f][q]);
+                o[2 * q] = c.x;
+                o[2 * q + 1] = c.y;
             }
             *reinterpret_cast<uint4*>(&Bs[buf][br + 128 * f][bc]) = make_uint4(o[0], o[1], o[2], o[3]);
             *reinterpret_cast<uint4*>(&Bs[buf][br + 128 * f][bc + 8]) = make_uint4(o[4], o[5], o[6], o[7]);

@@ -16,28 +16,15 @@
 
 #include <cstdlib>
 
-#include "fqss_dev.h"
+#include "fqss_mfma.h"
 
 namespace fqss {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TBM = 128, TBN = 128, TBK = 32;
 constexpr int TLDK = 40, TLDN = 160, TLDT = 36;
 // GroupNorm statistics travel as kTSlots partial (sum, sum^2) pairs per sample, each pair on its own 128-B
 // line: same-address fp64 atomics serialise at ~12 ns apiece, spreading them over 32 lines removes that wall.
 constexpr int kTSlots = FQSS_TSTAT_SLOTS, kTSlotStride = FQSS_TSTAT_STRIDE;
-
-__device__ __forceinline__ unsigned short t_bf(float f) { return (unsigned short)(__float_as_uint(f) >> 16); }
-__device__ __forceinline__ float t_tr(float f) { return __uint_as_float(__float_as_uint(f) & 0xFFFF0000u); }
-__device__ __forceinline__ void t_split3(float g, unsigned short& b1, unsigned short& b2, unsigned short& b3) {
-    const float h1 = t_tr(g), r1 = g - h1, h2 = t_tr(r1), r2 = r1 - h2;
-    b1 = t_bf(h1);
-    b2 = t_bf(h2);
-    b3 = t_bf(r2);
-}
 
 // mean / rstd of one sample from its slot partials -> out2[0..1] (LDS); every thread of the block calls this.
 __device__ __forceinline__ void t_stats_finalize(const double* __restrict__ st, double count, float eps, float* out2) {
@@ -64,7 +51,7 @@ __global__ __launch_bounds__(256) void k_split3_planes(const float* __restrict__
                                                         int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         unsigned short a, b, c;
-        t_split3(w[i], a, b, c);
+        split3(w[i], a, b, c);
         planes[i] = a;
         planes[n + i] = b;
         planes[2 * n + i] = c;
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(256) void k_split3_tiles(const float* __restrict__ 
         const int kt = (int)(tile % nkt), mt = (int)(tile / nkt);
         const int c = pc ^ ((row >> 3) & 1);
         unsigned short a, b, d;
-        t_split3(w[(int64_t)(mt * 256 + row) * Ci + kt * 16 + c * 8 + e], a, b, d);
+        split3(w[(int64_t)(mt * 256 + row) * Ci + kt * 16 + c * 8 + e], a, b, d);
         const int64_t o = tile * (3 * 4096) + row * 16 + pc * 8 + e;
         tiles[o] = a;
         tiles[o + 4096] = b;
@@ -92,14 +79,10 @@ __global__ __launch_bounds__(256) void k_split3_tiles(const float* __restrict__ 
     }
 }
 
-typedef float f32x4t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4t __attribute__((ext_vector_type(4)));
 struct TStage {          // one k-tile of global loads per thread: 3 planes x 2 x 16 B of the weight, 4 x 16 B of activations
-    u32x4t ra[3][2];
-    f32x4t rb[4];
+    u32x4 ra[3][2];
+    f32x4 rb[4];
 };
-__device__ __forceinline__ void t_load16(u32x4t& d, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory"); }
-__device__ __forceinline__ void t_load16(f32x4t& d, const void* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory"); }
 template <int N>
 __device__ __forceinline__ void t_wait(TStage& st) {
     asm volatile("s_waitcnt vmcnt(%10)"
@@ -157,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
     int panel, mt;
     if (!xcd_tile(g.tiles_n * g.batches, g.tiles_m, panel, mt)) return;
     const int b = panel / g.tiles_n, i0 = mt * TBM, j0 = (panel % g.tiles_n) * TBN;
-    const int gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
+    const TrLane tl = tr_lane(lane);
 
     if (PRO == 1) t_stats_finalize(g.pro_stats + (int64_t)b * kTSlots * kTSlotStride, g.pro_count, g.pro_eps, pms);
     else __syncthreads();
@@ -199,10 +182,10 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
         for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                t_load16(st.ra[p][h], g.A + p * plane + (int64_t)a_row_c * g.K + min(k0 + a_k + 8 * h, g.K - 8));
+                gload16(st.ra[p][h], g.A + p * plane + (int64_t)a_row_c * g.K + min(k0 + a_k + 8 * h, g.K - 8));
         const int k = min(k0 + bk_row, g.K - 1);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) t_load16(st.rb[q], Bb + (int64_t)k * g.ldb + min(j0 + 32 * q + bk_c, n_last));
+        for (int q = 0; q < 4; ++q) gload16(st.rb[q], Bb + (int64_t)k * g.ldb + min(j0 + 32 * q + bk_c, n_last));
     };
     auto store_tiles = [&](TStage& st, int k0) {
         t_wait<10>(st);   // this stage has landed; the 10 younger requests of the other stage stay in flight
@@ -210,8 +193,8 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
         const float p_a = (PRO == 1) ? pco[0][kc] : 1.f, p_b = (PRO == 1) ? pco[1][kc] : 0.f;
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
-            *reinterpret_cast<u32x4t*>(&As[p][a_row][a_k]) = st.ra[p][0];
-            *reinterpret_cast<u32x4t*>(&As[p][a_row][a_k + 8]) = st.ra[p][1];
+            *reinterpret_cast<u32x4*>(&As[p][a_row][a_k]) = st.ra[p][0];
+            *reinterpret_cast<u32x4*>(&As[p][a_row][a_k + 8]) = st.ra[p][1];
         }
         const bool ok = (k0 + bk_row) < g.K;   // rows of B past K contribute zeros (A needs no mask: finite x 0)
 #pragma unroll
@@ -219,23 +202,16 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
             const float x[4] = {st.rb[q][0], st.rb[q][1], st.rb[q][2], st.rb[q][3]};
             float h0[4], r1[4], r2[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
+            for (int e = 0; e < 4; ++e) {      // (the prologue of element e in front of its remainders: split3_pack4 of a finished x[] schedules differently)
                 float t = x[e];
                 if (PRO == 1) t = fmaf(t, p_a, p_b);
                 else if (PRO == 2) t = t > 0.f ? t : pslope * t;
                 if (!ok) t = 0.f;
                 h0[e] = t;
-                r1[e] = t - t_tr(t);
-                r2[e] = r1[e] - t_tr(r1[e]);
+                r1[e] = bf_rem(t);
+                r2[e] = bf_rem(r1[e]);
             }
-            // bf16 pairs: v_perm picks the high halves of two fp32 words
-            uint2 o1, o2, o3;
-            o1.x = __builtin_amdgcn_perm(__float_as_uint(h0[1]), __float_as_uint(h0[0]), 0x07060302u);
-            o1.y = __builtin_amdgcn_perm(__float_as_uint(h0[3]), __float_as_uint(h0[2]), 0x07060302u);
-            o2.x = __builtin_amdgcn_perm(__float_as_uint(r1[1]), __float_as_uint(r1[0]), 0x07060302u);
-            o2.y = __builtin_amdgcn_perm(__float_as_uint(r1[3]), __float_as_uint(r1[2]), 0x07060302u);
-            o3.x = __builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u);
-            o3.y = __builtin_amdgcn_perm(__float_as_uint(r2[3]), __float_as_uint(r2[2]), 0x07060302u);
+            const uint2 o1 = pack_bf4(h0), o2 = pack_bf4(r1), o3 = pack_bf4(r2);
             *reinterpret_cast<uint2*>(&Bs[0][bk_row][32 * q + bk_c]) = o1;
             *reinterpret_cast<uint2*>(&Bs[1][bk_row][32 * q + bk_c]) = o2;
             *reinterpret_cast<uint2*>(&Bs[2][bk_row][32 * q + bk_c]) = o3;
@@ -252,24 +228,17 @@ __global__ __launch_bounds__(256, 2) void k_tgemm(TGemmArgs g) {
                     af[p][mi] = *reinterpret_cast<const bf16x8*>(&As[p][wm * 64 + mi * 32 + lr][ks * 16 + 8 * lh]);
 #pragma unroll
                 for (int ni = 0; ni < 2; ++ni) {
-                    const int kr = ks * 16 + 8 * (gq >> 1) + tq;
-                    const int nc = wn * 64 + ni * 32 + 16 * (gq & 1) + 4 * tp;
-                    union { bf16x8 v; s16x4 h[2]; } u;
-                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
-                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
-                    bfr[p][ni] = u.v;
+                    const int kr = ks * 16 + tl.kr(), nc = tl.nc(wn * 64 + ni * 32);
+                    bfr[p][ni] = lds_read_tr_bf16x8(Bs[p], kr, nc);
                 }
             }
-            // the 6 partial products of weight >= 2^-16 (the dropped a2*b3, a3*b2, a3*b3 are below the fp32
-            // rounding of the sum), smallest pieces first
-            constexpr int IA[6] = {2, 0, 1, 1, 0, 0}, IB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
-            for (int sp = 0; sp < 6; ++sp)
+            for (int sp = 0; sp < 6; ++sp)      // the six products, smallest pieces first (fqss_mfma.h)
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                     for (int ni = 0; ni < 2; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[IA[sp]][mi], bfr[IB[sp]][ni], acc[mi][ni], 0, 0, 0);
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kX3A[sp]][mi], bfr[kX3B[sp]][ni], acc[mi][ni], 0, 0, 0);
         }
     };
 
@@ -421,7 +390,7 @@ static_assert(4 * 32 * TLDT * 4 + 2 * 8 * 8 <= T2_A_SLOT, "epilogue scratch fits
 
 // 16-B load with a scalar base + a 32-bit lane offset: the loader's addresses for 32 k-tiles x 4 rows are scalar adds on ONE register
 // (as 64-bit per-lane pointers the compiler precomputed and spilled them: a scratch reload in the counted stream ends in a vmcnt(0))
-__device__ __forceinline__ void t_load16s(f32x4t& d, const void* sbase, unsigned voff) {
+__device__ __forceinline__ void t_load16s(f32x4& d, const void* sbase, unsigned voff) {
     // s_nop 4: the compiler may have produced the scalar base by a VALU instruction (v_readlane of a spilled SGPR) right in front of
     // the statement; a vector-memory instruction that reads such an SGPR needs five wait states, and nothing pads the inside of an asm
     // statement (without it: wrong tiles and one memory fault)
@@ -524,7 +493,7 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
         const unsigned bvoff = (unsigned)((bk_row * (int)g.ldb + min(j0 + bk_c, n_last)) * 4);     // < 2^32: ld_x < 2^28 (host)
         const float* bbase = g.B + (int64_t)b * g.sBb;                                          // wave-uniform
         const int64_t bstep = (int64_t)T2BK * g.ldb, brow4 = 4 * g.ldb;
-        struct LStage { f32x4t rb[4]; };
+        struct LStage { f32x4 rb[4]; };
         auto load_b = [&](LStage& st, int t) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) t_load16s(st.rb[q], bbase + t * bstep + q * brow4, bvoff);
@@ -537,21 +506,15 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
                 const float p_a = (PRO == 1) ? pco[kc] : 1.f, p_b = (PRO == 1) ? pco[512 + kc] : 0.f;
                 float h0[4], r1[4], r2[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
+                for (int e = 0; e < 4; ++e) {      // (as k_tgemm: the prologue of element e in front of its remainders)
                     float v = st.rb[q][e];
                     if (PRO == 1) v = fmaf(v, p_a, p_b);
                     else if (PRO == 2) v = v > 0.f ? v : pslope * v;
                     h0[e] = v;
-                    r1[e] = v - t_tr(v);
-                    r2[e] = r1[e] - t_tr(r1[e]);
+                    r1[e] = bf_rem(v);
+                    r2[e] = bf_rem(r1[e]);
                 }
-                uint2 o1, o2, o3;
-                o1.x = __builtin_amdgcn_perm(__float_as_uint(h0[1]), __float_as_uint(h0[0]), 0x07060302u);
-                o1.y = __builtin_amdgcn_perm(__float_as_uint(h0[3]), __float_as_uint(h0[2]), 0x07060302u);
-                o2.x = __builtin_amdgcn_perm(__float_as_uint(r1[1]), __float_as_uint(r1[0]), 0x07060302u);
-                o2.y = __builtin_amdgcn_perm(__float_as_uint(r1[3]), __float_as_uint(r1[2]), 0x07060302u);
-                o3.x = __builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u);
-                o3.y = __builtin_amdgcn_perm(__float_as_uint(r2[3]), __float_as_uint(r2[2]), 0x07060302u);
+                const uint2 o1 = pack_bf4(h0), o2 = pack_bf4(r1), o3 = pack_bf4(r2);
                 *reinterpret_cast<uint2*>(bs + q * 4 * TLDN * 2) = o1;
                 *reinterpret_cast<uint2*>(bs + q * 4 * TLDN * 2 + T2BK * TLDN * 2) = o2;
                 *reinterpret_cast<uint2*>(bs + q * 4 * TLDN * 2 + 2 * T2BK * TLDN * 2) = o3;
@@ -594,7 +557,7 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
     } else {
         // =============================== compute waves (4 = 2 x 2, wave tile 128 x 64): fragment reads and MFMAs ====================
         const int wm = wave >> 1, wn = wave & 1, lr = lane & 31, lh = lane >> 5;
-        const int gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
+        const TrLane tl = tr_lane(lane);
         const float nscale = (g.act == FQSS_ACT_PRELU) ? *g.slope : (g.act == FQSS_ACT_RELU ? 0.0f : 1.0f);
         const bool has_bias = g.bias != nullptr;
         f32x16 acc[4][2];
@@ -609,12 +572,8 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
             for (int p = 0; p < 3; ++p)
 #pragma unroll
                 for (int ni = 0; ni < 2; ++ni) {
-                    const int kr = 8 * (gq >> 1) + tq;
-                    const int nc = wn * 64 + ni * 32 + 16 * (gq & 1) + 4 * tp;
-                    union { bf16x8 v; s16x4 h[2]; } u;
-                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
-                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
-                    bfr[p][ni] = u.v;
+                    const int kr = tl.kr(), nc = tl.nc(wn * 64 + ni * 32);
+                    bfr[p][ni] = lds_read_tr_bf16x8(Bs[p], kr, nc);
                 }
         };
         auto rd_a = [&](bf16x8 (&af)[3][2], int slot, int mh) {
@@ -629,14 +588,13 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
         };
         auto mm = [&](bf16x8 (&af)[3][2], bf16x8 (&bfr)[3][2], auto MH) {
             constexpr int mh = decltype(MH)::value;
-            constexpr int IA[6] = {2, 0, 1, 1, 0, 0}, IB[6] = {0, 2, 1, 0, 1, 0};     // the six products, smallest pieces first (k_tgemm)
 #pragma unroll
-            for (int sp = 0; sp < 6; ++sp)
+            for (int sp = 0; sp < 6; ++sp)      // the six products, smallest pieces first (fqss_mfma.h)
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                     for (int ni = 0; ni < 2; ++ni)
-                        acc[2 * mh + mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[IA[sp]][mi], bfr[IB[sp]][ni], acc[2 * mh + mi][ni], 0, 0, 0);
+                        acc[2 * mh + mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kX3A[sp]][mi], bfr[kX3B[sp]][ni], acc[2 * mh + mi][ni], 0, 0, 0);
         };
         using H0 = std::integral_constant<int, 0>;
         using H1 = std::integral_constant<int, 1>;
@@ -777,7 +735,7 @@ __global__ __launch_bounds__(512, 2) void k_tgemm2(TGemmArgs g) {
 // products, smallest first, as k_tgemm / k_tgemm2; the accumulation runs over k in the same order.
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int K1_BN = 64, K1_LDN = 72, K1_ROWS = 128;
-struct K1X { f32x4t v[8]; };
+struct K1X { f32x4 v[8]; };
 __device__ __forceinline__ void k1_wait(K1X& x) {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(x.v[0]), "+v"(x.v[1]), "+v"(x.v[2]), "+v"(x.v[3]), "+v"(x.v[4]), "+v"(x.v[5]), "+v"(x.v[6]), "+v"(x.v[7]) : : "memory");
 }
@@ -787,7 +745,8 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
     __shared__ __attribute__((aligned(16))) float Tst[4][32][TLDT];               // 18,432 B: a wave-private staging tile each
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lr = lane & 31, lh = lane >> 5, gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
+    const int lr = lane & 31, lh = lane >> 5;
+    const TrLane tl = tr_lane(lane);
     int group, rb;
     if (!xcd_tile(ngroups, g.M / K1_ROWS, group, rb)) return;
     const int i0 = rb * K1_ROWS + wave * 32;      // this wave's 32 output rows
@@ -815,7 +774,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
         const int b = ct / tiles_n64, j0 = (ct - b * tiles_n64) * K1_BN;
         const float* Bb = g.B + (int64_t)b * g.sBb + min(j0 + xc, n_last);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) t_load16(xr.v[q], Bb + (int64_t)(q * 16 + xk) * g.ldb);
+        for (int q = 0; q < 8; ++q) gload16(xr.v[q], Bb + (int64_t)(q * 16 + xk) * g.ldb);
     };
     float s1 = 0.0f, s2 = 0.0f;
     int sb = -1;                                   // the sample the statistics in (s1, s2) belong to
@@ -844,22 +803,10 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const float x[4] = {xr.v[q][0], xr.v[q][1], xr.v[q][2], xr.v[q][3]};
-            float r1[4], r2[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                r1[e] = x[e] - t_tr(x[e]);
-                r2[e] = r1[e] - t_tr(r1[e]);
-            }
-            uint2 o1, o2, o3;
-            o1.x = __builtin_amdgcn_perm(__float_as_uint(x[1]), __float_as_uint(x[0]), 0x07060302u);
-            o1.y = __builtin_amdgcn_perm(__float_as_uint(x[3]), __float_as_uint(x[2]), 0x07060302u);
-            o2.x = __builtin_amdgcn_perm(__float_as_uint(r1[1]), __float_as_uint(r1[0]), 0x07060302u);
-            o2.y = __builtin_amdgcn_perm(__float_as_uint(r1[3]), __float_as_uint(r1[2]), 0x07060302u);
-            o3.x = __builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u);
-            o3.y = __builtin_amdgcn_perm(__float_as_uint(r2[3]), __float_as_uint(r2[2]), 0x07060302u);
-            *reinterpret_cast<uint2*>(&Bs[0][q * 16 + xk][xc]) = o1;
-            *reinterpret_cast<uint2*>(&Bs[1][q * 16 + xk][xc]) = o2;
-            *reinterpret_cast<uint2*>(&Bs[2][q * 16 + xk][xc]) = o3;
+            const Split3x4 o = split3_pack4(x);
+            *reinterpret_cast<uint2*>(&Bs[0][q * 16 + xk][xc]) = o.h;
+            *reinterpret_cast<uint2*>(&Bs[1][q * 16 + xk][xc]) = o.m;
+            *reinterpret_cast<uint2*>(&Bs[2][q * 16 + xk][xc]) = o.l;
         }
         if (ct + ngroups < ntiles) load_x(ct + ngroups);     // the next tile's activations travel under this tile's MFMAs
         __syncthreads();
@@ -877,19 +824,8 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
         auto read_frags = [&](bf16x8 (&bfr)[3], int ks, int ni) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
-                const int kr = ks * 16 + 8 * (gq >> 1) + tq;
-                const int nc = ni * 32 + 16 * (gq & 1) + 4 * tp;
-                union { bf16x8 v; s16x4 h[2]; } u;
-                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr][nc]));
-                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(&Bs[p][kr + 4][nc]));
-                bfr[p] = u.v;
-            }
-        };
-        auto mfma_tile = [&](const bf16x8 (&bfr)[3], int ks, int ni) {
-            constexpr int IA[6] = {2, 0, 1, 1, 0, 0}, IB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-            for (int sp = 0; sp < 6; ++sp) {
-                acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks][IA[sp]], bfr[IB[sp]], acc[ni], 0, 0, 0);
+                const int kr = ks * 16 + tl.kr(), nc = tl.nc(ni * 32);
+                bfr[p] = lds_read_tr_bf16x8(Bs[p], kr, nc);
             }
         };
         bf16x8 fr[2][3];
@@ -897,7 +833,7 @@ __global__ __launch_bounds__(256, 2) void k_tgemm_k128(TGemmArgs g, int ngroups,
 #pragma unroll
         for (int u = 0; u < 16; ++u) {          // u = 8 ni + ks: one 32-column tile through the whole K, then the other
             if (u + 1 < 16) read_frags(fr[(u + 1) & 1], (u + 1) & 7, (u + 1) >> 3);
-            mfma_tile(fr[u & 1], u & 7, u >> 3);
+            x3_products(acc[u >> 3], wf[u & 7], fr[u & 1]);
         }
         __syncthreads();      // every wave is done with the LDS tile: the next iteration may overwrite it
         // ---- act, 16-B/lane row stores through the wave's staging tile, statistics (no workgroup barrier in here)
