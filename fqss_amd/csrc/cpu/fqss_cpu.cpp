@@ -1294,14 +1294,31 @@ int64_t fqss_stoi_ws_doubles(int P, int64_t L, int up, int down) {
     return (int64_t)P * ((up == down ? 0 : 2 * Lp) + NF + (NF + 2) / 2 + 2 * 15 * Tmax + Smax);
 }
 
-int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
-              int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, fqss_stream_t) {
-    REQUIRE(est && ref && taps && ws && d, "null pointer");
-    REQUIRE(stoi_ratio_ok(up, down), "up / down not in 1..65536 or not reduced");
-    REQUIRE(stoi_shape_ok(P, L, up, down) && ld_e >= L && ld_r >= L, "bad shape (1 <= P <= 32767, 1 <= L <= 2^37 / up, ld >= L)");
-    REQUIRE(n_taps >= 1 && (n_taps & 1) && (up != down || n_taps == 1), "n_taps even, or not 1 at up = down = 1");
-    REQUIRE(n_taps <= 1023 && 255 * (int64_t)down + n_taps <= 1022 * (int64_t)up, "resampler outside what one workgroup stages");
-    REQUIRE(ws_doubles >= fqss_stoi_ws_doubles(P, L, up, down), "workspace shorter than fqss_stoi_ws_doubles");
+// both entry points: modes 1 STOI, 2 extended, 3 both; d [popcount(modes)][P], STOI's row first; the band matrices are made once
+#define STOI_REQUIRE(cond, msg)                 \
+    do {                                        \
+        if (!(cond)) {                          \
+            set_error("%s: %s", what, msg);     \
+            return FQSS_EINVAL;                 \
+        }                                       \
+    } while (0)
+
+int64_t fqss_stoi_x_ws_doubles(int P, int64_t L, int up, int down, int modes) {
+    if (!stoi_shape_ok(P, L, up, down) || modes < 1 || modes > 3) return 0;
+    const int64_t Lp = (L * up + down - 1) / down, NF = Lp > 256 ? (Lp - 256 + 127) / 128 : 0;
+    return fqss_stoi_ws_doubles(P, L, up, down) + (modes == 3 ? (int64_t)P * (NF > 30 ? NF - 30 : 0) : 0);
+}
+
+static int stoi_run(const char* what, const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles,
+                    double* d, int P, int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, int modes) {
+    STOI_REQUIRE(est && ref && taps && ws && d, "null pointer");
+    STOI_REQUIRE(modes >= 1 && modes <= 3, "modes outside 1..3 (1 STOI, 2 extended, 3 both)");
+    STOI_REQUIRE(stoi_ratio_ok(up, down), "up / down not in 1..65536 or not reduced");
+    STOI_REQUIRE(stoi_shape_ok(P, L, up, down) && ld_e >= L && ld_r >= L, "bad shape (1 <= P <= 32767, 1 <= L <= 2^37 / up, ld >= L)");
+    STOI_REQUIRE(n_taps >= 1 && (n_taps & 1) && (up != down || n_taps == 1), "n_taps even, or not 1 at up = down = 1");
+    STOI_REQUIRE(n_taps <= 1023 && 255 * (int64_t)down + n_taps <= 1022 * (int64_t)up, "resampler outside what one workgroup stages");
+    STOI_REQUIRE(ws_doubles >= fqss_stoi_x_ws_doubles(P, L, up, down, modes), "workspace shorter than its _ws_doubles query");
+    double* const d_ext = d + (modes == 3 ? P : 0);
     const double EPS = 2.220446049250313e-16, PI = 3.14159265358979323846, CLIP = 1.0 + pow(10.0, 15.0 / 20.0);
     const int64_t Lp = (L * up + down - 1) / down, NF = Lp > 256 ? (Lp - 256 + 127) / 128 : 0, Lh = (n_taps - 1) / 2;
     std::vector<double> w(256), cs(512), sn(512);
@@ -1346,7 +1363,8 @@ int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps
             if (emax - 40.0 - e[f] < 0.0) kept.push_back(f);
         const int64_t K = (int64_t)kept.size(), T = K > 0 ? K - 1 : 0;
         if (T < 30) {
-            d[p] = 1e-5;
+            if (modes & 1) d[p] = 1e-5;
+            if (modes & 2) d_ext[p] = 1e-5;
             continue;
         }
         std::vector<double> tob[2];
@@ -1375,7 +1393,7 @@ int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps
             }
         }
         double total = 0.0;
-        for (int64_t m = 30; m <= T; ++m)
+        for (int64_t m = 30; (modes & 1) && m <= T; ++m)
             for (int k = 0; k < 15; ++k) {
                 const double *x = &tob[0][k * T + m - 30], *y = &tob[1][k * T + m - 30];
                 double xx = 0.0, yy = 0.0, yp[30], xc[30], mx = 0.0, my = 0.0, nx = 0.0, ny = 0.0, dot = 0.0;
@@ -1402,9 +1420,55 @@ int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps
                 for (int c = 0; c < 30; ++c) dot += (xc[c] / nx) * (yp[c] / ny);
                 total += dot;
             }
-        d[p] = total / (15.0 * (double)(T - 29));
+        if (modes & 1) d[p] = total / (15.0 * (double)(T - 29));
+        // the extended measure (include/fqss.h at fqss_stoi_x): rows, then columns, mean-free and of unit norm; a zero norm leaves zeros
+        total = 0.0;
+        for (int64_t m = 30; (modes & 2) && m <= T; ++m) {
+            double sg[2][15][30], dm = 0.0;
+            for (int s = 0; s < 2; ++s)
+                for (int k = 0; k < 15; ++k) {
+                    const double* v = &tob[s][k * T + m - 30];
+                    double mean = 0.0, ss = 0.0;
+                    for (int c = 0; c < 30; ++c) mean += v[c];
+                    mean /= 30.0;
+                    for (int c = 0; c < 30; ++c) {
+                        sg[s][k][c] = v[c] - mean;
+                        ss += sg[s][k][c] * sg[s][k][c];
+                    }
+                    const double nrm = sqrt(ss), inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+                    for (int c = 0; c < 30; ++c) sg[s][k][c] *= inv;
+                }
+            for (int c = 0; c < 30; ++c) {
+                double inv[2], dot = 0.0;
+                for (int s = 0; s < 2; ++s) {
+                    double mean = 0.0, ss = 0.0;
+                    for (int k = 0; k < 15; ++k) mean += sg[s][k][c];
+                    mean /= 15.0;
+                    for (int k = 0; k < 15; ++k) {
+                        sg[s][k][c] -= mean;
+                        ss += sg[s][k][c] * sg[s][k][c];
+                    }
+                    const double nrm = sqrt(ss);
+                    inv[s] = nrm > 0.0 ? 1.0 / nrm : 0.0;
+                }
+                for (int k = 0; k < 15; ++k) dot += (sg[0][k][c] * inv[0]) * (sg[1][k][c] * inv[1]);
+                dm += dot;
+            }
+            total += dm / 30.0;
+        }
+        if (modes & 2) d_ext[p] = total / (double)(T - 29);
     }
     return FQSS_OK;
+}
+
+int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
+              int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, fqss_stream_t) {
+    return stoi_run("fqss_stoi", est, ref, taps, n_taps, ws, ws_doubles, d, P, L, ld_e, ld_r, up, down, 1);
+}
+
+int fqss_stoi_x(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
+                int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, int modes, fqss_stream_t) {
+    return stoi_run("fqss_stoi_x", est, ref, taps, n_taps, ws, ws_doubles, d, P, L, ld_e, ld_r, up, down, modes);
 }
 
 // ------------------------------------------------------------------------------------------------ batched chunked inference

@@ -69,6 +69,21 @@ static int run(int up, int down, int64_t L, int P, bool expect_number) {
     }
     CHECK(fqss_stoi(est.data(), ref.data(), taps.data(), (int)taps.size(), ws.data(), need - 1, d.data(), P, L, ld, ld, up, down, nullptr) == FQSS_EINVAL);
     CHECK(fqss_stoi(est.data(), ref.data(), taps.data(), (int)taps.size(), ws.data(), need, d.data(), P, L, L - 1, ld, up, down, nullptr) == FQSS_EINVAL);
+    // fqss_stoi_x: both measures from one call (STOI's row first, the bits of fqss_stoi), the extended one alone, est = ref, modes refused
+    const int64_t need_x = fqss_stoi_x_ws_doubles(P, L, up, down, 3);
+    CHECK(need_x >= need && fqss_stoi_x_ws_doubles(P, L, up, down, 2) == need && fqss_stoi_x_ws_doubles(P, L, up, down, 0) == 0);
+    std::vector<double> wx((size_t)need_x), d2((size_t)(2 * P), -7.0), dx((size_t)P, -7.0);
+    CHECK(fqss_stoi(est.data(), ref.data(), taps.data(), (int)taps.size(), ws.data(), need, d.data(), P, L, ld, ld, up, down, nullptr) == 0);
+    CHECK(fqss_stoi_x(est.data(), ref.data(), taps.data(), (int)taps.size(), wx.data(), need_x, d2.data(), P, L, ld, ld, up, down, 3, nullptr) == 0);
+    CHECK(fqss_stoi_x(est.data(), ref.data(), taps.data(), (int)taps.size(), wx.data(), need, dx.data(), P, L, ld, ld, up, down, 2, nullptr) == 0);
+    CHECK(fqss_stoi_x(same.data(), ref.data(), taps.data(), (int)taps.size(), wx.data(), need, d1.data(), P, L, ld, ld, up, down, 2, nullptr) == 0);
+    for (int p = 0; p < P; ++p) {
+        CHECK(d2[(size_t)p] == d[(size_t)p] && d2[(size_t)(P + p)] == dx[(size_t)p]);
+        CHECK(expect_number ? (fabs(d1[(size_t)p] - 1.0) < 1e-12 && dx[(size_t)p] > 0.0 && dx[(size_t)p] < 0.9999) : (dx[(size_t)p] == 1e-5));
+    }
+    CHECK(fqss_stoi_x(est.data(), ref.data(), taps.data(), (int)taps.size(), wx.data(), need_x, dx.data(), P, L, ld, ld, up, down, 4, nullptr) == FQSS_EINVAL);
+    CHECK(fqss_stoi_x(est.data(), ref.data(), taps.data(), (int)taps.size(), wx.data(), need_x - 1, d2.data(), P, L, ld, ld, up, down, 3, nullptr) ==
+          FQSS_EINVAL);
     return 0;
 }
 

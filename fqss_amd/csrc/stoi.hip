@@ -10,6 +10,8 @@
 //   k_stoi_spec      one workgroup per spectral frame and signal: its 256 silence-removed samples gathered through the list (at most two
 //                    kept frames each), the second window, a 512-point radix-2 Stockham FFT in LDS, 15 band sums
 //   k_stoi_corr      grid (segments, pairs): 15 bands x 30 columns, one band per wave at a time, the columns on the lanes
+//   k_stoi_corr_ext  the extended measure's segment stage (fqss_stoi_x, mode 2), grid (segments, pairs): both 15 x 30 matrices in LDS, rows
+//                    normalised one band per wave, then columns one lane each
 //   k_stoi_finish    one workgroup per pair: the segment partials summed, the division, 1e-5 when fewer than 30 frames are left
 #include "fqss_dev.h"
 
@@ -224,16 +226,76 @@ __global__ __launch_bounds__(256) void k_stoi_corr(double* __restrict__ ws, int 
     if (tid == 0) ws[w.part + p * w.Smax + sg] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-__global__ __launch_bounds__(256) void k_stoi_finish(const double* __restrict__ ws, double* __restrict__ d, int P, int64_t L, int up, int down) {
+// Extended STOI (include/fqss.h at fqss_stoi_x): the segment's two 15 x 30 matrices live in LDS ([15][31] doubles each, 7440 B together).
+// Row phase: band k on wave k % 4, the 30 columns on the lanes, idle lanes zero (as k_stoi_corr): mean and centred sum of squares of
+// both signals on the DPP tree, the normalised rows written to LDS; consecutive lanes write consecutive doubles, and with the odd pitch
+// of 31 the four waves' rows start 31 doubles apart.  One barrier.  Column phase: lane n < 30 of wave 0 owns column n of BOTH
+// matrices (lanes read consecutive doubles of one row: every bank once), walks the 15 bands in band order three times from registers
+// -- mean, centred sum of squares, the sum of products with both inverse norms applied -- and one DPP sum over the lanes ends the segment.
+// A centred row or column of norm exactly 0 stays zero (inv = 0): no EPS, no noise, the same bits every run.
+constexpr int kStoiPitch = kStoiSeg + 1;
+__device__ __forceinline__ double stoi_inv_norm(double ss) {
+    const double nrm = sqrt(ss);
+    return nrm > 0.0 ? 1.0 / nrm : 0.0;
+}
+__global__ __launch_bounds__(256) void k_stoi_corr_ext(double* __restrict__ ws, int64_t part, int P, int64_t L, int up, int down) {
+    __shared__ double xs[kStoiBands * kStoiPitch], ys[kStoiBands * kStoiPitch];
+    const StoiLayout w = stoi_layout(P, L, up, down);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t p = blockIdx.y, sg = blockIdx.x;
+    const int K = reinterpret_cast<const int*>(ws + w.idx + p * ((w.NF + 2) / 2))[w.NF];
+    if (sg + kStoiSeg > K - 1) return;      // the whole workgroup
+    const bool col = lane < kStoiSeg;
+    for (int k = wv; k < kStoiBands; k += 4) {
+        const double* xt = ws + w.tob + ((p * 2 + 0) * kStoiBands + k) * w.Tmax + sg;
+        const double* yt = ws + w.tob + ((p * 2 + 1) * kStoiBands + k) * w.Tmax + sg;
+        const double x = col ? xt[lane] : 0.0, y = col ? yt[lane] : 0.0;
+        const double mx = wave_sum(x) / (double)kStoiSeg, my = wave_sum(y) / (double)kStoiSeg;
+        const double xc = col ? x - mx : 0.0, yc = col ? y - my : 0.0;
+        const double ix = stoi_inv_norm(wave_sum(xc * xc)), iy = stoi_inv_norm(wave_sum(yc * yc));
+        if (col) {
+            xs[k * kStoiPitch + lane] = xc * ix;
+            ys[k * kStoiPitch + lane] = yc * iy;
+        }
+    }
+    __syncthreads();
+    if (wv != 0) return;
+    double cx[kStoiBands], cy[kStoiBands], mx = 0.0, my = 0.0, sx = 0.0, sy = 0.0, dot = 0.0;
+#pragma unroll
+    for (int j = 0; j < kStoiBands; ++j) {
+        cx[j] = col ? xs[j * kStoiPitch + lane] : 0.0;
+        cy[j] = col ? ys[j * kStoiPitch + lane] : 0.0;
+        mx += cx[j];
+        my += cy[j];
+    }
+    mx /= (double)kStoiBands;
+    my /= (double)kStoiBands;
+#pragma unroll
+    for (int j = 0; j < kStoiBands; ++j) {
+        cx[j] -= mx;
+        cy[j] -= my;
+        sx += cx[j] * cx[j];
+        sy += cy[j] * cy[j];
+    }
+    const double ix = stoi_inv_norm(sx), iy = stoi_inv_norm(sy);
+#pragma unroll
+    for (int j = 0; j < kStoiBands; ++j) dot += (cx[j] * ix) * (cy[j] * iy);
+    dot = wave_sum(dot);
+    if (tid == 0) ws[part + p * w.Smax + sg] = dot / (double)kStoiSeg;
+}
+
+// d[p] = (the pair's segment partials at ws[part ..]) / (per * segments): per = 15 bands for STOI, 1 for the extended measure
+__global__ __launch_bounds__(256) void k_stoi_finish(const double* __restrict__ ws, int64_t part, double per, double* __restrict__ d, int P,
+                                                     int64_t L, int up, int down) {
     __shared__ double smem[4];
     const StoiLayout w = stoi_layout(P, L, up, down);
     const int64_t p = blockIdx.x;
     const int K = reinterpret_cast<const int*>(ws + w.idx + p * ((w.NF + 2) / 2))[w.NF];
     const int64_t nseg = (int64_t)K - 1 - (kStoiSeg - 1);      // T - 29
     double s[1] = {0.0};
-    for (int64_t i = threadIdx.x; i < nseg; i += 256) s[0] += ws[w.part + p * w.Smax + i];
+    for (int64_t i = threadIdx.x; i < nseg; i += 256) s[0] += ws[part + p * w.Smax + i];
     block_sum<double, 1>(s, smem);
-    if (threadIdx.x == 0) d[p] = nseg >= 1 ? s[0] / ((double)kStoiBands * (double)nseg) : 1e-5;
+    if (threadIdx.x == 0) d[p] = nseg >= 1 ? s[0] / (per * (double)nseg) : 1e-5;
 }
 
 static int64_t gcd64(int64_t a, int64_t b) { return b == 0 ? a : gcd64(b, a % b); }
@@ -241,6 +303,52 @@ static bool stoi_ratio_ok(int up, int down) { return up >= 1 && down >= 1 && up 
 constexpr int64_t kStoiMaxUpL = (int64_t)1 << 37;      // L up: frame numbers and grids stay below 2^31
 static bool stoi_shape_ok(int P, int64_t L, int up, int down) {
     return P >= 1 && P <= 32767 && L >= 1 && stoi_ratio_ok(up, down) && L <= kStoiMaxUpL / up;
+}
+
+// The host side of both entry points.  modes: 1 STOI, 2 extended, 3 both; d [popcount(modes)][P], STOI's row first.  The kernels up to
+// the band matrices run once; every mode has its own segment partials (the extended ones behind STOI's when both are asked for), its own
+// corr kernel and its own finish.  fqss_stoi is modes = 1: the launches it always made.
+static int64_t stoi_ws_total(const StoiLayout& w, int P, int modes) { return w.total + (modes == 3 ? (int64_t)P * w.Smax : 0); }
+
+#define STOI_REQUIRE(cond, msg)                     \
+    do {                                            \
+        if (!(cond)) {                              \
+            ::fqss::set_error("%s: %s", what, msg); \
+            return FQSS_EINVAL;                     \
+        }                                           \
+    } while (0)
+
+static int stoi_run(const char* what, const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles,
+                    double* d, int P, int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, int modes, fqss_stream_t stream) {
+    STOI_REQUIRE(est && ref && taps && ws && d, "null pointer");
+    STOI_REQUIRE(modes >= 1 && modes <= 3, "modes outside 1..3 (1 STOI, 2 extended, 3 both)");
+    STOI_REQUIRE(stoi_ratio_ok(up, down), "up / down not in 1..65536 or not reduced");
+    STOI_REQUIRE(stoi_shape_ok(P, L, up, down) && ld_e >= L && ld_r >= L, "bad shape (1 <= P <= 32767, 1 <= L <= 2^37 / up, ld >= L)");
+    STOI_REQUIRE(n_taps >= 1 && (n_taps & 1) && (up != down || n_taps == 1), "n_taps even, or not 1 at up = down = 1");
+    // a tile of 256 outputs reads at most (255 down + n_taps - 1) / up + 2 consecutive input samples
+    STOI_REQUIRE(n_taps <= kStoiMaxTaps && 255 * (int64_t)down + n_taps <= (kStoiSpan - 2) * (int64_t)up,
+                 "resampler outside what one workgroup stages");
+    const StoiLayout w = stoi_layout(P, L, up, down);
+    STOI_REQUIRE(ws_doubles >= stoi_ws_total(w, P, modes), "workspace shorter than its _ws_doubles query");
+    hipStream_t st = (hipStream_t)stream;
+    const int resampled = up != down;
+    if (resampled)
+        hipLaunchKernelGGL(k_stoi_resample, dim3((unsigned)cdiv(w.Lp, kStoiTile), 2u * P), dim3(256), 0, st, est, ref, taps, n_taps, ws, P, L, ld_e,
+                           ld_r, up, down);
+    if (w.NF > 0) hipLaunchKernelGGL(k_stoi_energy, dim3((unsigned)cdiv(w.NF, 4), (unsigned)P), dim3(256), 0, st, est, ref, ws, P, L, ld_e, ld_r, up, down, resampled);
+    hipLaunchKernelGGL(k_stoi_mask, dim3((unsigned)P), dim3(256), 0, st, ws, P, L, up, down);
+    if (w.Tmax > 0)
+        hipLaunchKernelGGL(k_stoi_spec, dim3((unsigned)w.Tmax, 2u * P), dim3(256), 0, st, est, ref, ws, P, L, ld_e, ld_r, up, down, resampled);
+    if (modes & 1) {
+        if (w.Smax > 0) hipLaunchKernelGGL(k_stoi_corr, dim3((unsigned)w.Smax, (unsigned)P), dim3(256), 0, st, ws, P, L, up, down);
+        hipLaunchKernelGGL(k_stoi_finish, dim3((unsigned)P), dim3(256), 0, st, (const double*)ws, w.part, (double)kStoiBands, d, P, L, up, down);
+    }
+    if (modes & 2) {
+        const int64_t part = modes == 3 ? w.total : w.part;
+        if (w.Smax > 0) hipLaunchKernelGGL(k_stoi_corr_ext, dim3((unsigned)w.Smax, (unsigned)P), dim3(256), 0, st, ws, part, P, L, up, down);
+        hipLaunchKernelGGL(k_stoi_finish, dim3((unsigned)P), dim3(256), 0, st, (const double*)ws, part, 1.0, d + (modes == 3 ? P : 0), P, L, up, down);
+    }
+    return launch_status(what);
 }
 
 }  // namespace fqss
@@ -255,25 +363,15 @@ extern "C" int64_t fqss_stoi_ws_doubles(int P, int64_t L, int up, int down) {
 
 extern "C" int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
                          int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, fqss_stream_t stream) {
-    FQSS_REQUIRE(est && ref && taps && ws && d, "null pointer");
-    FQSS_REQUIRE(stoi_ratio_ok(up, down), "up / down not in 1..65536 or not reduced");
-    FQSS_REQUIRE(stoi_shape_ok(P, L, up, down) && ld_e >= L && ld_r >= L, "bad shape (1 <= P <= 32767, 1 <= L <= 2^37 / up, ld >= L)");
-    FQSS_REQUIRE(n_taps >= 1 && (n_taps & 1) && (up != down || n_taps == 1), "n_taps even, or not 1 at up = down = 1");
-    // a tile of 256 outputs reads at most (255 down + n_taps - 1) / up + 2 consecutive input samples
-    FQSS_REQUIRE(n_taps <= kStoiMaxTaps && 255 * (int64_t)down + n_taps <= (kStoiSpan - 2) * (int64_t)up,
-                 "resampler outside what one workgroup stages");
-    const StoiLayout w = stoi_layout(P, L, up, down);
-    FQSS_REQUIRE(ws_doubles >= w.total, "workspace shorter than fqss_stoi_ws_doubles");
-    hipStream_t st = (hipStream_t)stream;
-    const int resampled = up != down;
-    if (resampled)
-        hipLaunchKernelGGL(k_stoi_resample, dim3((unsigned)cdiv(w.Lp, kStoiTile), 2u * P), dim3(256), 0, st, est, ref, taps, n_taps, ws, P, L, ld_e,
-                           ld_r, up, down);
-    if (w.NF > 0) hipLaunchKernelGGL(k_stoi_energy, dim3((unsigned)cdiv(w.NF, 4), (unsigned)P), dim3(256), 0, st, est, ref, ws, P, L, ld_e, ld_r, up, down, resampled);
-    hipLaunchKernelGGL(k_stoi_mask, dim3((unsigned)P), dim3(256), 0, st, ws, P, L, up, down);
-    if (w.Tmax > 0)
-        hipLaunchKernelGGL(k_stoi_spec, dim3((unsigned)w.Tmax, 2u * P), dim3(256), 0, st, est, ref, ws, P, L, ld_e, ld_r, up, down, resampled);
-    if (w.Smax > 0) hipLaunchKernelGGL(k_stoi_corr, dim3((unsigned)w.Smax, (unsigned)P), dim3(256), 0, st, ws, P, L, up, down);
-    hipLaunchKernelGGL(k_stoi_finish, dim3((unsigned)P), dim3(256), 0, st, (const double*)ws, d, P, L, up, down);
-    return launch_status("fqss_stoi");
+    return stoi_run("fqss_stoi", est, ref, taps, n_taps, ws, ws_doubles, d, P, L, ld_e, ld_r, up, down, 1, stream);
+}
+
+extern "C" int64_t fqss_stoi_x_ws_doubles(int P, int64_t L, int up, int down, int modes) {
+    if (!stoi_shape_ok(P, L, up, down) || modes < 1 || modes > 3) return 0;
+    return stoi_ws_total(stoi_layout(P, L, up, down), P, modes);
+}
+
+extern "C" int fqss_stoi_x(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
+                           int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, int modes, fqss_stream_t stream) {
+    return stoi_run("fqss_stoi_x", est, ref, taps, n_taps, ws, ws_doubles, d, P, L, ld_e, ld_r, up, down, modes, stream);
 }

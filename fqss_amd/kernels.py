@@ -2951,22 +2951,31 @@ def stoi_taps(fs, device):
     return _stoi_taps[key]
 
 
-def stoi(est, ref, fs):
+def stoi(est, ref, fs, extended=False):
     """est, ref [P, L] (rows may be pitched views; ref = the clean signals) sampled at `fs` -> short-time objective intelligibility of
     each pair, fp64 [P]: pystoi.stoi(clean, estimate, fs, extended=False) restated, see fqss_stoi in include/fqss.h; 1e-5 where fewer
-    than 30 spectral frames are left.  Rates served: 8000, 10000, 16000 Hz"""
+    than 30 spectral frames are left.  Rates served: 8000, 10000, 16000 Hz.  extended=True: the extended measure (ESTOI, fqss_stoi_x in
+    include/fqss.h) instead; extended="both": (stoi, estoi) from one fqss_stoi_x call, the kernels up to the band matrices run once"""
     if int(fs) != fs or int(fs) not in STOI_RATES:
         raise NotImplementedError(f"stoi: sample rate {fs} Hz is not served (resampler tap tables exist for {STOI_RATES} only)")
+    assert extended is False or extended is True or extended == "both", "stoi: extended is False, True or 'both'"
     _need_gpu(est, ref)
     est, P, L, ld_e = as_rowmat(est)
     ref, P2, L2, ld_r = as_rowmat(ref)
     assert (P, L) == (P2, L2), "stoi: shape mismatch"
     taps, up, down = stoi_taps(fs, est.device)
-    n_ws = _lib.query("fqss_stoi_ws_doubles", P, L, up, down)
+    if extended is False:
+        n_ws = _lib.query("fqss_stoi_ws_doubles", P, L, up, down)
+        ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
+        d = torch.empty(P, device=est.device, dtype=torch.float64)
+        _lib.call("fqss_stoi", _p(est), _p(ref), _p(taps), taps.numel(), _p(ws), n_ws, _p(d), P, L, ld_e, ld_r, up, down, _stream())
+        return d
+    modes = 2 if extended is True else 3
+    n_ws = _lib.query("fqss_stoi_x_ws_doubles", P, L, up, down, modes)
     ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
-    d = torch.empty(P, device=est.device, dtype=torch.float64)
-    _lib.call("fqss_stoi", _p(est), _p(ref), _p(taps), taps.numel(), _p(ws), n_ws, _p(d), P, L, ld_e, ld_r, up, down, _stream())
-    return d
+    d = torch.empty((modes + 1) // 2, P, device=est.device, dtype=torch.float64)
+    _lib.call("fqss_stoi_x", _p(est), _p(ref), _p(taps), taps.numel(), _p(ws), n_ws, _p(d), P, L, ld_e, ld_r, up, down, modes, _stream())
+    return d[0] if modes == 2 else (d[0], d[1])
 
 
 def infer_ola(chunk, mp, out, sum_weight, start, n, seg):

@@ -156,21 +156,23 @@ def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):
                  load_diag=load_diag)
 
 
-def stoi(est, ref, sample_rate):
+def stoi(est, ref, sample_rate, extended=False):
     """Short-time objective intelligibility between matching rows of est / ref [..., L] sampled at `sample_rate` (torchmetrics'
     ShortTimeObjectiveIntelligibility(fs)(preds=est, target=ref) = pystoi.stoi(ref, est, fs), third party: the published definition
     restated, see fqss_stoi in include/fqss.h; process.py:147).  Leading dimensions are flattened to pairs; returns fp64 [pairs] on the
-    device.  Rates served: 8000, 10000, 16000 Hz."""
-    return K.stoi(est.reshape(-1, est.shape[-1]), ref.reshape(-1, ref.shape[-1]), sample_rate)
+    device.  Rates served: 8000, 10000, 16000 Hz.  extended=True: the extended measure (ESTOI, fqss_stoi_x) instead; "both": the pair
+    (stoi, estoi) from one call."""
+    return K.stoi(est.reshape(-1, est.shape[-1]), ref.reshape(-1, ref.shape[-1]), sample_rate, extended=extended)
 
 
-def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000, with_sdr=True, with_stoi=False):
+def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000, with_sdr=True, with_stoi=False, stoi_extended=False):
     """(SI-SNR, SDR, STOI) averaged over the sources (process.py:127-154): every estimate is paired with the target of its best SI-SNR
     (first maximum) and the metrics are taken on that pair.  The pairing stays on the device (first-maximum index + gather) and all
     pairs go through one fqss_sdr launch.  A silent matched target makes that pair's SDR, and so the mean, NaN, as numpy.mean does in
     the reference.  with_sdr=False leaves the SDR slot NaN (val.py's mixture baseline uses the SI-SNR slot only).  with_stoi=True fills
     the STOI slot with the mean fqss_stoi of the same pairs at `sample_rate` (one more launch sequence, the same single read-back);
-    by default it stays NaN, as it was while pystoi -- third party and absent -- had no restatement here."""
+    by default it stays NaN, as it was while pystoi -- third party and absent -- had no restatement here.  stoi_extended=True puts the
+    extended measure (ESTOI, fqss_stoi_x) into that slot instead."""
     S = clean_waveforms.shape[0]
     est, clean = sep_waveform.reshape(S, -1), clean_waveforms.reshape(S, -1)
     db = K.sisnr_matrix(est, clean)
@@ -185,7 +187,7 @@ def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000, with_sdr
     if with_sdr:
         means.append(K.sdr(est, matched).mean())
     if with_stoi:
-        means.append(K.stoi(est, matched, sample_rate).mean())
+        means.append(K.stoi(est, matched, sample_rate, extended=bool(stoi_extended)).mean())
     means = torch.stack(means).tolist()                                 # the one read-back
     return means[0], means[1] if with_sdr else float("nan"), means[-1] if with_stoi else float("nan")
 

@@ -3,7 +3,8 @@
 set and report SI-SDR, its improvement over the unprocessed mixture, and SDR (fqss_sdr: torchmetrics' SignalDistortionRatio
 restated).  `dataset_cfg.name: librimix` walks `testing_cfg.test_dir` as val.py:28-92 does (mix_clean | mix_both | mix_single,
 s1..s3; whole utterances, resampled on the device); `synthetic` evaluates seeded two-speaker mixtures.  STOI (pystoi: third party,
-absent) is printed as nan unless `testing_cfg.stoi: true` asks for fqss_stoi, the restated definition, at the utterance's rate.
+absent) is printed as nan unless `testing_cfg.stoi: true` asks for fqss_stoi, the restated definition, at the utterance's rate;
+`testing_cfg.stoi_extended: true` beside it puts the extended measure (ESTOI, fqss_stoi_x) into the same slot.
 MUSDB needs the `musdb` package (absent): refused.  `val()` returns (SI-SDR, improvement); the SDR and the STOI of the run are in
 the printed result line."""
 import argparse
@@ -32,14 +33,14 @@ SYNTHETIC_RATE = 8000      # the synthetic mixtures stand in for the 8 kHz confi
 def val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, device):
     n_srcs = model_cfg.get("n_src", 1)
     n, L = testing_cfg.get("n_items", 4), int(testing_cfg.get("length_samples", 32000))
-    with_stoi = bool(testing_cfg.get("stoi", False))
+    with_stoi, extended = bool(testing_cfg.get("stoi", False)), bool(testing_cfg.get("stoi_extended", False))
     sisdr = sisdr_imp = sdr = stoi = 0.0
     for i in range(n):
         mix, clean = synth_batch(1, L, seed=10_000 + i, device=device)
         mix_wav, clean_wavs = mix[0], clean[0]                         # [1, L], [S, L]
         wavs = model_infer(model, mix_wav, n_srcs=n_srcs, segment=testing_cfg.get("segment_samples", None),
                            overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs)
-        s, d, st = metric_evaluation(wavs, clean_wavs, sample_rate=SYNTHETIC_RATE, with_stoi=with_stoi)
+        s, d, st = metric_evaluation(wavs, clean_wavs, sample_rate=SYNTHETIC_RATE, with_stoi=with_stoi, stoi_extended=extended)
         base = K.sisnr_matrix(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous())
         sisdr += s
         sisdr_imp += s - torch.diagonal(base).mean().item()
@@ -84,7 +85,7 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
                 x = K.resample(x, fs, int(fs * ratio))
             return x[:1].unsqueeze(0), x[1:].unsqueeze(0)
 
-    with_stoi = bool(testing_cfg.get("stoi", False))
+    with_stoi, extended = bool(testing_cfg.get("stoi", False)), bool(testing_cfg.get("stoi_extended", False))
     rate = int(int(dataset_cfg.get("sample_rate", 16000)) * ratio)       # the utterance's rate after resampling (val.py:83 passes fs too)
     sisdr = sisdr_imp = sdr = stoi = 0.0
     for i, (mix, clean) in enumerate(Prefetcher(_Utterances(), [[k] for k in range(n)], device, depth=1)):
@@ -92,7 +93,7 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
         wavs = model_infer(model, mix_wav, n_srcs=n_srcs, segment=testing_cfg.get("segment_samples", None),
                            overlap=testing_cfg.get("overlap", 0.25), device=device, target=clean_wavs,
                            chunk_batch=testing_cfg.get("chunk_batch"))
-        s, d, st = metric_evaluation(wavs, clean_wavs, sample_rate=rate, with_stoi=with_stoi)
+        s, d, st = metric_evaluation(wavs, clean_wavs, sample_rate=rate, with_stoi=with_stoi, stoi_extended=extended)
         # val.py:86: the sources as estimates, the mixture as target; only its SI-SNR is used
         base, _, _ = metric_evaluation(clean_wavs, mix_wav.expand(n_srcs, -1).contiguous(), with_sdr=False)
         sisdr += s

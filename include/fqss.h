@@ -1280,6 +1280,27 @@ int64_t fqss_stoi_ws_doubles(int P, int64_t L, int up, int down);
 int fqss_stoi(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
               int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, fqss_stream_t stream);
 
+/* Extended STOI (ESTOI, Jensen & Taal 2016; pystoi.stoi(clean, estimate, fs, extended=True)) beside STOI in one pass (csrc/stoi.hip).
+ * Restated from the published definition like fqss_stoi: the pystoi package is absent, parity with it is NOT pinned by anything; the
+ * kernels are pinned to this statement and to an fp64 NumPy checker (tests/test_gpu_estoi.py).  Steps 1-4 of fqss_stoi are unchanged
+ * (resampling, framing, silent-frame removal, 512-point spectra into the band amplitudes X, Y [15][T]).  Then for every segment m of
+ * 30 consecutive columns (the segments of step 5; no clipping, no energy normalisation), on X_m and Y_m [15][30] alike:
+ *  a. Rows.  From each band's row its mean over the 30 columns is subtracted; the centred row is divided by its Euclidean norm.
+ *  b. Columns.  From each column its mean over the 15 bands is subtracted; the centred column is divided by its norm.
+ *  c. d_m = (1 / 30) sum over j, n of X^_m[j][n] Y^_m[j][n];  d = mean over m of d_m.  T < 30: d = 1e-5, as for STOI.
+ * Zero-norm rule, a DELIBERATE difference from the package: pystoi adds EPS * N(0, 1) noise before each normalisation, which keeps a
+ * constant row finite and makes its own output irreproducible at the 1e-16 level.  Here there is no noise and no EPS: a centred row or
+ * column whose norm is exactly 0 stays all zero (inv = norm > 0 ? 1 / norm : 0, and the row or column is multiplied by inv).  The rule is
+ * scale-invariant and bit-reproducible; an all-zero estimate gives d = 0 exactly.
+ * modes is a bit mask: 1 STOI (fqss_stoi's d, the same bits), 2 ESTOI, 3 both.  d [popcount(modes)][P] fp64 on the device, STOI's row
+ * first.  The kernels of steps 1-4 run once whatever the mask; each mode adds its own segment kernel and finish and keeps its own
+ * per-segment partials in the workspace.  ws: at least fqss_stoi_x_ws_doubles(P, L, up, down, modes) doubles (fqss_stoi_ws_doubles for
+ * modes 1 and 2, P max(NF - 30, 0) more for 3), uninitialised.  Fixed summation orders, no atomics: the same bits every run and on any
+ * stream.  Refused with FQSS_EINVAL, nothing written: everything fqss_stoi refuses, and modes outside 1..3 (the query then returns 0). */
+int64_t fqss_stoi_x_ws_doubles(int P, int64_t L, int up, int down, int modes);
+int fqss_stoi_x(const float* est, const float* ref, const double* taps, int n_taps, double* ws, int64_t ws_doubles, double* d, int P,
+                int64_t L, int64_t ld_e, int64_t ld_r, int up, int down, int modes, fqss_stream_t stream);
+
 /* Histogram-MSE activation observer (csrc/aq_mse.hip; GradientActivationFakeQuantize_MSE, qat_quant.py:245-326 of the reference, which runs
  * np.histogram, merge_hist and the 100 x 100 search of mse_minmax_range on the host).  The statement is that algorithm in fp64 with two
  * deviations: the edges are fp64 (numpy makes fp32 edges for fp32 input) and the merged grid is capped at FQSS_AQ_MSE_MAX_BINS points.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Probe of the STOI kernels (csrc/stoi.hip): one `kernels.stoi` call on two pairs of 10 s at 8 kHz beside `kernels.sdr` of the same
-pairs and `process.model_infer` of the same utterance (full ConvTasNet, whole utterance), device events after warm-up, median of 20.
+pairs and `process.model_infer` of the same utterance (full ConvTasNet, whole utterance), device events after warm-up, median of 20;
+the extended measure alone (`extended=True`) and both measures from one call (`extended="both"`) beside it.
 
   python tools/stoi_probe.py [--fs 8000] [--seconds 10]
   rocprofv3 --kernel-trace --stats -d <dir> -- python tools/stoi_probe.py --stoi-only      (per-kernel times)
@@ -52,6 +53,10 @@ def main():
     print(f"d = {d.tolist()}")
     med, best = median_ms(lambda: K.stoi(est, clean, a.fs))
     print(f"kernels.stoi           median {med:8.3f} ms   min {best:8.3f} ms")
+    print(f"extended d = {K.stoi(est, clean, a.fs, extended=True).tolist()}")
+    for name, ext in (("extended", True), ("both", "both")):
+        med, best = median_ms(lambda: K.stoi(est, clean, a.fs, extended=ext))
+        print(f"kernels.stoi {name:<9} median {med:8.3f} ms   min {best:8.3f} ms")
     if a.stoi_only:
         return
     med, best = median_ms(lambda: K.sdr(est, clean))
