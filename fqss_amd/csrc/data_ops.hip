@@ -152,6 +152,113 @@ __global__ __launch_bounds__(256) void k_hd_augment_mix(const int16_t* __restric
     }
 }
 
+// Sepformer recipe (train_env/speechbrain_librimix/prepare_data.py; reference: compute_forward of speechbrain_librimix_trainer.py:51-75,
+// 262-326 after the speed perturbation): random circular shift per source, re-mix, WHAM noise, `wavedrop` (speechbrain's
+// TimeDomainSpecAugment: DropFreq = one 101-tap FIR, the composed notches; DropChunk = zeroed intervals) and the random cut, worked
+// from the training window BACKWARDS: only the window plus a 50-sample halo each side is read, and nothing of utterance length is built.
+//   n = min_s L_s (min with L_n when noise is given, with L_m in premix mode);  t_s[b,p] = src_s[b][(p - shift_s) mod L_s],  0 <= p < n
+//   m[b,p] = ((t_0 + t_1) + ...) (+ noise[b,p] last), one rounding per add (premix: m = mix_in, nothing summed);  m = 0 outside [0, n)
+//   f[b,p] = acc_101, acc_0 = 0, acc_{k+1} = fmaf(h[k], m[b, p + k - 50], acc_k)        (filter = 0: f = m, bit for bit)
+//   mix[b,q] = (exists c < n_chunk[b]: lo_c <= start + q < hi_c) ? 0 : f[b, start + q];   tgt[b,s,q] = t_s[b, start + q]
+// A workgroup owns SB_TILE = 1024 outputs of one item.  Phase 1: the 256 lanes walk the SB_TILE + 100 positions of the tile and its
+// halo, stride 256 (every load and every target store is one dense 1 KB line per wave); a lane gathers its position from the S rolled
+// sources -- one wrap compare per source, no modulo --, forms m in registers, writes the targets of the inner positions and parks m in
+// LDS as fp32 (4496 bytes), zero where p falls outside [0, n).  One barrier.  Phase 2: a lane owns 4 consecutive outputs and slides over
+// its 104 LDS values as 26 ds_read_b128 (16 bytes per lane, consecutive across lanes: no bank conflict), two of them live at a time; the
+// taps are indexed by the unrolled loop counter alone, so they are scalar loads; 4 independent fma chains, each in tap order k = 0..100.
+// Then the chunk rows of the item (uniform per workgroup: scalar loads) and one 16-byte store (T_out % 4 == 0; scalar otherwise).
+// No atomics, no workspace: the same bits every run and on any stream.  shift, start and the lengths are checked by the entry point;
+// the chunk table is device memory and only selects which outputs become zero -- no index is formed from it.
+constexpr int SB_TILE = 1024, SB_HALO = 50, SB_TAPS = 2 * SB_HALO + 1, SB_SPAN = SB_TILE + 2 * SB_HALO;
+
+struct SbArgs {
+    const float* src[3];
+    int64_t L[3], ld[3], shift[3];
+    const float* noise; int64_t ld_n;
+    const float* mix_in; int64_t ld_m;
+    const float* h;
+    const int* chunk; const int* n_chunk;
+    float* mix; float* tgt;
+    int64_t n, start, T_out;
+    int filter;
+};
+
+template <int S, bool WIDE>
+__global__ __launch_bounds__(256) void k_sb_augment(const SbArgs a) {
+    __shared__ __attribute__((aligned(16))) float m_lds[SB_SPAN];
+    const int64_t b = blockIdx.y;
+    const int64_t q0 = (int64_t)blockIdx.x * SB_TILE;
+    const float* __restrict__ h = a.h;
+    for (int i = threadIdx.x; i < SB_SPAN; i += 256) {
+        const int64_t q = q0 + i - SB_HALO, p = a.start + q;
+        const bool inner = i >= SB_HALO && i < SB_HALO + SB_TILE && q < a.T_out;       // inner => 0 <= p < n (start + T_out <= n)
+        float m = 0.0f;
+        if (p >= 0 && p < a.n) {
+            const bool sum = a.mix_in == nullptr;
+            if (sum || inner) {
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    int64_t j = p - a.shift[s];                                       // in (-L_s, n): one wrap brings it into [0, L_s)
+                    if (j < 0) j += a.L[s];
+                    const float t = a.src[s][b * a.ld[s] + j];
+                    m = s == 0 ? t : m + t;
+                    if (inner) a.tgt[(b * S + s) * a.T_out + q] = t;
+                }
+            }
+            if (!sum) m = a.mix_in[b * a.ld_m + p];
+            else if (a.noise) m = m + a.noise[b * a.ld_n + p];
+        }
+        m_lds[i] = m;
+    }
+    __syncthreads();
+    const int o0 = 4 * threadIdx.x;
+    const int64_t q = q0 + o0;
+    if (q >= a.T_out) return;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4* __restrict__ lv = reinterpret_cast<const f4*>(m_lds) + threadIdx.x;     // lv[j] = m_lds[o0 + 4 j .. + 3]
+    float out[4];
+    if (a.filter) {
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        f4 lo = lv[0];
+#pragma unroll
+        for (int kk = 0; kk < SB_TAPS; kk += 4) {                                      // taps kk .. kk + 3 see m_lds[o0 + kk .. o0 + kk + 6]
+            const f4 hi = kk + 4 < SB_TAPS ? lv[kk / 4 + 1] : lo;                      // (the last round holds tap 100 alone)
+            const float w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (kk + j < SB_TAPS) {
+                    const float hk = h[kk + j];
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) acc[o] = fmaf(hk, w[j + o], acc[o]);
+                }
+            }
+            lo = hi;
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o) out[o] = acc[o];
+    } else {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) out[o] = m_lds[SB_HALO + o0 + o];
+    }
+    const int nc = a.n_chunk ? min(a.n_chunk[b], FQSS_SB_C_MAX) : 0;
+    for (int c = 0; c < nc; ++c) {
+        const int64_t lo = a.chunk[(b * FQSS_SB_C_MAX + c) * 2], hi = a.chunk[(b * FQSS_SB_C_MAX + c) * 2 + 1];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const int64_t p = a.start + q + o;
+            if (p >= lo && p < hi) out[o] = 0.0f;
+        }
+    }
+    float* __restrict__ y = a.mix + b * a.T_out + q;
+    if (WIDE) {
+        *reinterpret_cast<f4*>(y) = f4{out[0], out[1], out[2], out[3]};
+    } else {
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+            if (q + o < a.T_out) y[o] = out[o];
+    }
+}
+
 }  // namespace fqss
 
 using namespace fqss;
@@ -206,4 +313,49 @@ extern "C" int fqss_hd_augment_mix(const int16_t* pcm, const float* mean, const 
     else        { if (wide) FQSS_HD_AUG(1, 4); else FQSS_HD_AUG(1, 1); }
 #undef FQSS_HD_AUG
     return launch_status("fqss_hd_augment_mix");
+}
+
+// src_s fp32 [B] rows of L_s samples, row stride ld_s (src1 / src2 NULL past S); noise / mix_in nullable, rows of L_n / L_m samples;
+// taps [101] fp32 (read only when filter != 0); chunk int32 [B][FQSS_SB_C_MAX][2] = (lo, hi) and n_chunk int32 [B], both nullable
+// together (no chunk anywhere); mix fp32 [B][T_out], tgt fp32 [B][S][T_out].  Everything that forms an address is checked here.
+extern "C" int fqss_sb_augment(const float* src0, const float* src1, const float* src2, int64_t L0, int64_t L1, int64_t L2, int64_t ld0,
+                               int64_t ld1, int64_t ld2, int64_t shift0, int64_t shift1, int64_t shift2, const float* noise, int64_t L_n,
+                               int64_t ld_n, const float* mix_in, int64_t L_m, int64_t ld_m, const float* taps, const int* chunk,
+                               const int* n_chunk, float* mix, float* tgt, int B, int S, int64_t start, int64_t T_out, int filter,
+                               fqss_stream_t stream) {
+    FQSS_REQUIRE(B > 0 && B <= 65535 && S >= 1 && S <= 3 && T_out > 0 && start >= 0, "bad shape");
+    FQSS_REQUIRE(mix && tgt && (!filter || taps) && (chunk != nullptr) == (n_chunk != nullptr), "null pointer");
+    SbArgs a = {};
+    const float* src[3] = {src0, src1, src2};
+    const int64_t L[3] = {L0, L1, L2}, ld[3] = {ld0, ld1, ld2}, shift[3] = {shift0, shift1, shift2};
+    int64_t n = INT64_MAX;
+    for (int s = 0; s < S; ++s) {
+        FQSS_REQUIRE(src[s], "null source");
+        FQSS_REQUIRE(L[s] > 0 && ld[s] >= L[s] && shift[s] >= 0 && shift[s] < L[s], "source length, stride or shift out of range");
+        FQSS_REQUIRE(!mix_in || shift[s] == 0, "premix mode takes no shift");
+        a.src[s] = src[s]; a.L[s] = L[s]; a.ld[s] = ld[s]; a.shift[s] = shift[s];
+        if (L[s] < n) n = L[s];
+    }
+    if (mix_in) {
+        FQSS_REQUIRE(!noise, "premix mode takes no noise");
+        FQSS_REQUIRE(L_m > 0 && ld_m >= L_m, "mixture length or stride out of range");
+        if (L_m < n) n = L_m;
+    } else if (noise) {
+        FQSS_REQUIRE(L_n > 0 && ld_n >= L_n, "noise length or stride out of range");
+        if (L_n < n) n = L_n;
+    }
+    FQSS_REQUIRE(n < ((int64_t)1 << 31) && T_out <= n && start <= n - T_out, "window outside [0, n) (or n >= 2^31: the chunk table is int32)");
+    const bool wide = T_out % 4 == 0 && (uintptr_t)mix % 16 == 0;
+    a.noise = noise; a.ld_n = ld_n; a.mix_in = mix_in; a.ld_m = ld_m; a.h = taps; a.chunk = chunk; a.n_chunk = n_chunk;
+    a.mix = mix; a.tgt = tgt; a.n = n; a.start = start; a.T_out = T_out; a.filter = filter ? 1 : 0;
+    const dim3 grid((unsigned)cdiv(T_out, SB_TILE), (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+#define FQSS_SB_AUG(SS)                                                                                   \
+    do {                                                                                                  \
+        if (wide) hipLaunchKernelGGL((k_sb_augment<SS, true>), grid, dim3(256), 0, st, a);                \
+        else hipLaunchKernelGGL((k_sb_augment<SS, false>), grid, dim3(256), 0, st, a);                    \
+    } while (0)
+    if (S == 1) FQSS_SB_AUG(1); else if (S == 2) FQSS_SB_AUG(2); else FQSS_SB_AUG(3);
+#undef FQSS_SB_AUG
+    return launch_status("fqss_sb_augment");
 }

@@ -3183,3 +3183,129 @@ def hd_augment_mix(pcm, T_out, src_b, off, flip, gain, mean=None, std=None, sour
     _lib.call("fqss_hd_augment_mix", _p(pcm), base + 4 * n * e if mean is not None else None, base + (4 * n + B) * e if mean is not None else None,
               base, base + n * e, base + 2 * n * e, base + 3 * n * e, _p(sources), _p(mix), B, S, C, T_in, T_out, 0 if mean is None else 1, _stream())
     return mix, sources
+
+
+# ------------------------------------------------------------------ data side: Sepformer recipe, shift / re-mix / wavedrop / cut (csrc/data_ops.hip)
+SB_TAPS = 101
+SB_C_MAX = _lib.CONSTANTS["FQSS_SB_C_MAX"]
+
+
+def notch_taps(freqs, width=SB_TAPS, notch_width=0.05):
+    """The ONE filter speechbrain's DropFreq applies for the drawn notch frequencies `freqs` (fractions of Nyquist): fp64 [width] on the
+    host.  Restated from the published package (speechbrain.processing.signal_processing.notch_filter, speechbrain.processing.
+    speech_augmentation.DropFreq); speechbrain is absent and parity with it is NOT pinned (the package windows with torch's default,
+    periodic, Blackman window in fp32; this is the symmetric window in fp64, so the result is symmetric and orientation cannot matter).
+      x = arange(width) - pad;  f += notch_width;  sinc(t) = sin(t) / t, 1 at the centre
+      hlpf = sinc(3 (f - w) x) * blackman, / its sum;  hhpf = sinc(3 (f + w) x) * blackman, / minus its sum, + 1 at the centre
+    and, from the delta, filter <- the central `width` taps of filter * (hlpf + hhpf) for every frequency in turn.  [] -> the delta."""
+    import numpy as np
+    pad = width // 2
+    x = np.arange(width, dtype=np.float64) - pad
+    win = np.blackman(width)
+
+    def sinc(t):
+        return np.where(t == 0, 1.0, np.sin(t) / np.where(t == 0, 1.0, t))
+
+    h = np.zeros(width, dtype=np.float64)
+    h[pad] = 1.0
+    for f in freqs:
+        f = float(f) + notch_width
+        lp = sinc(3 * (f - notch_width) * x) * win
+        lp /= lp.sum()
+        hp = sinc(3 * (f + notch_width) * x) * win
+        hp /= -hp.sum()
+        hp[pad] += 1.0
+        h = np.convolve(h, lp + hp)[pad:pad + width]
+        h = 0.5 * (h + h[::-1])                      # symmetric in exact arithmetic; this removes the last-bit differences of the fp64 sums
+    return h
+
+
+def check_sb_augment(lengths, shifts, n, start, T_out, taps, chunks, B):
+    """Host-side gate of `sb_augment`: nothing is uploaded or launched unless every index is in range.  ValueError otherwise."""
+    if not 1 <= len(lengths) <= 3:
+        raise ValueError(f"sb_augment: S = {len(lengths)} sources (1 to 3 are built)")
+    if len(shifts) != len(lengths):
+        raise ValueError(f"sb_augment: {len(shifts)} shifts for {len(lengths)} sources")
+    for s, (L, sh) in enumerate(zip(lengths, shifts)):
+        if not 0 <= sh < L:
+            raise ValueError(f"sb_augment: shift[{s}] = {sh} outside [0, L = {L}) (reduce it modulo the source's length)")
+    if n >= 1 << 31:
+        raise ValueError(f"sb_augment: n = {n}: the chunk table travels as int32")
+    if T_out < 1 or start < 0 or start + T_out > n:
+        raise ValueError(f"sb_augment: start = {start}, T_out = {T_out} outside [0, n = {n}]")
+    if taps is not None:
+        if taps.numel() != SB_TAPS or not bool(torch.isfinite(taps).all()):
+            raise ValueError(f"sb_augment: taps must be {SB_TAPS} finite values")
+    if chunks is not None:
+        if len(chunks) != B:
+            raise ValueError(f"sb_augment: chunks has {len(chunks)} rows for a batch of {B}")
+        for b, row in enumerate(chunks):
+            if len(row) > SB_C_MAX:
+                raise ValueError(f"sb_augment: n_chunk[{b}] = {len(row)} > C_MAX = {SB_C_MAX}")
+            for lo, hi in row:
+                if not 0 <= lo <= hi <= n:
+                    raise ValueError(f"sb_augment: chunk ({lo}, {hi}) of item {b} outside 0 <= lo <= hi <= n = {n}")
+
+
+def _sb_rows(t, name):
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f"sb_augment: {name} must be fp32 [B, L], got {t.dtype} {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def sb_augment(sources, shifts, taps, chunks, start, T_out, noise=None, mix_in=None):
+    """sources: S (1..3) fp32 [B, L_s] device tensors (after the speed perturbation: the lengths differ) -> (mix [B, 1, T_out], tgt
+    [B, S, T_out]): circular shift of every source over its own length, left-to-right sum (+ noise, cut to the shortest), the 101-tap
+    FIR `taps` (None: no notch was drawn, the filter is skipped), the zeroed `chunks` and the window [start, start + T_out), in one
+    launch that reads only the window and a 50-sample halo (include/fqss.h: fqss_sb_augment).  mix_in [B, L_m]: premix mode, the given
+    mixture instead of the sum (no noise, shifts 0).  shifts: ints in [0, L_s); taps: a CPU tensor of 101 values; chunks: per item a
+    list of (lo, hi) with 0 <= lo <= hi <= n, at most SB_C_MAX of them, or None.  Every range is checked here, then one upload."""
+    sources = list(sources)
+    S = len(sources)
+    if not 1 <= S <= 3:
+        raise ValueError(f"sb_augment: S = {S} sources (1 to 3 are built)")
+    rows = [_sb_rows(t, f"sources[{s}]") for s, t in enumerate(sources)]
+    B = rows[0][0].shape[0]
+    if B < 1 or any(t.shape[0] != B for t, _ in rows):
+        raise ValueError("sb_augment: every source holds the same B >= 1 items")
+    shifts = [int(v) for v in shifts]
+    lengths = [int(t.shape[1]) for t, _ in rows]
+    if mix_in is not None and (noise is not None or any(shifts)):
+        raise ValueError("sb_augment: premix mode (mix_in) takes no noise and no shift")
+    extra = mix_in if mix_in is not None else noise
+    if extra is not None:
+        extra, ld_x = _sb_rows(extra, "mix_in" if mix_in is not None else "noise")
+        if extra.shape[0] != B:
+            raise ValueError("sb_augment: noise / mix_in must hold B items")
+    n = min(lengths + ([int(extra.shape[1])] if extra is not None else []))
+    start, T_out = int(start), int(T_out)
+    if taps is not None:
+        taps = torch.as_tensor(taps).detach().reshape(-1)
+    check_sb_augment(lengths, shifts, n, start, T_out, taps, chunks, B)
+    dev = rows[0][0].device
+    if _lib.BACKEND == "cpu" or any(not t.is_cuda or t.device != dev for t in [r[0] for r in rows] + ([extra] if extra is not None else [])):
+        raise _lib.FqssError("sb_augment runs on the HIP backend with the waveforms in ROCm device memory (no CPU fallback)")
+    has_chunks = chunks is not None and any(len(r) for r in chunks)
+    tab = torch.zeros(SB_TAPS + (B * (1 + 2 * SB_C_MAX) if has_chunks else 0), dtype=torch.int32)
+    if taps is not None:
+        tab[:SB_TAPS] = taps.to(torch.float32).contiguous().view(torch.int32)
+    if has_chunks:
+        for b, row in enumerate(chunks):
+            tab[SB_TAPS + b] = len(row)
+            if row:
+                o = SB_TAPS + B + b * 2 * SB_C_MAX
+                tab[o:o + 2 * len(row)] = torch.tensor(row, dtype=torch.int32).reshape(-1)
+    d = tab.to(dev, non_blocking=True)               # one small upload; freed into the current stream's pool, behind the launch that reads it
+    base, e = d.data_ptr(), d.element_size()
+    mix = torch.empty(B, 1, T_out, device=dev, dtype=torch.float32)
+    tgt = torch.empty(B, S, T_out, device=dev, dtype=torch.float32)
+    ptr = [_p(t) for t, _ in rows] + [None] * (3 - S)
+    L3, ld3, sh3 = lengths + [0] * (3 - S), [ld for _, ld in rows] + [0] * (3 - S), shifts + [0] * (3 - S)
+    is_noise, is_mix = (extra is not None and mix_in is None), mix_in is not None
+    _lib.call("fqss_sb_augment", *ptr, *L3, *ld3, *sh3, _p(extra) if is_noise else None, extra.shape[1] if is_noise else 0, ld_x if is_noise else 0,
+              _p(extra) if is_mix else None, extra.shape[1] if is_mix else 0, ld_x if is_mix else 0, base if taps is not None else None,
+              base + (SB_TAPS + B) * e if has_chunks else None, base + SB_TAPS * e if has_chunks else None, _p(mix), _p(tgt), B, S, start, T_out,
+              0 if taps is None else 1, _stream())
+    return mix, tgt

@@ -20,7 +20,7 @@ plain mappings and ignored.  Step semantics kept:
     from speechbrain 0.5.14's published behaviour: third-party, parity unpinned).
 Data: `dataset_cfg.name: librimix` is the reference's configuration (configs/sepformer_2spks_8k.yaml:27-39): `prepare_librimix` writes
 the CSVs into `save_folder`, `SbLibriMix` (prepare_data.py) serves whole utterances with the train-time speed perturbation / re-mix /
-random cut of `compute_forward` on the device, a batch ahead of the step (fqss_amd/loader.py); `synthetic`: seeded mixtures of
+random shift / `wavedrop` / random cut of `compute_forward` on the device, a batch ahead of the step (fqss_amd/loader.py); `synthetic`: seeded mixtures of
 `model_cfg.n_src` speakers.
 Every epoch ends with `<work_dir>/checkpoint.pth`, the full training state (what speechbrain's Checkpointer keeps); the top-level
 key `resume: <path> | auto` continues from one (fqss_amd/checkpoint.py)."""
@@ -137,11 +137,11 @@ class _Data:
             "train": SbLibriMix(os.path.join(save, f"libri{n_spks}mix_train-360.csv"), train=True, speeds=sp.get("speeds", (95, 100, 105)),
                                 use_speedperturb=bool(hp.get("use_speedperturb", False)), perturb_prob=sp.get("perturb_prob", 1.0),
                                 limit_training_signal_len=bool(hp.get("limit_training_signal_len", False)),
-                                training_signal_len=int(hp.get("training_signal_len", 32000)), **common),
+                                training_signal_len=int(hp.get("training_signal_len", 32000)),
+                                use_rand_shift=bool(hp.get("use_rand_shift", False)), min_shift=int(hp.get("min_shift", -8000)),
+                                max_shift=int(hp.get("max_shift", 8000)), use_wavedrop=bool(hp.get("use_wavedrop", False)),
+                                wavedrop=hp.get("wavedrop"), **common),
             "val": SbLibriMix(os.path.join(save, f"libri{n_spks}mix_dev.csv"), **common)}
-        for k in ("use_wavedrop", "use_rand_shift"):
-            if hp.get(k):
-                raise NotImplementedError(f"speechbrain env: {k} (off in every shipped config) has no device kernel")
 
     def batches(self, split, epoch):
         hp, comm = self.hp, self.comm

@@ -1387,6 +1387,31 @@ int fqss_resample_fir(const float* x, const float* h, float* y, int64_t rows, in
 int fqss_hd_augment_mix(const int16_t* pcm, const float* mean, const float* stdv, const int* src_b, const int* off, const int* flip,
                         const float* gain, float* sources, float* mix, int B, int S, int C, int64_t T_in, int64_t T_out, int normalise,
                         fqss_stream_t stream);
+/* Sepformer recipe of the speechbrain env (train_env/speechbrain_librimix/prepare_data.py; the reference's compute_forward,
+ * speechbrain_librimix_trainer.py:51-75, 262-326, after the speed perturbation): random circular shift per source, re-mix, WHAM noise,
+ * `wavedrop` (speechbrain's TimeDomainSpecAugment: DropFreq, the composed notch filters as ONE 101-tap FIR, then DropChunk, zeroed
+ * intervals) and the random cut, in one launch that works from the training window backwards.  speechbrain is absent: its published
+ * behaviour is restated (kernels.notch_taps, prepare_data.draw_wavedrop) and parity with the package is not pinned; the kernel is pinned
+ * to this statement.
+ *   src_s fp32 [B] rows of L_s samples (row stride ld_s), s < S, S = 1..3 (src1 / src2 NULL past S); 0 <= shift_s < L_s
+ *   n        = min_s L_s, then min(n, L_n) when noise is given                    (premix mode: min(n, L_m) instead)
+ *   t_s[b,p] = src_s[b][(p - shift_s) mod L_s]                  0 <= p < n     (torch.roll over the source's OWN length, then cut to n)
+ *   m[b,p]   = ((t_0 + t_1) + ...) (+ noise[b,p] last)          fp32, left to right, one rounding per add;  m = 0 outside [0, n)
+ *   f[b,p]   = acc_101,  acc_0 = 0,  acc_{k+1} = fmaf(h[k], m[b, p + k - 50], acc_k)      (zero padding, "same" length)
+ *   mix[b,q] = (exists c < n_chunk[b]: lo_c <= start + q < hi_c) ? 0 : f[b, start + q]     0 <= q < T_out,  start + T_out <= n
+ *   tgt[b,s,q] = t_s[b, start + q]                                                         (bit copies)
+ * Premix mode (mix_in != NULL; the reference with use_speedperturb off): m = mix_in [B] rows of L_m samples, nothing is summed, noise
+ * must be NULL and every shift 0 -- the dataset's own mixture goes through the filter and the mask, the targets are only cut.
+ * filter = 0 skips the FIR: f = m bit for bit (what the delta taps return as values; no notch was drawn).  taps: 101 fp32 on the device.
+ * chunk int32 [B][FQSS_SB_C_MAX][2] = (lo, hi) and n_chunk int32 [B] on the device, both NULL for "no chunk".  mix fp32 [B][T_out],
+ * tgt fp32 [B][S][T_out].  No atomics and no workspace: the same bits every run and on any stream.  The entry point checks what forms
+ * an address (lengths, strides, shifts, start, T_out; n < 2^31); the chunk table only selects outputs to zero, its ranges
+ * (0 <= lo <= hi <= n, n_chunk <= FQSS_SB_C_MAX) and the finiteness of the taps are the caller's to check BEFORE the upload.  HIP only. */
+#define FQSS_SB_C_MAX 16
+int fqss_sb_augment(const float* src0, const float* src1, const float* src2, int64_t L0, int64_t L1, int64_t L2, int64_t ld0, int64_t ld1,
+                    int64_t ld2, int64_t shift0, int64_t shift1, int64_t shift2, const float* noise, int64_t L_n, int64_t ld_n,
+                    const float* mix_in, int64_t L_m, int64_t ld_m, const float* taps, const int* chunk, const int* n_chunk, float* mix,
+                    float* tgt, int B, int S, int64_t start, int64_t T_out, int filter, fqss_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Descriptor-struct forms of the long entry points ("fqss_<op>_{fwd,bwd}(const FqssTensor* in..,
