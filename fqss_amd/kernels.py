@@ -3185,6 +3185,88 @@ def hd_augment_mix(pcm, T_out, src_b, off, flip, gain, mean=None, std=None, sour
     return mix, sources
 
 
+# ------------------------------------------------------------------ data side: repitch of the htdemucs env (csrc/repitch.hip)
+REPITCH_RATIOS = {-2: (49, 55), -1: (17, 18), 0: (1, 1), 1: (18, 17), 2: (55, 49)}     # semitones -> rho = P / Q (include/fqss.h)
+RP_HS, RP_V, RP_R, RP_J, RP_HQ_ROWS = _h("RP_HS", "RP_V", "RP_R", "RP_J", "RP_HQ_ROWS")
+RP_BOTH = sum(_h("RP_SEARCH", "RP_RESAMPLE"))
+RP_A_RANGE = (0.70, 1.45)                 # the stretch factors A / 2^16 the host lets through
+_RP_HQ = {}
+
+
+def repitch_taps(P, Q):
+    """int64 [Q, RP_J] numpy: the polyphase taps of the rate change by P / Q as include/fqss.h states them (Hann-windowed sinc, cutoff
+    0.9 * min(1, Q / P), fp64), every phase scaled to 2^15, rounded, its largest tap adjusted so that the integers sum to exactly 2^15."""
+    import numpy as np
+    P, Q, J = int(P), int(Q), RP_J
+    hq = np.zeros((Q, J), dtype=np.int64)
+    if P == Q:
+        hq[:, J // 2 - 1] = 1 << 15
+        return hq
+    w = 0.9 * min(1.0, Q / P)
+    u = (np.arange(J, dtype=np.float64) - (J // 2 - 1))[None, :] - np.arange(Q, dtype=np.float64)[:, None] / Q
+    h = w * np.sinc(w * u) * np.cos(np.pi * u / J) ** 2
+    hq[:] = np.rint(h / h.sum(axis=1, keepdims=True) * (1 << 15)).astype(np.int64)
+    hq[np.arange(Q), hq.argmax(axis=1)] += (1 << 15) - hq.sum(axis=1)
+    return hq
+
+
+def repitch_table():
+    """int32 [RP_HQ_ROWS, RP_J] CPU tensor: the taps of the five ratios one after the other, in pitch order -2..+2"""
+    import numpy as np
+    hq = torch.from_numpy(np.concatenate([repitch_taps(*REPITCH_RATIOS[k]) for k in sorted(REPITCH_RATIOS)])).to(torch.int32)
+    assert hq.shape == (RP_HQ_ROWS, RP_J)
+    return hq
+
+
+def repitch_A(pitch, tempo):
+    """A = round(tau * Q / P * 2^16) of the statement, in fp64 on the host; pitch in semitones, tempo in percent"""
+    P, Q = REPITCH_RATIOS[int(pitch)]
+    return int(round((1.0 + float(tempo) / 100.0) * Q / P * 65536.0))
+
+
+def check_repitch_rows(B, S, C, T_in, T_rp, on, pitch, A):
+    """Host-side gate of `hd_repitch`: nothing is uploaded unless every row is in range.  on / pitch / A: CPU integer tensors of B * S
+    elements (pitch in semitones).  ValueError otherwise."""
+    if C not in (1, 2) or B < 1 or S < 1 or B * S > 65535 or T_rp < 1 or T_in < T_rp or T_in >= 1 << 30:
+        raise ValueError(f"hd_repitch: bad shape B={B} S={S} C={C} T_in={T_in} T_rp={T_rp}")
+    for name, t in (("on", on), ("pitch", pitch), ("A", A)):
+        if not isinstance(t, torch.Tensor) or t.is_cuda:
+            raise ValueError(f"hd_repitch: {name} must be a CPU tensor (its range is checked on the host before the upload)")
+        if t.dtype not in (torch.int32, torch.int64) or t.numel() != B * S:
+            raise ValueError(f"hd_repitch: {name} must be an integer tensor of {B * S} elements, got {t.dtype} x {t.numel()}")
+    if int(on.min()) < 0 or int(on.max()) > 1:
+        raise ValueError("hd_repitch: on outside {0, 1}")
+    if int(pitch.min()) < min(REPITCH_RATIOS) or int(pitch.max()) > max(REPITCH_RATIOS):
+        raise ValueError(f"hd_repitch: pitch outside [{min(REPITCH_RATIOS)}, {max(REPITCH_RATIOS)}] semitones")
+    lo, hi = (int(round(v * 65536)) for v in RP_A_RANGE)
+    if int(A.min()) < lo or int(A.max()) > hi:
+        raise ValueError(f"hd_repitch: A outside [{RP_A_RANGE[0]}, {RP_A_RANGE[1]}] * 2^16")
+
+
+def hd_repitch(pcm, T_rp, on, pitch, A, return_pos=False):
+    """pcm int16 [B, S, T_in, C] on the device -> int16 [B, S, T_rp, C]: rows that are on are stretched by A / 2^16 (WSOLA) and
+    resampled by their pitch's ratio, the others cropped (include/fqss.h: fqss_hd_repitch, integers only).  on / pitch (semitones) / A
+    [B, S] are CPU tensors: every range is checked here, then one upload.  return_pos: also the segment positions int32 [B, S, M]."""
+    if pcm.dim() != 4 or pcm.dtype != torch.int16:
+        raise ValueError(f"hd_repitch: pcm must be int16 [B, S, T_in, C], got {pcm.dtype} {tuple(pcm.shape)}")
+    B, S, T_in, C = pcm.shape
+    T_rp = int(T_rp)
+    check_repitch_rows(B, S, C, T_in, T_rp, on, pitch, A)
+    if not pcm.is_cuda or _lib.BACKEND == "cpu":
+        raise _lib.FqssError("hd_repitch runs on the HIP backend with pcm in ROCm device memory (no CPU fallback)")
+    pcm = pcm.contiguous()
+    hq = _RP_HQ.get(pcm.device)
+    if hq is None:
+        hq = _RP_HQ[pcm.device] = repitch_table().to(pcm.device)
+    rows = torch.stack([on.reshape(-1), pitch.reshape(-1) - min(REPITCH_RATIOS), A.reshape(-1)], dim=1).to(torch.int32)
+    d = rows.contiguous().to(pcm.device, non_blocking=True)    # one small upload; freed into the current stream's pool, behind the launches
+    M = _lib.query("fqss_hd_repitch_ws_bytes", B, S, T_rp) // (4 * B * S)
+    pos = torch.empty(B, S, M, device=pcm.device, dtype=torch.int32)
+    out = torch.empty(B, S, T_rp, C, device=pcm.device, dtype=torch.int16)
+    _lib.call("fqss_hd_repitch", _p(pcm), _p(d), _p(hq), _p(pos), _p(out), B, S, C, T_in, T_rp, RP_BOTH, _stream())
+    return (out, pos) if return_pos else out
+
+
 # ------------------------------------------------------------------ data side: Sepformer recipe, shift / re-mix / wavedrop / cut (csrc/data_ops.hip)
 SB_TAPS = 101
 SB_C_MAX = _lib.CONSTANTS["FQSS_SB_C_MAX"]

@@ -15,8 +15,9 @@ reference always reads configs/htdemucs.yaml through hydra.  Step semantics kept
   * every epoch ends with `<work_dir>/checkpoint.pth`, the full training state (the place of the solver's checkpoint.th); `resume=<path>`
     or `resume=auto` continues from one (fqss_amd/checkpoint.py).
 Data: `dset.name: synthetic` (seeded Gaussian stems), or folders of WAV stems (`dset.wav` / `dset.musdb` + `use_musdb`, wav_dataset.py):
-a prefetching reader a batch ahead of the step, int16 samples to the device, demucs' augmentations (shift / flip / scale / remix, restated)
-and the mixture in one fused kernel; validation is un-augmented windows of the training length.  demucs' repitch, EMA copies,
+a prefetching reader a batch ahead of the step, int16 samples to the device, demucs' repitch (kernels.hd_repitch, an integer restatement:
+soundstretch is absent), its other augmentations (shift / flip / scale / remix, restated) and the mixture in one fused kernel;
+validation is un-augmented windows of the training length.  EMA copies,
 `apply_model` split inference and the SDR evaluation are the reference's CPU / third-party data side."""
 import json
 import os
@@ -106,7 +107,7 @@ class Solver:
         self.ckpt_file = os.path.join(conf["work_dir"], checkpoint.NAME)
         self.sets = None
         if wav_dataset.configured(conf["dset"]):
-            # refusals first (repitch, a per-GPU batch the remix groups do not divide): nothing is read before them
+            # refusals first (a repitch range that is not built, a per-GPU batch the remix groups do not divide): nothing is read before them
             wav_dataset.check_augment_cfg(conf.get("augment"), conf["batch_size"] // comm.world)
             train_set, valid_set = wav_dataset.build_datasets(conf, device)
             if len(train_set.sources) != model.n_srcs:

@@ -24,7 +24,13 @@ Validation departs from the reference ON PURPOSE: the reference validates whole 
 overlap-add inference) against `mixture.wav`; here the validation set is consecutive windows of the training length over each
 validation track, un-augmented (identity table), the mixture being the left-to-right sum of the stems.
 
-`augment.repitch.proba > 0` is refused: it needs the external `soundstretch` program."""
+  repitch   `augment.repitch` (demucs' RepitchedWrapper: proba, max_pitch, max_tempo, tempo_std, same).  demucs shells out to the
+            external `soundstretch` program, which is absent: proba > 0 alone is refused, as it always was.  With the key
+            `engine: wsola` (not demucs') a drawn item is stretched (WSOLA) and resampled on the device by
+            kernels.hd_repitch, in integers, as include/fqss.h states it at fqss_hd_repitch.  Parity with soundstretch is not pinned;
+            its `-speech` mode for demucs' `vocals` list is not distinguished (one parameter set serves every stem); a semitone is a
+            small rational (18/17, 55/49).  With it on, an example leaves the repitch T_rp = int((1 - max_tempo / 100) * seg) long
+            (demucs' `out_length`), repitched or not, and a step sees T_rp - stride samples; validation windows follow."""
 import json
 import math
 import os
@@ -67,12 +73,47 @@ def identity_table(B, S):
     return AugmentTable(torch.arange(B, dtype=torch.int64)[:, None].expand(B, S).contiguous(), z, z.clone(), torch.ones(B, S, dtype=torch.float32))
 
 
-def check_augment_cfg(cfg, batch_size=None):
-    """refusals that do not depend on a draw: repitch, and a batch the remix groups do not divide"""
-    cfg = cfg or {}
-    if float((cfg.get("repitch") or {}).get("proba") or 0) > 0:
+def repitch_cfg(cfg):
+    """the `augment.repitch` block with demucs' defaults, or None when proba is 0 or absent.  demucs' own repitch (the external
+    `soundstretch` program) stays refused, as before: the device restatement is not soundstretch, so a recipe names it,
+    `augment.repitch.engine: wsola`, before proba > 0 is taken."""
+    r = (cfg or {}).get("repitch") or {}
+    if not float(r.get("proba") or 0) > 0:
+        return None
+    engine = r.get("engine") or "soundstretch"
+    if engine == "soundstretch":
         raise NotImplementedError("augment.repitch.proba > 0: repitch needs the external `soundstretch` program and is not built "
-                                  "(set augment.repitch.proba: 0)")
+                                  "(set augment.repitch.engine: wsola for the restatement on the device, or augment.repitch.proba: 0)")
+    if engine != "wsola":
+        raise ValueError(f"augment.repitch.engine {engine!r}: wsola | soundstretch")
+    return dict(proba=float(r["proba"]), max_pitch=int(r.get("max_pitch", 2)), max_tempo=float(r.get("max_tempo", 12)),
+                tempo_std=float(r.get("tempo_std", 5)), same=bool(r.get("same", True)))
+
+
+def repitch_length(T_in, cfg):
+    """demucs' `out_length`: what an example of T_in samples is cut to behind the repitch (T_in itself when repitch is off)"""
+    r = repitch_cfg(cfg)
+    return int(T_in) if r is None else int((1 - 0.01 * r["max_tempo"]) * int(T_in))
+
+
+def check_augment_cfg(cfg, batch_size=None):
+    """refusals that do not depend on a draw: repitch without `engine: wsola` or with a range the kernel is not built for, and a batch
+    the remix groups do not divide"""
+    cfg = cfg or {}
+    r = repitch_cfg(cfg)
+    if r is not None:
+        if not 0 <= r["max_pitch"] <= max(K.REPITCH_RATIOS):
+            raise ValueError(f"augment.repitch.max_pitch {r['max_pitch']}: 0 to {max(K.REPITCH_RATIOS)} semitones are built (one rational "
+                             "ratio per semitone, kernels.REPITCH_RATIOS)")
+        if not 0 <= r["max_tempo"] < 25:
+            raise ValueError(f"augment.repitch.max_tempo {r['max_tempo']}: 0 <= max_tempo < 25 is built")
+        if not 0 < r["proba"] <= 1 or not r["tempo_std"] >= 0:
+            raise ValueError(f"augment.repitch: proba {r['proba']} / tempo_std {r['tempo_std']} out of range")
+        P, Q = K.REPITCH_RATIOS[r["max_pitch"]]
+        lo, hi = (1 - 0.01 * r["max_tempo"]) * Q / P, (1 + 0.01 * r["max_tempo"]) * P / Q
+        if lo < K.RP_A_RANGE[0] or hi > K.RP_A_RANGE[1]:
+            raise ValueError(f"augment.repitch: max_pitch {r['max_pitch']} with max_tempo {r['max_tempo']} stretches by {lo:.3f} to {hi:.3f}; "
+                             f"{K.RP_A_RANGE[0]} to {K.RP_A_RANGE[1]} is built")
     remix = cfg.get("remix") or {}
     if batch_size is not None and float(remix.get("proba") or 0) > 0:
         g = int(remix.get("group_size") or batch_size)
@@ -118,6 +159,31 @@ def draw_augment(B, S, C, shift, cfg, generator):
         src_b = (perm + gs * torch.arange(B // gs, dtype=torch.int64)[:, None, None]).reshape(B, S)
         off, flip, gain = off.gather(0, src_b), flip.gather(0, src_b), gain.gather(0, src_b)
     return AugmentTable(src_b, off, flip, gain)
+
+
+class RepitchTable(NamedTuple):
+    """one row per (b, s) of the batch as it is read: on -> stem s of item b is stretched by A / 2^16 and resampled by its pitch's ratio"""
+    on: torch.Tensor            # [B, S] int64, 0 | 1
+    pitch: torch.Tensor         # [B, S] int64, semitones
+    tempo: torch.Tensor         # [B, S] float64, percent (0 where off)
+    A: torch.Tensor             # [B, S] int64 = round((1 + tempo / 100) * Q / P * 2^16), 2^16 where off
+
+
+def draw_repitch(B, S, cfg, generator):
+    """demucs' RepitchedWrapper, restated: per item (`same`, demucs' default) or per (item, stem), rand() < proba switches the repitch
+    on; then pitch = randint(-max_pitch, max_pitch) inclusive and tempo = clamp(normal(0, tempo_std), +-max_tempo) percent.  Three draws of
+    the whole shape from `generator`, in this order: the switch, the pitch, the tempo; rows that are off keep pitch 0 / tempo 0.
+    demucs' `vocals` list (soundstretch's -speech mode) is not distinguished: one parameter set serves every stem."""
+    r = repitch_cfg(cfg)
+    if r is None:
+        raise ValueError("draw_repitch: augment.repitch.proba is 0 or absent")
+    shape = (B, 1) if r["same"] else (B, S)
+    on = (torch.rand(shape, generator=generator, dtype=torch.float64) < r["proba"]).to(torch.int64)
+    pitch = torch.randint(-r["max_pitch"], r["max_pitch"] + 1, shape, generator=generator) * on
+    tempo = (torch.randn(shape, generator=generator, dtype=torch.float64) * r["tempo_std"]).clamp_(-r["max_tempo"], r["max_tempo"]) * on
+    on, pitch, tempo = (t.expand(B, S).contiguous() for t in (on, pitch, tempo))
+    A = torch.tensor([K.repitch_A(p, t) for p, t in zip(pitch.reshape(-1).tolist(), tempo.reshape(-1).tolist())], dtype=torch.int64).reshape(B, S)
+    return RepitchTable(on, pitch, tempo, A)
 
 
 # ---- files ------------------------------------------------------------------------------------------------------------------------
@@ -285,7 +351,10 @@ class WavStems:
         self.stride = int(self.samplerate * (shift or 0))
         if seg <= self.stride or seg < 1:
             raise ValueError(f"dset.segment ({seg} samples) must be longer than dset.shift ({self.stride} samples)")
-        self.T_out = seg - self.stride                       # what a step sees
+        self.T_rp = repitch_length(seg, self.augment)        # what the repitch leaves of an example (seg when it is off)
+        if self.T_rp <= self.stride:
+            raise ValueError(f"augment.repitch leaves {self.T_rp} samples of a segment, dset.shift crops {self.stride}")
+        self.T_out = self.T_rp - self.stride                 # what a step sees
         self.T_in = seg if self.train else self.T_out        # what an example holds
         self.hop = (self.stride or seg) if self.train else self.T_out
         meta = load_metadata(self.tracks, self.sources, self.samplerate, self.channels, self.normalize, cache_file)
@@ -314,6 +383,11 @@ class WavStems:
     def host_batch(self, indices, stage=None):
         """(pcm int16 [B, S, T_in, C] -- a view of `stage` when one is given --, table, mean [B] | None, std [B] | None), all on the
         host: the files' samples as they are, zeros behind the end of a track"""
+        return self.host_batch_repitch(indices, stage)[:4]
+
+    def host_batch_repitch(self, indices, stage=None):
+        """host_batch and, fifth, the repitch rows of a training batch (None when repitch is off): drawn from the batch's generator BEHIND
+        every draw of the chain and only when repitch is on, so the chain's table does not depend on the switch"""
         B, S, C, T = len(indices), len(self.sources), self.channels, self.T_in
         n = B * S * T * C
         if stage is not None:
@@ -324,6 +398,7 @@ class WavStems:
             pcm = torch.empty(B, S, T, C, dtype=torch.int16)
         hv = pcm.numpy()
         where = [self.example(int(i)) for i in indices]
+        rp = None
         for b, (k, start) in enumerate(where):
             got = max(0, min(T, self.length[k] - start))
             for s, name in enumerate(self.sources):
@@ -341,21 +416,26 @@ class WavStems:
             seed = getattr(indices, "seed", None)
             if seed is None:
                 raise ValueError("a training batch carries the seed of its position (SeededBatch(indices, batch_seed(...)))")
-            table = draw_augment(B, S, C, self.stride, self.augment, torch.Generator().manual_seed(seed))
+            g = torch.Generator().manual_seed(seed)
+            table = draw_augment(B, S, C, self.stride, self.augment, g)
+            if repitch_cfg(self.augment) is not None:
+                rp = draw_repitch(B, S, self.augment, g)
         else:
             table = identity_table(B, S)
         mean = std = None
         if self.normalize:
             mean = torch.tensor([self.mean[k] for k, _ in where], dtype=torch.float64).to(torch.float32)
             std = torch.tensor([self.std[k] for k, _ in where], dtype=torch.float64).to(torch.float32)
-        return pcm, table, mean, std
+        return pcm, table, mean, std, rp
 
     # ---- device side ----------------------------------------------------------------------------------------------------------
     def batch(self, indices, stage=None):
         """(mix [B, C, T_out], sources [B, S, C, T_out]) on the device, enqueued on the calling thread's current stream: one upload of
-        the int16 block (asynchronous through the caller's pinned `stage`), one fused launch"""
-        pcm, table, mean, std = self.host_batch(indices, stage)
+        the int16 block (asynchronous through the caller's pinned `stage`), the repitch when the recipe has one, one fused launch"""
+        pcm, table, mean, std, rp = self.host_batch_repitch(indices, stage)
         dev = pcm.to(self.device, non_blocking=stage is not None)
+        if rp is not None:
+            dev = K.hd_repitch(dev, self.T_rp, rp.on, rp.pitch, rp.A)
         return K.hd_augment_mix(dev, self.T_out, table.src_b, table.off, table.flip, table.gain, mean, std)
 
 
@@ -367,5 +447,5 @@ def build_datasets(conf, device="cuda"):
     kw = dict(sources=d["sources"], samplerate=d["samplerate"], channels=d["channels"], segment=d["segment"], shift=d.get("shift") or 0,
               normalize=bool(d.get("normalize")), cache_file=cache, device=device)
     train = WavStems(train_dirs, train=True, augment=conf.get("augment"), **kw)
-    valid = WavStems(valid_dirs, train=False, max_examples=d.get("valid_samples"), **kw)
+    valid = WavStems(valid_dirs, train=False, augment=conf.get("augment"), max_examples=d.get("valid_samples"), **kw)     # the window length
     return train, valid

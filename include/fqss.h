@@ -1412,6 +1412,45 @@ int fqss_sb_augment(const float* src0, const float* src1, const float* src2, int
                     int64_t ld2, int64_t shift0, int64_t shift1, int64_t shift2, const float* noise, int64_t L_n, int64_t ld_n,
                     const float* mix_in, int64_t L_m, int64_t ld_m, const float* taps, const int* chunk, const int* n_chunk, float* mix,
                     float* tgt, int B, int S, int64_t start, int64_t T_out, int filter, fqss_stream_t stream);
+/* Repitch of the htdemucs env (csrc/repitch.hip; demucs' RepitchedWrapper, `augment.repitch` of the reference's configs/htdemucs.yaml,
+ * which shells out to the external `soundstretch` program).  soundstretch is absent: parity with it is NOT pinned, and its `-speech`
+ * mode for vocals is not distinguished.  What the kernels are pinned to, bit for bit, is this statement; it uses integers only.
+ *   pcm int16 [B][S][T_in][C], C = 1 | 2  ->  out int16 [B][S][T_rp][C], T_rp <= T_in.  A stream is one (b, s); its channels are processed
+ *   jointly.  x[i] = 0 for i outside [0, T_in).  rows int32 [B * S][3] = (on, pitch index, A), on the device.
+ * on == 0:  y[n] = x[n], n < T_rp (a crop).
+ * on == 1:  pitch index 0..4 = -2..+2 semitones selects rho = P / Q = 49/55, 17/18, 1/1, 18/17, 55/49 (1.05 and 0.02 cents off the
+ *   tempered semitones); with tau = 1 + tempo / 100 the HOST computes A = round(tau * Q / P * 2^16) in fp64.
+ * Stage 1, WSOLA stretch by A / 2^16, Hs = FQSS_RP_HS, V = FQSS_RP_V, R = FQSS_RP_R.  Segment m of the stretched stream z starts at
+ *   m * Hs and is copied from the input at p_m;  p_0 = 0 and for m >= 1, in int64,
+ *     n_m = (m * Hs * A) >> 16;   t[i] = x[p_{m-1} + Hs + i], i < V                 (the natural continuation of the previous segment)
+ *     cost(d) = sum over i < V and c of (x[n_m + d + i][c] - t[i][c])^2,  -R <= d <= R      (exact; below 2^42)
+ *     p_m = n_m + argmin_d cost(d), the LOWEST d among equal costs
+ *   z, held scaled by 512:  z512[m * Hs + i] = (V - i) * t[i] + i * x[p_m + i] for i < V and m >= 1, else 512 * x[p_m + i];  0 below index 0.
+ *   A stream has floor((floor((T_rp - 1) P / Q) + J / 2) / Hs) + 1 segments: up to the last index stage 2 reads.
+ * Stage 2, rate change by P / Q, J = FQSS_RP_J taps per phase.  For n < T_rp:  c = (n P) div Q,  phi = (n P) mod Q,
+ *     acc = sum over j < J of hq[phi][j] * z512[c - J / 2 + 1 + j]   (int64);   y[n] = clamp((acc + 2^23) >> 24, -32768, 32767),
+ *   the shift arithmetic.  hq: int32 [FQSS_RP_HQ_ROWS][J] on the device, the Q rows of the five ratios one after the other in pitch-index
+ *   order (55 + 18 + 1 + 17 + 49 rows).  The host builds them (kernels.repitch_taps): tap j of phase phi is the Hann-windowed sinc
+ *     w * sinc(w u) * cos^2(pi u / J),  sinc(v) = sin(pi v) / (pi v),  u = j - J / 2 + 1 - phi / Q,  w = 0.9 * min(1, Q / P),  in fp64,
+ *   every phase divided by its sum, times 2^15, rounded to nearest-even, and its largest tap (the first of equals) adjusted so that the
+ *   integers sum to exactly 2^15.  For
+ *   1 / 1 the single row is 2^15 at j = J / 2 - 1 and zero elsewhere, so on == 1 with A = 2^16 and p_m = m Hs returns x.
+ * pos_ws: int32 [B * S][M] workspace, M = fqss_hd_repitch_ws_bytes(B, S, T_rp) / (4 B S) (the segments of the largest ratio); on return
+ * row (b, s) holds p_m for that stream's segments and 0 elsewhere (every column for a stream that is off).  Two launches on `stream`:
+ * the search, one workgroup per stream, then the rate change over (tiles, streams); stages = FQSS_RP_SEARCH | FQSS_RP_RESAMPLE runs
+ * both, one bit alone that stage only (the rate change then reads the positions an earlier search left in pos_ws).  Every read of pcm is guarded by [0, T_in) whatever
+ * the rows hold; the caller still checks on in {0, 1}, the pitch index in [0, 4] and 0.70 <= A / 2^16 <= 1.45 BEFORE the upload.
+ * T_in < 2^30, B * S <= 65535.  HIP only.                                                                                           */
+#define FQSS_RP_HS 1536
+#define FQSS_RP_V 512
+#define FQSS_RP_R 512
+#define FQSS_RP_J 32
+#define FQSS_RP_HQ_ROWS 140
+#define FQSS_RP_SEARCH 1
+#define FQSS_RP_RESAMPLE 2
+int64_t fqss_hd_repitch_ws_bytes(int B, int S, int64_t T_rp);
+int fqss_hd_repitch(const int16_t* pcm, const int* rows, const int* hq, int* pos_ws, int16_t* out, int B, int S, int C, int64_t T_in,
+                    int64_t T_rp, int stages, fqss_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Descriptor-struct forms of the long entry points ("fqss_<op>_{fwd,bwd}(const FqssTensor* in..,
