@@ -11,15 +11,11 @@
 // ResidualErrorBlock (qat_layers.py:1330-1341, 1194-1202) and their autograd.
 #define FQSS_USES_GRAD_ADD   // the fp32 gradient atomics of this file go through grad_add (fqss_dev.h: FQSS_DETERMINISTIC=1)
 #include "fqss_mfma.h"
+#include "eval_dev.h"
 
 namespace fqss {
 
-// torch.clip(v, -128, 127) of process.py:14: a NaN stays NaN (fminf / fmaxf would return the bound, and the 0 / 0 of a silent row
-// would come out as -1 where the reference -- and include/fqss.h -- say NaN)
-__device__ __forceinline__ float split_clip(float v) {
-    v = v < -128.0f ? -128.0f : v;
-    return v > 127.0f ? 127.0f : v;
-}
+// split_clip (torch.clip that keeps a NaN) and split2_raw (the normalize=False body): eval_dev.h, shared with track_eval.hip
 
 // process.py:10-14 with threshold=1, n_bits=8, sign=True
 __device__ __forceinline__ float split_q(float x) {
@@ -83,11 +79,7 @@ __global__ __launch_bounds__(256) void k_splitter2_raw(const float* __restrict__
     const int64_t n = (int64_t)B * T;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / T, t = i - b * T;
-        const float v = x[i];
-        const float q0 = split_clip(floorf(v / delta)) * delta;
-        const float r = ((2.0f * (v - q0)) * thr) / delta - thr;      // process.py:35 op order
-        out[(b * 2 + 0) * T + t] = q0;
-        out[(b * 2 + 1) * T + t] = split_clip(floorf(r / delta)) * delta;
+        split2_raw(x[i], thr, delta, out[(b * 2 + 0) * T + t], out[(b * 2 + 1) * T + t]);
     }
 }
 

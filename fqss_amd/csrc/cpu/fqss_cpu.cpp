@@ -1532,11 +1532,12 @@ int fqss_sisnr_chunks(const float* est, const float* ref, float* db, int* map, i
     return FQSS_OK;
 }
 
-int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S, int C, int64_t L, int64_t seg, int64_t stride,
-                          int64_t ld_chunk, int64_t ld_out, fqss_stream_t) {
-    REQUIRE(chunks && out, "null pointer");
-    REQUIRE(S > 0 && C > 0 && S * C <= 65535 && chunk_geometry_ok(L, seg, stride) && ld_chunk >= seg && ld_out >= L,
-            "bad shape (1 <= stride <= seg, ld_chunk >= seg, ld_out >= L)");
+// fqss_infer_ola_chunks and, with stats, fqss_infer_ola_chunks_affine: one loop, so that stats == NULL is the former's bits
+static int ola_chunks_run(const char* what, const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L,
+                          int64_t seg, int64_t stride, int64_t ld_chunk, int64_t ld_out) {
+    STOI_REQUIRE(chunks && out, "null pointer");      // (the macro that names the entry point by `what`)
+    STOI_REQUIRE(S > 0 && C > 0 && S * C <= 65535 && chunk_geometry_ok(L, seg, stride) && ld_chunk >= seg && ld_out >= L,
+                 "bad shape (1 <= stride <= seg, ld_chunk >= seg, ld_out >= L)");
     const int64_t N = chunk_count(L, stride);
 #pragma omp parallel for collapse(2) schedule(static)
     for (int64_t d = 0; d < S; ++d)
@@ -1551,8 +1552,96 @@ int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S
                     acc = acc + w * (sign * chunks[((k * S + src) * C + c) * ld_chunk + tt]);
                     wsum += w;
                 }
-                out[(d * C + c) * ld_out + t] = acc / wsum;
+                const float v = acc / wsum;
+                out[(d * C + c) * ld_out + t] = stats ? v * stats[1] + stats[0] : v;      // (-ffp-contract=off: two roundings)
             }
+    return FQSS_OK;
+}
+int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S, int C, int64_t L, int64_t seg, int64_t stride,
+                          int64_t ld_chunk, int64_t ld_out, fqss_stream_t) {
+    return ola_chunks_run("fqss_infer_ola_chunks", chunks, map, nullptr, out, S, C, L, seg, stride, ld_chunk, ld_out);
+}
+int fqss_infer_ola_chunks_affine(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L, int64_t seg,
+                                 int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t) {
+    return ola_chunks_run("fqss_infer_ola_chunks_affine", chunks, map, stats, out, S, C, L, seg, stride, ld_chunk, ld_out);
+}
+
+// ------------------------------------------------------------------------------------------------ track evaluation
+// include/fqss.h, "Track evaluation of the HTDemucs recipe": the statements in straight loops (fp64 sums in index order; the HIP
+// library's tile order differs in the last bits of the fp64 sums, which the statement leaves open).  The workspaces are not used.
+static inline bool track_tiles_ok(int64_t n) { return n > 0 && (n + FQSS_TRACK_TILE - 1) / FQSS_TRACK_TILE <= 0x7fffffff; }
+int64_t fqss_track_stats_ws_doubles(int64_t L) { return track_tiles_ok(L) ? 2 * ((L + FQSS_TRACK_TILE - 1) / FQSS_TRACK_TILE) : 0; }
+int fqss_track_stats(const float* x, double* ws, int64_t ws_doubles, float* stats, int C, int64_t L, int64_t ld, fqss_stream_t) {
+    REQUIRE(x && ws && stats, "null pointer");
+    REQUIRE(C > 0 && C <= 64 && track_tiles_ok(L) && ld >= L, "bad shape (1 <= C <= 64, L >= 1, ld >= L)");
+    REQUIRE(ws_doubles >= fqss_track_stats_ws_doubles(L), "workspace shorter than fqss_track_stats_ws_doubles");
+    auto m_t = [&](int64_t t) {
+        float m = x[t];
+        for (int c = 1; c < C; ++c) m += x[c * ld + t];
+        return (double)(m / (float)C);
+    };
+    double sum = 0.0, sq = 0.0;
+    for (int64_t t = 0; t < L; ++t) sum += m_t(t);
+    const double mean = sum / (double)L;
+    for (int64_t t = 0; t < L; ++t) sq += (m_t(t) - mean) * (m_t(t) - mean);
+    stats[0] = (float)mean;
+    stats[1] = (float)sqrt(sq / (double)(L - 1));
+    return FQSS_OK;
+}
+
+int fqss_chunk_gather_mc(const float* mix, const float* stats, float* out, int C, int64_t L, int64_t ld, int64_t seg, int64_t stride,
+                         int64_t k0, int G, fqss_stream_t) {
+    REQUIRE(mix && out, "null pointer");
+    REQUIRE(chunk_geometry_ok(L, seg, stride) && C > 0 && G > 0 && (int64_t)G * C <= 65535 && ld >= L && k0 >= 0 && k0 < chunk_count(L, stride),
+            "bad shape (1 <= stride <= seg, 0 <= k0 < ceil(L / stride), 1 <= G * C <= 65535, ld >= L)");
+    const int64_t N = chunk_count(L, stride);
+    for (int64_t g = 0; g < G; ++g)
+        for (int64_t c = 0; c < C; ++c) {
+            const int64_t k = k0 + g < N ? k0 + g : N - 1, n = L - k * stride;
+            const float* src = mix + c * ld + k * stride;
+            float* dst = out + (g * C + c) * seg;
+            for (int64_t t = 0; t < seg; ++t) dst[t] = t >= n ? 0.0f : (stats ? (src[t] - stats[0]) / stats[1] : src[t]);
+        }
+    return FQSS_OK;
+}
+
+int fqss_splitter2_raw_rows(const float* x, float* out, int B, int64_t N, uint32_t* row_max, fqss_stream_t) {
+    REQUIRE(x && out && row_max, "null pointer");
+    REQUIRE(B > 0 && N > 0, "bad shape");
+    for (int64_t b = 0; b < B; ++b) {
+        float thr;
+        memcpy(&thr, &row_max[b], 4);
+        for (int64_t t = 0; t < N; ++t) thr = fmaxf(thr, fabsf(x[b * N + t]));
+        memcpy(&row_max[b], &thr, 4);
+        const float delta = thr / 128.0f;      // process.py:26-36 with normalize=False: x is not divided by thr
+        for (int64_t t = 0; t < N; ++t) {
+            const float v = x[b * N + t];
+            const float q0 = split_clip(floorf(v / delta)) * delta;
+            const float r = ((2.0f * (v - q0)) * thr) / delta - thr;
+            out[(b * 2 + 0) * N + t] = q0;
+            out[(b * 2 + 1) * N + t] = split_clip(floorf(r / delta)) * delta;
+        }
+    }
+    return FQSS_OK;
+}
+
+int64_t fqss_nsdr_ws_doubles(int P, int64_t N) {
+    return P > 0 && P <= 65535 && track_tiles_ok(N) ? 2 * (int64_t)P * ((N + FQSS_TRACK_TILE - 1) / FQSS_TRACK_TILE) : 0;
+}
+int fqss_nsdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t N, int64_t ld_e, int64_t ld_r,
+              fqss_stream_t) {
+    REQUIRE(est && ref && ws && db, "null pointer");
+    REQUIRE(P > 0 && P <= 65535 && track_tiles_ok(N) && ld_e >= N && ld_r >= N, "bad shape (1 <= P <= 65535, N >= 1, ld_e, ld_r >= N)");
+    REQUIRE(ws_doubles >= fqss_nsdr_ws_doubles(P, N), "workspace shorter than fqss_nsdr_ws_doubles");
+    for (int64_t p = 0; p < P; ++p) {
+        double num = 0.0, den = 0.0;
+        for (int64_t i = 0; i < N; ++i) {
+            const double r = ref[p * ld_r + i], d = r - (double)est[p * ld_e + i];
+            num += r * r;
+            den += d * d;
+        }
+        db[p] = 10.0 * log10((num + 1e-7) / (den + 1e-7));
+    }
     return FQSS_OK;
 }
 

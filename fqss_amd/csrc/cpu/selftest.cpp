@@ -194,6 +194,35 @@ int main() {
         CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, oc.data(), Sc, 1, Lc, seg, 0, seg, Lc, nullptr) == FQSS_EINVAL);
         CHECK(fqss_splitter2_rows(rows.data(), sp2.data(), G, seg, nullptr, nullptr) == FQSS_EINVAL);
     }
+    // track evaluation: stats of a pitched stereo track, a normalised gather that runs past the short last chunk, the per-item raw
+    // splitter, the de-normalising overlap-add (which undoes the gather's normalisation), the nSDR of a track against itself
+    {
+        const int64_t Lt = 310, ldt = 313, seg = 100, hop = 75, Nt = 5;
+        const int Ct = 2, G = 3;
+        auto x = rnd((size_t)Ct * ldt);
+        std::vector<double> ws((size_t)fqss_track_stats_ws_doubles(Lt) + (size_t)fqss_nsdr_ws_doubles(Ct, Lt)), db(Ct, 1.0);
+        std::vector<float> st(2), ck((size_t)(Nt + 1) * Ct * seg), sp((size_t)G * 2 * Ct * seg), back((size_t)Ct * Lt);
+        std::vector<uint32_t> rmax(G, 0u);
+        CHECK(fqss_track_stats(x.data(), ws.data(), (int64_t)ws.size(), st.data(), Ct, Lt, ldt, nullptr) == 0);
+        CHECK(st[1] > 0.0f && fabsf(st[0]) < st[1]);
+        for (int64_t k0 = 0; k0 < Nt; k0 += G)
+            CHECK(fqss_chunk_gather_mc(x.data(), st.data(), ck.data() + k0 * Ct * seg, Ct, Lt, ldt, seg, hop, k0, G, nullptr) == 0);
+        for (int64_t t = 10; t < seg; ++t) CHECK(ck[(4 * Ct + 1) * seg + t] == 0.0f && ck[(5 * Ct + 1) * seg + t] == 0.0f);
+        CHECK(fqss_splitter2_raw_rows(ck.data(), sp.data(), G, Ct * seg, rmax.data(), nullptr) == 0);
+        // chunks [N][S = 1][C][seg]: the overlap-add of the normalised chunks, de-normalised, is the track again
+        CHECK(fqss_infer_ola_chunks_affine(ck.data(), nullptr, st.data(), back.data(), 1, Ct, Lt, seg, hop, seg, Lt, nullptr) == 0);
+        for (int c = 0; c < Ct; ++c)
+            for (int64_t t = 0; t < Lt; ++t) CHECK(fabsf(back[c * Lt + t] - x[c * ldt + t]) <= 1e-5f);
+        CHECK(fqss_nsdr(back.data(), x.data(), ws.data(), (int64_t)ws.size(), db.data(), Ct, Lt, Lt, ldt, nullptr) == 0);
+        CHECK(db[0] > 80.0 && db[1] > 80.0);
+        CHECK(fqss_track_stats(x.data(), ws.data(), 0, st.data(), Ct, Lt, ldt, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_track_stats(x.data(), ws.data(), (int64_t)ws.size(), st.data(), Ct, Lt, Lt - 1, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_chunk_gather_mc(x.data(), nullptr, ck.data(), Ct, Lt, ldt, seg, hop, Nt, G, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_splitter2_raw_rows(ck.data(), sp.data(), G, Ct * seg, nullptr, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_infer_ola_chunks_affine(ck.data(), nullptr, st.data(), back.data(), 1, Ct, Lt, seg, seg + 1, seg, Lt, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_nsdr(back.data(), x.data(), ws.data(), 1, db.data(), Ct, Lt, Lt, ldt, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_track_stats_ws_doubles(0) == 0 && fqss_nsdr_ws_doubles(0, Lt) == 0);
+    }
     CHECK(fqss_version() == FQSS_VERSION);
     printf("selftest ok\n");
     return 0;

@@ -3,7 +3,7 @@
 // (torchmetrics' ScaleInvariantSignalNoiseRatio, third party: restated from its published form, zero-mean SI-SDR with eps = 2^-23).
 // All of it stays on the device: five fp64 moments per (estimate, target) pair, a one-wave finish that also takes the re-ordering
 // decision of `swap_channel_order` (so no host round trip per chunk), and one stream for the weighted overlap-add.
-#include "fqss_dev.h"
+#include "eval_dev.h"
 
 namespace fqss {
 
@@ -49,17 +49,7 @@ __global__ void k_sisnr_finish(const double* __restrict__ mom, float* __restrict
     }
 }
 
-// triangular chunk weight of model_infer (process.py:166-168): 1..h, (seg-h)..1 over max, h = seg / 2
-__device__ __forceinline__ float tri_weight(int64_t t, int64_t seg) {
-    const int64_t h = seg / 2;
-    const float mx = (float)(seg - h);
-    return (t < h ? (float)(t + 1) : (float)(seg - t)) / mx;
-}
-
-// one step of the weighted overlap-add, acc + w * (sign * v): k_infer_ola and k_infer_ola_chunks both accumulate through this one
-// expression, so the two round alike (two multiplications and one addition, no fused multiply-add: the library is built with
-// -ffp-contract=off)
-__device__ __forceinline__ float ola_step(float acc, float w, float sign, float v) { return acc + w * (sign * v); }
+// tri_weight, ola_step and the gather form's per-sample walk (ola_chunks_sample): eval_dev.h, shared with track_eval.hip
 
 // out[d][c][start + t] += w[t] * sign_d * chunk[src_d][c][t];  sum_weight[start + t] += w[t]   (t < n)
 __global__ __launch_bounds__(256) void k_infer_ola(const float* __restrict__ chunk, const int* __restrict__ map, float* __restrict__ out,
@@ -149,22 +139,8 @@ __global__ __launch_bounds__(256) void k_infer_ola_chunks(const float* __restric
                                                            int S, int C, int64_t L, int64_t seg, int64_t stride, int64_t N, int64_t ld_chunk,
                                                            int64_t ld_out) {
     const int dc = blockIdx.y, d = dc / C, c = dc % C;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < L; t += (int64_t)gridDim.x * 256) {
-        const int64_t k_lo = t < seg ? 0 : (t - seg) / stride + 1;      // first k with t - k * stride < seg
-        int64_t k_hi = t / stride;                                       // last k with k * stride <= t
-        if (k_hi > N - 1) k_hi = N - 1;
-        float acc = 0.0f, wsum = 0.0f;
-        for (int64_t k = k_lo; k <= k_hi; ++k) {
-            const int* mp = map != nullptr ? map + (k * S + d) * 2 : nullptr;
-            const int src = mp != nullptr ? mp[0] : d;
-            const float sign = mp != nullptr ? (float)mp[1] : 1.0f;
-            const int64_t tt = t - k * stride;
-            const float w = tri_weight(tt, seg);
-            acc = ola_step(acc, w, sign, chunks[((k * S + src) * C + c) * ld_chunk + tt]);
-            wsum += w;
-        }
-        out[((int64_t)d * C + c) * ld_out + t] = acc / wsum;
-    }
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < L; t += (int64_t)gridDim.x * 256)
+        out[((int64_t)d * C + c) * ld_out + t] = ola_chunks_sample(chunks, map, S, C, d, c, t, seg, stride, N, ld_chunk);
 }
 
 }  // namespace fqss

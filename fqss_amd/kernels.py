@@ -1226,6 +1226,18 @@ def splitter2_rows(x):
     return out
 
 
+def splitter2_raw_rows(x):
+    """x [B, ...] -> [B, 2, prod(...)]: the normalize=False splitter with one threshold per item, thr_b = max|x[b]|; row b is
+    splitter2(x[b:b+1], normalize=False), bit for bit"""
+    _need_gpu(x)
+    x2 = x.reshape(x.shape[0], -1).contiguous()
+    B, T = x2.shape
+    ws = torch.zeros(B, device=x.device, dtype=torch.int32)
+    out = torch.empty(B, 2, T, device=x.device, dtype=torch.float32)
+    _lib.call("fqss_splitter2_raw_rows", _p(x2), _p(out), B, T, _p(ws), _stream())
+    return out
+
+
 def frames_conv_fwd(x, w, stride, add=None):
     """x [N,Ci,T] dense, w [Co,Ci,K] -> z [N,Co,M] (+ add [N,Co,M])"""
     _need_gpu(x, w)
@@ -3019,18 +3031,66 @@ def sisnr_chunks(est, ref, stride, k0, db=None, mp=None):
     return db, mp
 
 
-def infer_ola_chunks(chunks, mp, length, stride):
+def infer_ola_chunks(chunks, mp, length, stride, stats=None):
     """chunks [N.., S, (C,) seg] (at least ceil(length / stride) chunks), mp [N.., S, 2] int32 or None -> [S, (C,) length]: the
-    triangular overlap-add of infer_ola over every chunk in order and infer_normalize, bit for bit, in one launch"""
-    _need_gpu(chunks)
+    triangular overlap-add of infer_ola over every chunk in order and infer_normalize, bit for bit, in one launch.  stats (track_stats'
+    (mean, std) on the device): every sample leaves as v * std + mean (fqss_infer_ola_chunks_affine)"""
+    _need_gpu(chunks, stats)
     S, seg = chunks.shape[1], chunks.shape[-1]
     C = chunks.shape[2] if chunks.dim() == 4 else 1
     n_chunks = -(-length // stride) if stride > 0 else 0
     assert chunks.is_contiguous() and chunks.shape[0] >= n_chunks, "infer_ola_chunks: dense chunks, one per hop"
     assert mp is None or (mp.is_contiguous() and mp.dtype == torch.int32 and mp.shape[0] >= n_chunks and tuple(mp.shape[1:]) == (S, 2))
     out = torch.empty((S, C, length) if chunks.dim() == 4 else (S, length), device=chunks.device, dtype=torch.float32)
-    _lib.call("fqss_infer_ola_chunks", _p(chunks), _p(mp), _p(out), S, C, length, seg, stride, seg, length, _stream())
+    if stats is None:
+        _lib.call("fqss_infer_ola_chunks", _p(chunks), _p(mp), _p(out), S, C, length, seg, stride, seg, length, _stream())
+    else:
+        assert stats.numel() == 2 and stats.is_contiguous(), "infer_ola_chunks: stats is (mean, std)"
+        _lib.call("fqss_infer_ola_chunks_affine", _p(chunks), _p(mp), _p(stats), _p(out), S, C, length, seg, stride, seg, length, _stream())
     return out
+
+
+# ------------------------------------------------------------------ track evaluation (csrc/track_eval.hip)
+TRACK_TILE, = _h("TRACK_TILE")           # samples of one fp64 tile partial of track_stats / nsdr
+
+
+def track_stats(x):
+    """x [C, L] (rows may be pitched) -> (mean, std) fp32 [2] on the device of the channel mean x.mean(0): formed in fp64, rounded once;
+    std is the unbiased one (torch's default), NaN at L = 1 (fqss_track_stats in include/fqss.h)"""
+    _need_gpu(x)
+    assert x.dim() == 2, "track_stats: [channels, length]"
+    x, C, L, ld = as_rowmat(x)
+    n_ws = _lib.query("fqss_track_stats_ws_doubles", L)
+    ws = torch.empty(max(n_ws, 1), device=x.device, dtype=torch.float64)
+    stats = torch.empty(2, device=x.device, dtype=torch.float32)
+    _lib.call("fqss_track_stats", _p(x), _p(ws), n_ws, _p(stats), C, L, ld, _stream())
+    return stats
+
+
+def chunk_gather_mc(mix, seg, stride, k0, G, stats=None):
+    """mix [C, L] (rows may be pitched) -> [G, C, seg]: row g = mix[:, (k0 + g) * stride : ... + seg], rows past the last chunk repeat it;
+    stats: in-range samples leave as (v - mean) / std; samples past L are 0 either way"""
+    _need_gpu(mix, stats)
+    assert mix.dim() == 2, "chunk_gather_mc: [channels, length]"
+    assert stats is None or (stats.numel() == 2 and stats.is_contiguous()), "chunk_gather_mc: stats is (mean, std)"
+    mix, C, L, ld = as_rowmat(mix)
+    out = torch.empty(G, C, seg, device=mix.device, dtype=torch.float32)
+    _lib.call("fqss_chunk_gather_mc", _p(mix), _p(stats), _p(out), C, L, ld, seg, stride, k0, G, _stream())
+    return out
+
+
+def nsdr(est, ref):
+    """est, ref [P, N] (rows may be pitched) -> 10 log10((sum ref^2 + 1e-7) / (sum (ref - est)^2 + 1e-7)) of each row, fp64 [P] on the
+    device (the reference's calc_nsdr; fqss_nsdr in include/fqss.h)"""
+    _need_gpu(est, ref)
+    est, P, N, ld_e = as_rowmat(est)
+    ref, P2, N2, ld_r = as_rowmat(ref)
+    assert (P, N) == (P2, N2), "nsdr: shape mismatch"
+    n_ws = _lib.query("fqss_nsdr_ws_doubles", P, N)
+    ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
+    db = torch.empty(P, device=est.device, dtype=torch.float64)
+    _lib.call("fqss_nsdr", _p(est), _p(ref), _p(ws), n_ws, _p(db), P, N, ld_e, ld_r, _stream())
+    return db
 
 
 # ------------------------------------------------------------------ affine form of the quantizers (csrc/export_q.hip)

@@ -246,13 +246,15 @@ class fast_codes:
         FAST = self.prev
 
 
-SPLIT_PER_ITEM = False  # True (`split_per_item(True)`): the 8-bit splitter normalises every batch item by its own maximum
+SPLIT_PER_ITEM = False  # True / "items" (`split_per_item(..)`): the 8-bit splitter normalises every batch item by its own maximum
 
 
 class split_per_item:
     """split_per_item(True): `process.preprocess(n_splitter=2)` takes one threshold per batch item (fqss_splitter2_rows) instead of one
     for the whole tensor -- what the reference computes when it calls the model on one chunk at a time; `process.model_infer(chunk_batch=G)`
-    turns it on around its batched forward"""
+    turns it on around its batched forward.  True serves [B, 1, T] waveforms and refuses every other input, as it always did.
+    split_per_item("items") serves every input: a multi-channel or multi-dimensional item [A, ...] is one row of A * ... samples
+    (normalize=False: fqss_splitter2_raw_rows) -- what the batched forward of a multi-channel mixture (HTDemucs) runs under."""
 
     def __init__(self, on=True):
         self.on = on
@@ -1190,6 +1192,11 @@ def splitter2(x):
 def splitter2_rows(x):
     with torch.no_grad():
         return K.splitter2_rows(x)
+
+
+def splitter2_raw_rows(x):
+    with torch.no_grad():
+        return K.splitter2_raw_rows(x)
 
 
 class _ForkState:

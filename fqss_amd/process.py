@@ -3,7 +3,8 @@
 `preprocess` = global max-normalise + MSB/LSB floor-quantised channels (HIP: fqss_minmax + fqss_splitter2),
 `postprocess` = `x0 + x1 * 2^-8` (HIP: fqss_axpby).  The evaluation helpers of the reference's process.py run on the device too:
 chunked overlap-add inference with per-chunk source re-ordering, SI-SNR (fqss_sisnr_matrix), SDR (fqss_sdr) and STOI (fqss_stoi) of
-`metric_evaluation`.  STOI is opt-in (`with_stoi=True`; pystoi is third party and absent: restated, NaN by default).
+`metric_evaluation`, and the nSDR of `calc_nsdr` (fqss_nsdr).  STOI is opt-in (`with_stoi=True`; pystoi is third party and absent:
+restated, NaN by default).
 """
 import torch
 
@@ -26,13 +27,16 @@ def preprocess(x, n_splitter=1, n_bits=8, sign=True, normalize=True):
         raise NotImplementedError("the splitter kernel serves n_splitter=2, 8 bit, signed")
     if normalize and x.shape[1] == 1 and x.dim() == 3:
         return ops.splitter2_rows(x) if ops.SPLIT_PER_ITEM else ops.splitter2(x)
-    if ops.SPLIT_PER_ITEM:
-        raise NotImplementedError("ops.split_per_item serves [B, 1, T] waveforms (fqss_splitter2_rows); the multi-channel / "
-                                  "normalize=False splitter of HTDemucs has one threshold for the whole tensor")
+    if ops.SPLIT_PER_ITEM is True:
+        raise NotImplementedError("ops.split_per_item(True) serves [B, 1, T] waveforms (fqss_splitter2_rows); the multi-channel / "
+                                  "normalize=False splitter of HTDemucs takes one threshold per item under ops.split_per_item(\"items\")")
     # multi-channel / multi-dimensional inputs (HTDemucs: [B, A, Fr, T] spectrogram, [B, A, T] waveform): the flattened
     # [B, 2, A*...] result is torch.cat([msb, lsb], dim=1)
-    with torch.no_grad():
-        y = K.splitter2(x, normalize=normalize)
+    if ops.SPLIT_PER_ITEM:      # "items": one threshold per item, the item is one row of A * ... samples
+        y = ops.splitter2_rows(x) if normalize else ops.splitter2_raw_rows(x)
+    else:
+        with torch.no_grad():
+            y = K.splitter2(x, normalize=normalize)
     return y.view(x.shape[0], 2 * x.shape[1], *x.shape[2:])
 
 
@@ -72,53 +76,63 @@ def swap_channel_order(sep_tensor, clean_tensor):
     return out.reshape(sep_tensor.shape)
 
 
-def _model_infer_batched(model, mix, num_srcs, segment, overlap, target, chunk_batch):
+def _model_infer_batched(model, mix, num_srcs, segment, overlap, target, chunk_batch, stats=None):
     """the chunks of one utterance through the model `chunk_batch` at a time: what the chunk-by-chunk loop of `model_infer` computes
     (per-chunk splitter threshold, per-chunk re-ordering, the same overlap-add in the same order) in ceil(N / G) forwards instead of N;
-    nothing is read back to the host"""
+    nothing is read back to the host.  Multi-channel mixtures (no target; the model declares `audio_channels`) go through
+    fqss_chunk_gather_mc and the forward runs under ops.split_per_item("items"); `stats` ((mean, std) on the device,
+    kernels.track_stats) normalises the chunks in the gather and de-normalises the result in the overlap-add's store."""
     G = int(chunk_batch)
     if G < 1:
         raise ValueError(f"chunk_batch must be a positive number of chunks, got {chunk_batch!r}")
     channels, length = mix.shape
-    if channels > 1:
-        raise NotImplementedError("chunk_batch serves one-channel mixtures (the waveform models); multi-channel chunked inference "
-                                  "runs chunk by chunk (chunk_batch=None)")
+    if channels > 1 and (target is not None or getattr(model, "audio_channels", 1) != channels):
+        raise NotImplementedError("chunk_batch serves one-channel mixtures (the waveform models) and, without a target to re-order "
+                                  f"against, models that declare audio_channels = {channels} (HTDemucs); any other multi-channel "
+                                  "chunked inference runs chunk by chunk (chunk_batch=None)")
     segment = int(segment)
     stride = int((1 - overlap) * segment)
     if not 1 <= stride <= segment:
         raise ValueError(f"chunk_batch needs 1 <= int((1 - overlap) * segment) <= segment, got a hop of {stride}")
-    mix = mix.contiguous()
+    multi = channels > 1 or stats is not None
+    if not multi:
+        mix = mix.contiguous()
     n_chunks = len(range(0, length, stride))
     n_pad = -(-n_chunks // G) * G
     want_map = target is not None and num_srcs > 1
     maps = torch.empty(n_pad, num_srcs, 2, device=mix.device, dtype=torch.int32) if want_map else None
     db = torch.empty(G, num_srcs, num_srcs, device=mix.device, dtype=torch.float32) if want_map else None
+    shape = (num_srcs, channels) if channels > 1 else (num_srcs,)
     buf = None
     for k0 in range(0, n_chunks, G):
-        chunks = K.chunk_gather(mix, segment, stride, k0, G)
-        with torch.no_grad(), ops.split_per_item(True):
+        chunks = K.chunk_gather_mc(mix, segment, stride, k0, G, stats=stats) if multi else K.chunk_gather(mix, segment, stride, k0, G)
+        with torch.no_grad(), ops.split_per_item("items" if channels > 1 else True):
             y = model(chunks).detach()
-        y = y.reshape(G, num_srcs, y.shape[-1])
+        y = y.reshape(G, *shape, y.shape[-1])
         n = min(y.shape[-1], segment)
         if buf is None:     # a model that returns fewer than `segment` samples is zero-padded, as the whole-utterance call pads it
-            buf = (torch.zeros if n < segment else torch.empty)(n_pad, num_srcs, segment, device=mix.device, dtype=torch.float32)
-        buf[k0:k0 + G, :, :n].copy_(y[..., :n])
+            buf = (torch.zeros if n < segment else torch.empty)(n_pad, *shape, segment, device=mix.device, dtype=torch.float32)
+        buf[k0:k0 + G, ..., :n].copy_(y[..., :n])
         if want_map:
             K.sisnr_chunks(buf[k0:k0 + G], target.reshape(num_srcs, -1), stride, k0, db=db, mp=maps[k0:k0 + G])
-    return K.infer_ola_chunks(buf, maps, length, stride)
+    return K.infer_ola_chunks(buf, maps, length, stride, stats=stats)
 
 
-def model_infer(model, mix, n_srcs=1, segment=None, overlap=0.25, device="cuda", target=None, chunk_batch=None):
+def model_infer(model, mix, n_srcs=1, segment=None, overlap=0.25, device="cuda", target=None, chunk_batch=None, stats=None):
     """process.model_infer (process.py:156-194): whole-utterance inference, or chunks of `segment` samples hopped by
     (1 - overlap) * segment, re-ordered per chunk against `target` and blended with the triangular window.  mix [channels, length];
     returns [n_srcs, (channels,) length] on the device (the reference returns a CPU tensor).  chunk_batch=G (opt-in) sends the chunks
-    through the model G at a time (`_model_infer_batched`); None runs them one by one."""
+    through the model G at a time (`_model_infer_batched`); None runs them one by one.  stats (with chunk_batch only): the track's
+    (mean, std) on the device -- the model sees (mix - mean) / std and the result is de-normalised (val.py:109-120 of the reference)."""
     if str(device) == "cpu" and _lib.BACKEND != "cpu":
         raise RuntimeError("fqss_amd runs on ROCm devices only (oracle/ is the CPU checker)")
+    if stats is not None and not (segment and chunk_batch is not None):
+        raise ValueError("model_infer: stats is served by the batched chunk path (segment and chunk_batch)")
     mix = mix.to(device)
     if segment and chunk_batch is not None:
         num_srcs = model.n_srcs if hasattr(model, "n_srcs") else n_srcs
-        return _model_infer_batched(model, mix, num_srcs, segment, overlap, None if target is None else target.to(device), chunk_batch)
+        return _model_infer_batched(model, mix, num_srcs, segment, overlap, None if target is None else target.to(device), chunk_batch,
+                                    stats=stats)
     if not segment:
         with torch.no_grad():
             out = model(mix.unsqueeze(0)).detach()[0]
@@ -146,6 +160,13 @@ def model_infer(model, mix, n_srcs=1, segment=None, overlap=0.25, device="cuda",
         K.infer_ola(chunk_out, mp, out, sum_weight, start, n, segment)
     K.infer_normalize(out, sum_weight)
     return out
+
+
+def calc_nsdr(ref, sig):
+    """the reference's calc_nsdr (process.py:70-75; demucs' new_sdr): 10 log10((sum ref^2 + 1e-7) / (sum (ref - sig)^2 + 1e-7)) over the
+    last two dimensions of [..., C, L].  Leading dimensions are flattened to rows; returns fp64 [...] on the device (fqss_nsdr)."""
+    lead = ref.shape[:-2]
+    return K.nsdr(sig.reshape(-1, sig.shape[-2] * sig.shape[-1]), ref.reshape(-1, ref.shape[-2] * ref.shape[-1])).reshape(lead)
 
 
 def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):

@@ -5,8 +5,10 @@ restated).  `dataset_cfg.name: librimix` walks `testing_cfg.test_dir` as val.py:
 s1..s3; whole utterances, resampled on the device); `synthetic` evaluates seeded two-speaker mixtures.  STOI (pystoi: third party,
 absent) is printed as nan unless `testing_cfg.stoi: true` asks for fqss_stoi, the restated definition, at the utterance's rate;
 `testing_cfg.stoi_extended: true` beside it puts the extended measure (ESTOI, fqss_stoi_x) into the same slot.
-MUSDB needs the `musdb` package (absent): refused.  `val()` returns (SI-SDR, improvement); the SDR and the STOI of the run are in
-the printed result line."""
+`dataset_cfg.name: musdbhq` with `testing_cfg.NSDR: true` is the reference's `val_musdbhq_NSDR` (val.py:95-131) over folders of WAV
+stems (`val_musdbhq_nsdr` below: the `musdb` package is not needed for it); without NSDR the branch needs `museval` (absent): refused.
+`val()` returns (SI-SDR, improvement), or the nSDR tuple of the musdbhq branch; the SDR and the STOI of the run are in the printed
+result line."""
 import argparse
 import glob
 import os
@@ -105,6 +107,64 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
     return sisdr / n, sisdr_imp / n, sdr / n, stoi / n
 
 
+def _read_stereo_wav(path, rate, channels, device):
+    """[channels, L] fp32 on the device, int16 / 32768 (exact): what musdb's `track.audio` holds, transposed"""
+    import numpy as np
+    from .train_env.htdemucs_musdbhq.wav_dataset import _open_checked
+    w = _open_checked(path, rate, channels)
+    try:
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, channels)
+    finally:
+        w.close()
+    return torch.from_numpy(pcm.copy()).to(device).t().contiguous().float().div_(32768.0)
+
+
+def val_musdbhq_nsdr(model, testing_cfg, device):
+    """val_musdbhq_NSDR of the reference (val.py:95-131) on the device: per track, normalise the mixture by the mean / std of its
+    channel mean (fqss_track_stats), separate it chunk by chunk, de-normalise, and score every source with calc_nsdr (fqss_nsdr: one
+    launch sequence and one read-back per track).  Tracks are the sub-folders of `<test_dir>/test` when that folder exists, else of
+    `<test_dir>`; each holds mixture.wav and <source>.wav for every model.sources, 16-bit PCM at `testing_cfg.samplerate` (44100) with
+    the model's channel count.  `testing_cfg.chunk_batch: G` sends G chunks per forward with the normalisation inside the gather and
+    the overlap-add (process.model_infer(chunk_batch=G, stats=...)); absent, the chunks go one by one and both are tensor operations.
+    Prints the reference's progress lines; returns (mean over sources, per-source means..).
+    Differences from the reference: it asserts exactly 50 tracks (the MUSDB18-HQ test set) -- here an empty folder raises and any
+    other count is printed; the files are read by the `wave` module, not by `musdb` (parity with that reader is not pinned); mean and
+    std are fp64 sums rounded once, not torch's fp32 reductions."""
+    import numpy as np
+    from .process import calc_nsdr
+    from .train_env.htdemucs_musdbhq.wav_dataset import MIXTURE, _list_tracks
+    root = testing_cfg["test_dir"]
+    if os.path.isdir(os.path.join(root, "test")):
+        root = os.path.join(root, "test")
+    tracks = _list_tracks(root)
+    if not tracks:
+        raise FileNotFoundError(f"{root}: no track folders (each holds {MIXTURE}.wav and one WAV per source)")
+    print("{} tracks under {}".format(len(tracks), root))
+    sources = list(model.sources)
+    rate, channels = int(testing_cfg.get("samplerate", 44100)), int(getattr(model, "audio_channels", 2))
+    segment, overlap, G = testing_cfg.get("segment_samples", None), testing_cfg.get("overlap", 0.25), testing_cfg.get("chunk_batch")
+    sdrs = np.zeros((len(sources), len(tracks)))
+    for j, name in enumerate(tracks):
+        read = lambda stem: _read_stereo_wav(os.path.join(root, name, stem + ".wav"), rate, channels, device)
+        mix = read(MIXTURE)
+        stats = K.track_stats(mix)
+        if segment and G is not None:
+            separations = model_infer(model, mix, segment=segment, overlap=overlap, device=device, chunk_batch=G, stats=stats)
+        else:
+            separations = model_infer(model, (mix - stats[0]) / stats[1], segment=segment, overlap=overlap, device=device)
+            separations = separations * stats[1] + stats[0]
+        refs = torch.stack([read(src) for src in sources])
+        if refs.shape != separations.shape:
+            raise ValueError(f"{os.path.join(root, name)}: stems {tuple(refs.shape)}, separations {tuple(separations.shape)}")
+        sdrs[:, j] = calc_nsdr(refs, separations).tolist()          # the track's one read-back
+        if j % 10 == 0:
+            print("\n****** Track {}/{} ******".format(j + 1, len(tracks)))
+            for i, src in enumerate(sources):
+                print("{}: SDR={:0.3f}".format(src, sdrs[i, j]))
+    sdrs = np.mean(sdrs, axis=1)
+    return (float(np.mean(sdrs)),) + tuple(float(v) for v in sdrs)
+
+
 def val(argv=None):
     import sys
     if argv is not None:
@@ -125,7 +185,14 @@ def val(argv=None):
     elif dataset_cfg["name"] == "synthetic":
         sisnr, imp, sdr, stoi = val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "musdbhq":
-        raise NotImplementedError("dataset musdbhq: val.py:95-178 reads MUSDB18-HQ through the third-party `musdb` package (absent here)")
+        if not testing_cfg.get("NSDR", False):
+            raise NotImplementedError("dataset musdbhq: val.py:134-178 scores with the third-party `museval` package (absent here); "
+                                      "testing_cfg.NSDR: true is served (val_musdbhq_nsdr)")
+        res = val_musdbhq_nsdr(model, testing_cfg, "cuda")
+        # the reference's line, its SNDR_VOCALS spelling included (val.py:221)
+        print(",".join(["NSDR={:0.2f}".format(res[0])] + ["{}_{}={:0.2f}".format("SNDR" if s == "vocals" else "NSDR", s.upper(), v)
+                                                         for s, v in zip(model.sources, res[1:])]))
+        return res
     else:
         assert False, "Dataset {} is not supported!".format(dataset_cfg["name"])
     print("SI-SDR={:0.2f},SI-SDR-imp={:0.2f},SDR={:0.2f},STOI={:0.3f}".format(sisnr, imp, sdr, stoi))

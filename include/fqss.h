@@ -1546,6 +1546,48 @@ int fqss_gln_fq_fwd(const FqssTensor* x, const FqssQParams* qx, const float* gam
                     int nslots, fqss_stream_t stream);
 int fqss_tgemm_desc(const FqssTGemmDesc* d, fqss_stream_t stream);
 
+/* Track evaluation of the HTDemucs recipe (csrc/track_eval.hip; val.py:95-131 of the reference, `val_musdbhq_NSDR`, and calc_nsdr of
+ * its process.py:70-75): normalise a multi-channel track by the mean / std of its channel mean, cut it into batches of chunks, run
+ * the per-item normalize=False splitter on a batch, overlap-add and de-normalise the estimates, and score them -- all on the device.
+ * fp32 in; every sum is formed in fp64 in a fixed order; no floating-point atomics: every result is the same bits from run to run.
+ * "fp32 division" below is the IEEE-754 correctly rounded quotient.  A refused call returns FQSS_EINVAL and writes nothing.
+ * FQSS_TRACK_TILE: samples of one tile partial of fqss_track_stats and fqss_nsdr.
+ *
+ * fqss_track_stats  x [C][L] (row stride ld >= L) -> stats[2] = (mean, std), fp32 on the device (val.py:109-112: ref = mix.mean(0);
+ *   ref.mean(); ref.std()).  m_t = (x[0][t] + x[1][t] + ... in channel order, fp32) / C (fp32 division); mean = (sum_t (double) m_t) / L;
+ *   std = sqrt(sum_t ((double) m_t - mean)^2 / (L - 1)) (torch's unbiased default; two passes, the second takes the unrounded fp64
+ *   mean).  Both are formed in fp64 and rounded to fp32 once, at the end; L = 1 gives std NaN, as torch does.  Each sum: one fp64
+ *   partial per tile of FQSS_TRACK_TILE samples into ws, then one workgroup adds the partials in tile order.  Stated as fp64-then-round:
+ *   NOT bit parity with torch's fp32 mean / std, whose summation order is not specified (it agrees to fp32 rounding noise).
+ *   ws: at least fqss_track_stats_ws_doubles(L) = 2 * ceil(L / FQSS_TRACK_TILE) doubles (0 for an L that is refused), uninitialised.
+ * fqss_chunk_gather_mc  mix [C][L] (row stride ld) -> out [G][C][seg]: out[g][c][t] = mix[c][(k0 + g) * stride + t] with the chunk
+ *   geometry of fqss_chunk_gather (rows past chunk N - 1 repeat chunk N - 1).  stats (optional, fqss_track_stats' pair): an in-range
+ *   sample v is written as (v - mean) / std, one fp32 subtraction and one fp32 division.  Samples past L are written as 0 with or
+ *   without stats (the reference normalises the track and zero-pads the chunk afterwards).  stats == NULL, C = 1: fqss_chunk_gather's
+ *   bits.  16-byte requests when seg, stride, ld are multiples of 4 and mix, out are 16-byte aligned; one sample per request otherwise.
+ * fqss_splitter2_raw_rows  fqss_splitter2_raw with one threshold per item: x [B][N] -> out [B][2][N], thr_b = max|x[b][:]|; row_max:
+ *   B words zeroed by the caller, left holding the bit images of thr_b.  Row b is, bit for bit, fqss_splitter2_raw of item b alone;
+ *   an all-zero item is NaN in its own row only.  (The normalised per-item form of a multi-channel item is fqss_splitter2_rows on
+ *   the flattened item.)
+ * fqss_infer_ola_chunks_affine  fqss_infer_ola_chunks, each sample v then stored as v * std + mean (an fp32 multiplication and an
+ *   fp32 addition, not fused; val.py:120) with (mean, std) read from stats on the device.  stats == NULL: fqss_infer_ola_chunks' bits.
+ * fqss_nsdr  P rows est[p][:N], ref[p][:N] (row strides ld_e, ld_r >= N) -> db[p] = 10 log10((num + 1e-7) / (den + 1e-7)) in fp64,
+ *   num = sum ref^2, den = sum (ref - est)^2, the difference and both squares in fp64 (calc_nsdr; demucs' new_sdr when a row is one
+ *   (batch, source) item of C * L contiguous samples).  One (num, den) partial per tile of FQSS_TRACK_TILE samples and row into ws, added
+ *   in tile order by one workgroup per row.  ws: at least fqss_nsdr_ws_doubles(P, N) = 2 * P * ceil(N / FQSS_TRACK_TILE) doubles
+ *   (0 for arguments that are refused), uninitialised. */
+#define FQSS_TRACK_TILE 4096
+int64_t fqss_track_stats_ws_doubles(int64_t L);
+int fqss_track_stats(const float* x, double* ws, int64_t ws_doubles, float* stats, int C, int64_t L, int64_t ld, fqss_stream_t stream);
+int fqss_chunk_gather_mc(const float* mix, const float* stats, float* out, int C, int64_t L, int64_t ld, int64_t seg, int64_t stride,
+                         int64_t k0, int G, fqss_stream_t stream);
+int fqss_splitter2_raw_rows(const float* x, float* out, int B, int64_t N, uint32_t* row_max, fqss_stream_t stream);
+int fqss_infer_ola_chunks_affine(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L, int64_t seg,
+                                 int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream);
+int64_t fqss_nsdr_ws_doubles(int P, int64_t N);
+int fqss_nsdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t N, int64_t ld_e, int64_t ld_r,
+              fqss_stream_t stream);
+
 
 #ifdef __cplusplus
 }
