@@ -97,7 +97,7 @@ def restore(ck, step, teacher):
     """a loaded checkpoint into a freshly built run: stepper (student, arena, quantizer state), teacher, random streams -> the
     trainer's own state.  The streams come last, so nothing the restore itself draws moves them."""
     step.load_state_dict(ck["step"])
-    if teacher is not None and ck.get("teacher") is not None:
+    if teacher is not None and ck.get("teacher") is not None and step.teacher is not None:
         teacher.load_state_dict(ck["teacher"], strict=True)
         step.teacher._planes = None         # (the fused teacher chain splits its weights once: from these, not the fresh ones)
     set_rng_state(ck["rng"])

@@ -1645,6 +1645,77 @@ int fqss_nsdr(const float* est, const float* ref, double* ws, int64_t ws_doubles
     return FQSS_OK;
 }
 
+// include/fqss.h, fqss_hd_loss_x: the statement in straight loops (fp64 sums in index order; the workspace is not used)
+int64_t fqss_hd_loss_x_ws_doubles(int B, int S, int64_t N, int teacher) {
+    if (B <= 0 || S <= 0 || N <= 0 || (int64_t)B * S > 65535) return 0;
+    return (int64_t)B * S * (teacher ? 5 : 3) * ((N + FQSS_HD_LOSS_TILE - 1) / FQSS_HD_LOSS_TILE + 1) + 3 * (int64_t)S;
+}
+int fqss_hd_loss_x(const float* est, const float* fest, const float* src, const float* wt, double* ws, float* out, float* coef, float* gest,
+                   int B, int S, int64_t N, float kd_lambda, int kind, fqss_stream_t) {
+    REQUIRE(kind == 0 || kind == 1, "kind: 0 = l1, 1 = mse");
+    REQUIRE(kind == 0 || fest == nullptr, "the mse loss has no distillation term (solver.py:364): fest must be null");
+    REQUIRE(fest != nullptr || kd_lambda == 0.0f, "kd_lambda > 0 needs a teacher estimate (fest is null)");
+    REQUIRE(B >= 0 && S > 0 && N >= 0 && (int64_t)B * S <= 65535, "bad shape");
+    if (B == 0 || N == 0) return FQSS_OK;
+    REQUIRE(est && src && wt && ws && out && coef, "null pointer");
+    auto sgn = [](float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); };
+    const double dn = (double)N, lam = (double)kd_lambda;
+    double wsum = 0.0, tot[3] = {0.0, 0.0, 0.0};
+    for (int s = 0; s < S; ++s) wsum += wt[s];
+    for (int s = 0; s < S; ++s) {
+        double ls = 0.0, rs = 0.0, ns = 0.0, ks = 0.0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t bs = (int64_t)b * S + s;
+            const float *e = est + bs * N, *r = src + bs * N, *f = fest ? fest + bs * N : nullptr;
+            double A = 0.0, Q = 0.0, P = 0.0, Kd = 0.0, F = 0.0;
+            for (int64_t i = 0; i < N; ++i) {
+                const double sv = r[i], d = (double)e[i] - sv;
+                A += fabs(d);
+                Q += d * d;
+                P += sv * sv;
+                if (f) {
+                    Kd += fabs((double)e[i] - (double)f[i]);
+                    F += (sv - (double)f[i]) * (sv - (double)f[i]);
+                }
+            }
+            ns += 10.0 * log10((P + 1e-7) / (Q + 1e-7));
+            float w = 1.0f;
+            if (f) {
+                const float sdr_t = 10.0f * log10f((float)((P + 1e-7) / (F + 1e-7)));
+                const float sdr_q = 10.0f * log10f((float)((P + 1e-7) / (Q + 1e-7)));
+                w = expf((sdr_t - sdr_q) / 10.0f);
+                ks += (double)w * (Kd / dn);
+            }
+            out[3 + 4 * S + bs] = w;
+            ls += kind == 0 ? A / dn : Q / dn;
+            rs += kind == 0 ? A / dn : sqrt(Q / dn);
+            const double c = (double)wt[s] / wsum;
+            const float c0 = (float)(c * (f ? 1.0 - lam : (kind == 0 ? 1.0 : 2.0)) / ((double)B * dn));
+            const float c1 = f ? (float)(c * lam * (double)w / ((double)B * dn)) : 0.0f;
+            if (gest)
+                for (int64_t i = 0; i < N; ++i) {
+                    const float d = e[i] - r[i];
+                    float g = kind == 1 ? c0 * d : c0 * sgn(d);
+                    if (f) g += c1 * sgn(e[i] - f[i]);
+                    gest[bs * N + i] = g;
+                }
+            coef[bs * 2 + 0] = c0;
+            coef[bs * 2 + 1] = c1;
+        }
+        ls /= B, rs /= B, ns /= B, ks /= B;
+        if (fest) ls = (1.0 - lam) * ls + lam * ks;
+        out[3 + s] = (float)ls;
+        out[3 + S + s] = (float)rs;
+        out[3 + 2 * S + s] = (float)ns;
+        out[3 + 3 * S + s] = (float)ks;
+        tot[0] += (double)wt[s] * ls;
+        tot[1] += (double)wt[s] * rs;
+        tot[2] += (double)wt[s] * ns;
+    }
+    for (int k = 0; k < 3; ++k) out[k] = (float)(tot[k] / wsum);
+    return FQSS_OK;
+}
+
 // include/fqss.h, fqss_aq_hist / fqss_aq_mse_search: the histogram-MSE activation observer in straight fp64 loops.  The workspace has the
 // layout of the HIP library's (csrc/aq_mse.hip AqLayout), so that kernels.aq_mse_search reads b, vals and e(i, j) from either.
 namespace {

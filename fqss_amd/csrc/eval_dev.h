@@ -39,6 +39,19 @@ __device__ __forceinline__ float ola_chunks_sample(const float* __restrict__ chu
     return acc / wsum;
 }
 
+// p[i .. i + 3] clipped to [0, n): one 16-byte request when VEC (the caller vouches for the alignment) and the quad is whole; 0 past n.
+// The tile sums of track_eval.hip and of hd_loss.hip (fqss_hd_loss_x) read through it: both load forms give the same samples
+template <bool VEC>
+__device__ __forceinline__ void load_quad(const float* __restrict__ p, int64_t i, int64_t n, float (&v)[4]) {
+    if (VEC && i + 4 <= n) {
+        const float4 q = *reinterpret_cast<const float4*>(p + i);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = i + e < n ? p[i + e] : 0.0f;
+    }
+}
+
 // torch.clip(v, -128, 127) of process.py:14: a NaN stays NaN (fminf / fmaxf would return the bound, and the 0 / 0 of a silent row
 // would come out as -1 where the reference -- and include/fqss.h -- say NaN)
 __device__ __forceinline__ float split_clip(float v) {

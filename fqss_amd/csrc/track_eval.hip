@@ -14,18 +14,6 @@ namespace fqss {
 constexpr int kTile = FQSS_TRACK_TILE;
 static_assert(kTile == 256 * 4 * 4, "a tile is 256 lanes x 4 visits x 4 samples");
 
-// p[i .. i + 3] clipped to [0, n): one 16-byte request when VEC (the caller vouches for the alignment) and the quad is whole
-template <bool VEC>
-__device__ __forceinline__ void load_quad(const float* __restrict__ p, int64_t i, int64_t n, float (&v)[4]) {
-    if (VEC && i + 4 <= n) {
-        const float4 q = *reinterpret_cast<const float4*>(p + i);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = i + e < n ? p[i + e] : 0.0f;
-    }
-}
-
 // sum of p[0 .. n) in every thread of a 256-thread workgroup: lane i adds p[i], p[i + 256], .. in index order, then the DPP tree and the
 // four waves in wave order.  smem: 5 doubles
 __device__ __forceinline__ double tile_order_sum(const double* p, int64_t n, double* smem) {

@@ -1,5 +1,7 @@
 """Thin torch-tensor front end of the C ABI: shape/stride checks on the host, then one ctypes
 call per kernel on torch's current HIP stream.  No arithmetic happens in this file."""
+import collections
+
 import torch
 
 from . import _lib
@@ -2908,6 +2910,36 @@ def hd_kd_loss(est, fest, src, weights, kd_lambda, want_grad=True):
     g = torch.empty_like(est) if want_grad else None
     _lib.call("fqss_hd_kd_loss", _p(est), _p(fest), _p(src), _p(weights), _p(sums), _p(out), _p(coef), _p(g), B, S, N, float(kd_lambda), _stream())
     return out[:1], out[1:1 + S], out[1 + S:1 + 2 * S], out[1 + 2 * S:].view(B, S), g
+
+
+HD_LOSS_KINDS = {"l1": 0, "mse": 1}
+HdLoss = collections.namedtuple("HdLoss", "loss reco nsdr loss_s reco_s nsdr_s kd_s w gest")
+
+
+def hd_loss_x(est, fest, src, weights, kd_lambda, kind="l1", want_grad=True):
+    """the htdemucs solver's losses and its validation nSDR in one pass (solver.py:333-390; fqss_hd_loss_x in include/fqss.h): est / src
+    [B, S, C, T], fest the teacher's estimate or None, kind "l1" | "mse" -> HdLoss(loss [1], reco [1], nsdr [1], loss_s / reco_s / nsdr_s /
+    kd_s [S], w [B, S], dloss/dest or None).  Without a teacher kd_lambda must be 0; mse takes no teacher.  An empty batch (B = 0 or no
+    samples) gives NaN in every field."""
+    if kind not in HD_LOSS_KINDS:
+        raise ValueError(f"hd_loss_x: kind {kind!r}: one of {sorted(HD_LOSS_KINDS)}")
+    _need_gpu(est, fest, src, weights)
+    est, src = est.contiguous(), src.contiguous()
+    fest = None if fest is None else fest.contiguous()
+    B, S = est.shape[0], est.shape[1]
+    N = est.numel() // max(B * S, 1)
+    assert (fest is None or fest.shape == est.shape) and src.shape == est.shape and weights.numel() == S
+    n_ws = _lib.query("fqss_hd_loss_x_ws_doubles", B, S, N, int(fest is not None))
+    ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
+    out = torch.empty(3 + 4 * S + B * S, device=est.device, dtype=torch.float32)
+    if B == 0 or N == 0:
+        out.fill_(float("nan"))         # the entry point writes nothing for an empty batch: the means of nothing are NaN
+    coef = torch.empty(max(B * S * 2, 1), device=est.device, dtype=torch.float32)
+    g = torch.empty_like(est) if want_grad else None
+    _lib.call("fqss_hd_loss_x", _p(est), _p(fest), _p(src), _p(weights), _p(ws), _p(out), _p(coef), _p(g), B, S, N, float(kd_lambda),
+              HD_LOSS_KINDS[kind], _stream())
+    s = [out[3 + k * S:3 + (k + 1) * S] for k in range(4)]
+    return HdLoss(out[0:1], out[1:2], out[2:3], s[0], s[1], s[2], s[3], out[3 + 4 * S:].view(B, S), g)
 
 
 # ------------------------------------------------------------------ evaluation side (csrc/infer.hip)

@@ -509,11 +509,15 @@ class KDTrainStep:
     def __init__(self, model, fmodel, kd_lambda=0.1, lr=1e-3, clip=5.0, comm=None, loss="sisdr_pit", source_weights=None,
                  batched_quantizers=True, fast=True, coded=True, buckets=None, sync_observer_ranges=True,
                  betas=(0.9, 0.999), loss_threshold=None, teacher_ahead=False, accumulate=1, optimizer="adam", weight_decay=0.0,
-                 momentum=0.0, nesterov=False, param_decay=None, ema_decays=(), ema_epoch_decays=()):
+                 momentum=0.0, nesterov=False, param_decay=None, ema_decays=(), ema_epoch_decays=(), loss_kind="l1"):
         """loss: "sisdr_pit" = the asteroid KD loss (mysystem.py:124-151); "sisdr_pit_per_sample" = the speechbrain env's form of it
         (speechbrain_librimix_trainer.py:99-115, 141-149: log per sample, mean over the samples whose loss exceeds `loss_threshold`;
         per-GPU batch 1 or 2, see fqss_kd_loss_per_sample); "l1_sdr" = the htdemucs solver's
         (solver.py:333-366: L1 task + SDR-weighted L1 distillation, per-source weights).  clip <= 0: no clipping (htdemucs.yaml:84).
+        loss_kind ("l1_sdr" only): "l1" | "mse", the solver's optim.loss.  "mse" has no distillation term (solver.py:364-368): the step
+        keeps no teacher whatever fmodel and kd_lambda say.  fmodel=None: a teacher-free step (kd_lambda must be 0) -- no teacher is
+        held and no teacher forward runs, eagerly or in the captured graphs; its l1_sdr loss node is fqss_hd_loss_x, as is mse's.  With
+        a teacher and l1 the loss node stays fqss_hd_kd_loss.
         batched_quantizers=False keeps every quantizer on its own launches (no QuantTables / codes-only dataflow);
         fast=False: quantizing layers also write their fp32 outputs (no carriers); coded=False: no layer output carries codes,
         every layer runs its un-fused fp32 kernels (the reference dataflow the tests pin the fused step against).
@@ -582,6 +586,12 @@ class KDTrainStep:
         self.loss_kind, self.source_weights, self.batched_quantizers = loss, source_weights, batched_quantizers
         if loss not in ("sisdr_pit", "sisdr_pit_per_sample", "l1_sdr"):
             raise ValueError(f"unknown loss {loss!r}")
+        if loss_kind not in K.HD_LOSS_KINDS or (loss_kind != "l1" and loss != "l1_sdr"):
+            raise ValueError(f"loss_kind {loss_kind!r}: one of {sorted(K.HD_LOSS_KINDS)}, and only the l1_sdr loss has kinds")
+        self.hd_kind = loss_kind
+        self.has_teacher = fmodel is not None and loss_kind != "mse"
+        if not self.has_teacher and loss_kind != "mse" and kd_lambda > 0:
+            raise ValueError(f"kd_lambda = {kd_lambda} needs a teacher (fmodel is None)")
         self.loss_threshold = loss_threshold       # per-sample objective only: samples at or below it leave the batch mean
         self.fast, self.coded = bool(fast and coded), bool(coded)
         self._graphs = None
@@ -638,11 +648,13 @@ class KDTrainStep:
             assert all(self.segments[k][1] == self.segments[k + 1][0] for k in range(len(self.segments) - 1)), self.segments
         self._cstream = None
         self.comm_events = None     # bench.py: (end of the last backward segment, all exchanges joined) as timing events of a replay
-        for p in fmodel.parameters():
-            p.requires_grad_(False)
-        self.teacher = TeacherRunner(fmodel)     # fused inference chain for the frozen float teacher
-        if self.cpu:
-            self.teacher.ok = False
+        self.teacher = None
+        if self.has_teacher:
+            for p in fmodel.parameters():
+                p.requires_grad_(False)
+            self.teacher = TeacherRunner(fmodel)     # fused inference chain for the frozen float teacher
+            if self.cpu:
+                self.teacher.ok = False
         self._tstream = None
         self.last = None
         self.tables = None          # QuantTables once the quantizing phase is reached
@@ -684,6 +696,12 @@ class KDTrainStep:
         return {"kind": o["kind"], "weight_decay": o["weight_decay"], "momentum": o["momentum"], "nesterov": o["nesterov"],
                 "param_decay": dict(o["param_decay"]) if self._wd_slot is not None else {}}
 
+    def _objective_block(self):
+        """the checkpoint's `objective` entry: None for a step with a teacher and the l1 kind, whose files keep the keys they always had"""
+        if self.has_teacher and self.hd_kind == "l1":
+            return None
+        return {"loss_kind": self.hd_kind, "teacher": bool(self.has_teacher)}
+
     def _check_stored_optim(self, sd):
         """the moments of one optimizer mean nothing to another (SGD's buffer lives where Adam's first moment does), and an EMA copy
         belongs to its decay: a file written under another kind or another EMA list is refused, naming both"""
@@ -694,6 +712,11 @@ class KDTrainStep:
                 raise ValueError(f"KDTrainStep.load_state_dict: the file was written by optimizer {theirs['kind']!r} (momentum "
                                  f"{theirs['momentum']}, nesterov {theirs['nesterov']}), this step runs {mine['kind']!r} (momentum "
                                  f"{mine['momentum']}, nesterov {mine['nesterov']}); their state does not carry over")
+        default = {"loss_kind": "l1", "teacher": True}
+        mine, theirs = self._objective_block() or default, sd.get("objective") or default
+        if mine != theirs:
+            raise ValueError(f"KDTrainStep.load_state_dict: the file was written under the objective {theirs} (loss kind, with a teacher), "
+                             f"this step trains under {mine}; the best loss and the moments of one do not carry over to the other")
         ema = sd.get("ema") or {"kinds": [], "decays": []}
         if list(ema["kinds"]) != self.ema_kinds or [float(d) for d in ema["decays"]] != self.ema_decays:
             raise ValueError(f"KDTrainStep.load_state_dict: the file holds the EMA copies {list(zip(ema['kinds'], ema['decays']))}, "
@@ -708,7 +731,8 @@ class KDTrainStep:
         gets the same `rank_ranges`.  Not stored: QuantTables, graphs and look-ahead results (rebuilt by the next eager quantizing step
         and maybe_capture), and the integer shadows of FQSS_DETERMINISTIC=1, which are empty between steps.  Nor the gradient
         accumulator: a window with micro-batches pending is refused (the trainers flush() before they write a checkpoint).
-        Only a step that departs from plain Adam without decay adds `optim`; only a step with EMA copies adds `ema`."""
+        Only a step that departs from plain Adam without decay adds `optim`; only a step with EMA copies adds `ema`; only a step
+        without a teacher or with another loss kind than l1 adds `objective`."""
         if self.pending or self._open:
             raise RuntimeError(f"KDTrainStep.state_dict: {self.pending + int(self._open)} micro-batch(es) of an accumulation window are "
                                "pending; call flush() first (their gradients are not part of the stored state)")
@@ -727,6 +751,8 @@ class KDTrainStep:
         more = {}
         if self._optim_block() is not None:
             more["optim"] = self._optim_block()
+        if self._objective_block() is not None:
+            more["objective"] = self._objective_block()
         if self.ema_decays:
             more["ema"] = {"kinds": list(self.ema_kinds), "decays": list(self.ema_decays), "count": c(self.ema_count),
                            "copies": [c(e) for e in self.ema], "extra": [{n: c(t) for n, t in x.items()} for x in self.ema_extra]}
@@ -859,7 +885,8 @@ class KDTrainStep:
         # MFMA-bound GEMMs overlap the student's HBM-bound layers; inside a hipGraph capture this becomes a parallel
         # branch of the graph) and joins before the loss.
         cur = None if self.cpu else torch.cuda.current_stream()
-        teacher_free = self.loss_kind != "l1_sdr" and not self.kd_lambda > 0        # kd_lambda = 0: plain PIT SI-SDR loss, no teacher
+        # kd_lambda = 0: plain PIT SI-SDR loss, no teacher; l1_sdr: a step built without one (fmodel=None, or loss_kind="mse")
+        teacher_free = not self.has_teacher or (self.loss_kind != "l1_sdr" and not self.kd_lambda > 0)
         ahead = fest_given is not None
         two_streams = TEACHER_STREAM and not self.cpu
         if teacher_free:
@@ -900,6 +927,14 @@ class KDTrainStep:
         if self.loss_kind == "l1_sdr":
             if self.source_weights is None:
                 self.source_weights = torch.ones(tgt.shape[1], device=tgt.device)
+        if self.loss_kind == "l1_sdr" and teacher_free:
+            # mse (solver.py:364-368) or l1 without the distillation term: the loss family's entry point, nSDR beside the loss
+            r = K.hd_loss_x(est.detach(), None, tgt, self.source_weights, 0.0, kind=self.hd_kind, want_grad=True)
+            gest = r.gest
+            if self.grad_at is not None:
+                gest = K.hd_loss_x(self.grad_at, None, tgt, self.source_weights, 0.0, kind=self.hd_kind, want_grad=True).gest
+            res = dict(loss=r.loss, task=r.loss_s, kd=r.kd_s, w=r.w, reco=r.reco, nsdr=r.nsdr, nsdr_s=r.nsdr_s, gnorm=a.gnorm, est=est.detach())
+        elif self.loss_kind == "l1_sdr":
             loss, task, kd, w, gest = K.hd_kd_loss(est.detach(), fest, tgt, self.source_weights, self.kd_lambda, want_grad=True)
             if self.grad_at is not None:       # tests: dloss/dest taken at a given output (the L1 loss has a sign gradient)
                 gest = K.hd_kd_loss(self.grad_at, fest, tgt, self.source_weights, self.kd_lambda, want_grad=True)[4]
@@ -1211,7 +1246,7 @@ class KDTrainStep:
         fest_cur = None
         self._tgraph = None
         self._ahead_key = None
-        if self.teacher_ahead and (self.loss_kind == "l1_sdr" or self.kd_lambda > 0):
+        if self.teacher_ahead and self.has_teacher and (self.loss_kind == "l1_sdr" or self.kd_lambda > 0):
             if self._tstream is None:
                 self._tstream = _teacher_stream()
             self._sxn = x.clone()

@@ -8,20 +8,24 @@ reference's hydra entry point does (train.py:44-46 passes `+device=<device>`); t
 reference always reads configs/htdemucs.yaml through hydra.  Step semantics kept (solver.py:314-429):
   * train: mix = sum of the stems; estimate = student(mix); teacher under no_grad; loss = source-weighted
     (1 - kd_lambda) L1(est, src) + kd_lambda w L1(est, teacher), w = exp((sdr_teacher - sdr_student) / 10) per (sample, source);
+    `kd_lambda: 0` is the plain QAT run -- no teacher is built or run; `optim.loss: mse` is the source-weighted mean squared error,
+    which has no distillation term in the reference either (solver.py:364-368: no teacher, kd_lambda ignored with a warning);
     optional clip_grad; Adam(lr, betas (momentum, beta2)); global batch divided over the ranks (train.py:200-201), gradients
     averaged over ranks;
-  * valid: eval mode on the validation stems, `reco` = source-weighted L1; the best state by `test.metric: loss` is written to
-    `<work_dir>/best.th` as {"state", "kwargs", "history"} (the keys load_model.py:38-45, 76-102 read back);
+  * valid: eval mode on the validation stems: `loss` (of optim.loss), `reco` (L1, or the root of the mse), `nsdr` and
+    `nsdr_<source>` (demucs' new_sdr, solver.py:384-390) from one kernels.hd_loss_x call per batch, for the model and every EMA copy;
+    the best state by `test.metric` (`loss`: lowest, `nsdr`: highest) is written to `<work_dir>/best.th` as {"state", "kwargs", "history"} (the keys load_model.py:38-45, 76-102 read back);
   * every epoch ends with `<work_dir>/checkpoint.pth`, the full training state (the place of the solver's checkpoint.th); `resume=<path>`
     or `resume=auto` continues from one (fqss_amd/checkpoint.py).
 Data: `dset.name: synthetic` (seeded Gaussian stems), or folders of WAV stems (`dset.wav` / `dset.musdb` + `use_musdb`, wav_dataset.py):
 a prefetching reader a batch ahead of the step, int16 samples to the device, demucs' repitch (kernels.hd_repitch, an integer restatement:
 soundstretch is absent), its other augmentations (shift / flip / scale / remix, restated) and the mixture in one fused kernel;
-validation is un-augmented windows of the training length.  EMA copies,
-`apply_model` split inference and the SDR evaluation are the reference's CPU / third-party data side."""
+validation is un-augmented windows of the training length.  `apply_model` split inference in validation (`valid_apply`) is not
+built: validation scores windows of the training length."""
 import json
 import os
 import sys
+import warnings
 
 import torch
 import yaml
@@ -87,8 +91,12 @@ class Solver:
     def __init__(self, conf, model, fmodel, comm, device):
         self.conf, self.model, self.fmodel, self.comm, self.device = conf, model, fmodel, comm, device
         opt = conf["optim"]
-        if opt.get("loss", "l1") != "l1":
-            raise NotImplementedError("htdemucs env: optim.loss: the L1 loss is the one that is built")
+        self.loss_kind = str(opt.get("loss", "l1"))
+        if self.loss_kind not in K.HD_LOSS_KINDS:
+            raise ValueError(f"htdemucs env: optim.loss {opt.get('loss')!r}: l1 or mse")
+        self.metric = str((conf.get("test") or {}).get("metric", "loss"))
+        if self.metric not in ("loss", "nsdr"):
+            raise ValueError(f"htdemucs env: test.metric {self.metric!r}: loss or nsdr")
         # get_optimizer (train.py:88-119): Adam or AdamW over the model, the modules with a make_optim_group() -- the cross-transformer --
         # in a group of their own, with their own weight decay whatever optim.weight_decay says
         kind = str(opt.get("optim", "adam")).lower()
@@ -97,13 +105,14 @@ class Solver:
         self.weights = torch.tensor(conf.get("weights", [1.0] * model.n_srcs), device=device, dtype=torch.float32)
         ema = conf.get("ema") or {}
         self.step = KDTrainStep(model, fmodel, kd_lambda=float(conf.get("kd_lambda", 0.1)), lr=float(opt["lr"]),
-                                clip=float(opt.get("clip_grad") or 0.0), comm=comm, loss="l1_sdr", source_weights=self.weights,
+                                clip=float(opt.get("clip_grad") or 0.0), comm=comm, loss="l1_sdr", loss_kind=self.loss_kind,
+                                source_weights=self.weights,
                                 betas=(float(opt.get("momentum", 0.9)), float(opt.get("beta2", 0.999))),
                                 accumulate=opt.get("accumulate_grad_batches", 1),    # ours (demucs has none): micro-batches per update
                                 optimizer=kind, weight_decay=float(opt.get("weight_decay", 0) or 0), param_decay=group_decays(model),
                                 ema_decays=tuple(ema.get("batch") or ()), ema_epoch_decays=tuple(ema.get("epoch") or ()))
         self.history = []
-        self.best_state, self.best_loss = None, float("inf")
+        self.best_state, self.best_loss = None, float("-inf" if self.metric == "nsdr" else "inf")
         self.ckpt_file = os.path.join(conf["work_dir"], checkpoint.NAME)
         self.sets = None
         if wav_dataset.configured(conf["dset"]):
@@ -118,6 +127,9 @@ class Solver:
         """student, arena, quantizer state, learning rate, teacher and random streams from a training-state checkpoint; then the
         solver's own fields.  The next epoch is len(history)."""
         ts = checkpoint.restore(ckpt, self.step, self.fmodel)
+        if ts.get("metric", "loss") != self.metric:
+            raise ValueError(f"htdemucs env: the checkpoint's best state was chosen by test.metric {ts.get('metric', 'loss')!r}, this run "
+                             f"asks for {self.metric!r}")
         self.history, self.best_loss, self.best_state = list(ts["history"]), ts["best_loss"], ts["best_state"]
         if self.comm.rank == 0:
             print(f"Resuming after epoch {len(self.history)}: best {self.best_loss}", flush=True)
@@ -164,22 +176,30 @@ class Solver:
             d = self.conf["dset"]
             n = d["steps_per_epoch"] if train else d["valid_steps"]
             it = self._synthetic_batches(epoch, n, train)
-        tot = torch.zeros(1, device=self.device, dtype=torch.float64)
+        S = self.model.n_srcs
+        tot = torch.zeros(3 + S, device=self.device, dtype=torch.float64)      # loss, reco, nsdr, nsdr per source
         self.model.train(train)
         for mix, sources in it:
             if train:
                 self.step.maybe_capture(mix, sources)
-                tot += self.step(mix, sources)["loss"].double()
+                r = self.step(mix, sources)
+                # a teacher-free step returns the solver's `reco` (mse: the mean root, solver.py:367-368); the L1 + teacher step logs
+                # its loss under both names, as it always has
+                tot[:2] += torch.cat([r["loss"], r.get("reco", r["loss"])]).double()
             else:
                 with torch.no_grad():
                     est = self.model(mix)
-                    loss, task, _, _, _ = K.hd_kd_loss(est, est, sources, self.weights, 0.0, want_grad=False)    # kd_lambda 0: the L1 task loss
-                tot += loss.double()
+                    # solver.py:364-390: the task loss of optim.loss, its `reco` and new_sdr per source, one pass over est and sources
+                    r = K.hd_loss_x(est, None, sources, self.weights, 0.0, kind=self.loss_kind, want_grad=False)
+                tot += torch.cat([r.loss, r.reco, r.nsdr, r.nsdr_s]).double()
         if train:
             self.step.flush()       # optim.accumulate_grad_batches: a window the epoch cut short updates on what it holds
             self.step.ema_epoch_update()    # ema.epoch: once per epoch, after training (solver.py:438-440)
         self.comm.all_reduce_sum(tot)
-        out = {"loss": tot.item() / (n * self.comm.world), "reco": tot.item() / (n * self.comm.world)}
+        mean = (tot / (n * self.comm.world)).tolist()
+        out = {"loss": mean[0], "reco": mean[1]}
+        if not train:
+            out.update(nsdr=mean[2], **{f"nsdr_{name}": v for name, v in zip(self.model.sources, mean[3:])})
         if train:
             out["launch"] = "hipGraph replay" if self.step._graphs is not None else "eager"
         if pf is not None:
@@ -190,10 +210,10 @@ class Solver:
         for epoch in range(len(self.history), self.conf["epochs"]):
             m = {"train": self._run_one_epoch(epoch), "valid": self._run_one_epoch(epoch, train=False)}
             self.model.train()
-            key = self.conf.get("test", {}).get("metric", "loss")
-            if key != "loss":
-                raise NotImplementedError("htdemucs env: best-model selection by nsdr needs demucs' evaluation (third party)")
-            # the EMA copies are validated with the model's own pass; the best of them all by `loss` is the epoch's candidate for
+            # test.metric (solver.py:220-236): the lowest `loss` or the highest `nsdr`; `better` compares two values of it
+            key = self.metric
+            better = (lambda a, b: a > b) if key == "nsdr" else (lambda a, b: a < b)
+            # the EMA copies are validated with the model's own pass; the best of them all by the metric is the epoch's candidate for
             # best_state, under the name the reference records (solver.py:220-236)
             # (a run without copies keeps the history it always wrote: `valid` is the model's own pass)
             bcopy = None
@@ -206,27 +226,27 @@ class Solver:
                     with self.step.ema_swap(k):
                         v = self._run_one_epoch(epoch, train=False)
                     m["valid"][name] = v
-                    if v["loss"] < bvalid["loss"]:
+                    if better(v[key], bvalid[key]):
                         bvalid, bname, bcopy = v, name, k
                 m["valid"].update(bvalid)
                 m["valid"]["bname"] = bname
             self.model.train()
-            if m["valid"]["loss"] <= self.best_loss:
-                self.best_loss = m["valid"]["loss"]
+            if not better(self.best_loss, m["valid"][key]):        # (best_loss: the best value of the metric so far, whichever it is)
+                self.best_loss = m["valid"][key]
                 state = self.model.state_dict() if bcopy is None else self.step.ema_state(bcopy)
                 self.best_state = {k: v.detach().cpu().clone() for k, v in state.items()}
             m["valid"]["best"] = self.best_loss
             self.history.append(m)
             if self.comm.rank == 0:
-                print(f"epoch {epoch + 1}: train loss {m['train']['loss']:.5f}  valid loss {m['valid']['loss']:.5f}  best {self.best_loss:.5f}",
-                      flush=True)
+                print(f"epoch {epoch + 1}: train loss {m['train']['loss']:.5f}  valid loss {m['valid']['loss']:.5f}  nsdr "
+                      f"{m['valid']['nsdr']:.3f}  best {key} {self.best_loss:.5f}", flush=True)
                 os.makedirs(self.conf["work_dir"], exist_ok=True)
                 torch.save({"state": self.best_state, "kwargs": self.model._init_kwargs, "history": self.history},
                            os.path.join(self.conf["work_dir"], "best.th"))
                 with open(os.path.join(self.conf["work_dir"], "history.json"), "w") as f:
                     json.dump(self.history, f)
             checkpoint.save_training_state(self.ckpt_file, self.step, dict(epoch=epoch + 1, history=self.history, best_loss=self.best_loss,
-                                                                           best_state=self.best_state), self.fmodel)
+                                                                           best_state=self.best_state, metric=self.metric), self.fmodel)
         return self.history
 
 
@@ -249,9 +269,12 @@ def get_solver(conf, ckpt=None):
     if mc.get("model_path"):
         sd = torch.load(mc["model_path"], map_location="cpu", weights_only=False)   # trusted local package ({"state", "kwargs"})
         model.load_state_dict(sd.get("state", sd), strict=True)
-    fmodel = copy.deepcopy(model).to(dev).eval() if float(conf.get("kd_lambda", 0.1)) > 0 else None
-    if fmodel is None:
-        raise NotImplementedError("htdemucs env: kd_lambda = 0 (no teacher) is not built; the shipped value is 0.1")
+    # the float teacher, frozen before the student is quantized -- unless nothing distils from it: kd_lambda 0 (plain QAT), or
+    # optim.loss: mse, whose branch of the reference never looks at the teacher (solver.py:364)
+    lam, mse = float(conf.get("kd_lambda", 0.1)), conf["optim"].get("loss", "l1") == "mse"
+    if mse and lam > 0:
+        warnings.warn(f"htdemucs env: optim.loss: mse has no distillation term; kd_lambda = {lam} is ignored and no teacher is built")
+    fmodel = copy.deepcopy(model).to(dev).eval() if lam > 0 and not mse else None
     model = quantize_model(model, mc["quantization"]).to(dev).train()
     model._init_kwargs = kwargs
     assert conf["batch_size"] % comm.world == 0

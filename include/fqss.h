@@ -1206,6 +1206,32 @@ int fqss_transpose2d(const float* x, float* y, int64_t batch, int64_t R, int64_t
 int fqss_hd_kd_loss(const float* est, const float* fest, const float* src, const float* wt, double* sums, float* out, float* coef,
                     float* gest, int B, int S, int64_t N, float kd_lambda, fqss_stream_t stream);
 
+/* The loss family around it (csrc/hd_loss.hip; solver.py:333-390): l1 or mse, with or without a teacher, and the nSDR the solver's
+ * validation logs, from one pass.  est / src (/ fest) [B][S][N] dense, N = channels * samples; wt [S].  Per item (b, s), in fp64 (the
+ * differences are formed in fp64, i.e. exactly): A = sum |est - src|, Q = sum (est - src)^2, P = sum src^2, and with a teacher
+ * K = sum |est - fest|, F = sum (src - fest)^2.
+ *   kind 0 (l1), fest given: fqss_hd_kd_loss' statement -- task_s = mean_b A / N, w_bs = exp((sdr(src, fest) - sdr(src, est)) / 10) by
+ *     its fp32 operation sequence, kd_s = mean_b w_bs K / N, loss_s = (1 - lambda) task_s + lambda kd_s, reco_s = task_s.
+ *   kind 0, fest NULL (kd_lambda must be 0): loss_s = reco_s = mean_b A / N.
+ *   kind 1 (mse, solver.py:364-368; fest must be NULL -- the reference has no distillation term there): loss_s = mean_b Q / N,
+ *     reco_s = mean_b sqrt(Q / N).
+ *   every kind: nsdr_bs = 10 log10((P + 1e-7) / (Q + 1e-7)) (demucs' new_sdr), nsdr_s = mean_b nsdr_bs, and
+ *     (loss, reco, nsdr) = sum_s wt_s (loss_s, reco_s, nsdr_s) / sum_s wt_s.  Everything is fp64 until it is stored as fp32.
+ * out: [loss, reco, nsdr, loss_s.., reco_s.., nsdr_s.., kd_s.. (0 without a teacher), w_bs.. (1 without a teacher)] =
+ *   3 + 4S + B*S floats.  coef: B*S*2 floats of scratch.  gest (optional) = dloss/dest: wt_s / (sum wt * B * N) times
+ *   sign(est - src) (l1, sign(0) = 0; with a teacher (1 - lambda) of it plus lambda w_bs sign(est - fest)) or 2 (est - src) (mse).
+ * Sums: one fp64 partial per tile of FQSS_HD_LOSS_TILE samples and item STORED into ws, added in tile order by one workgroup: no
+ *   atomics, nothing for the caller to clear, the same bits on every run and stream, with 16-byte or one-sample requests alike.
+ *   ws: at least fqss_hd_loss_x_ws_doubles(B, S, N, fest != NULL) doubles (0 for a shape that is refused or empty), uninitialised.
+ * B * S <= 65535 as fqss_hd_kd_loss.  B = 0 or N = 0: FQSS_OK, nothing is written.  A refused call writes nothing.
+ * Cost: not measured.  The one finishing workgroup adds B * S * (3 or 5) * ceil(N / FQSS_HD_LOSS_TILE) partials, four sums at a time,
+ *   and forms a source in one thread over its B items: sized for the recipe (B * S = 16, a few hundred tiles); a serial tail near the
+ *   B * S limit.                                                                                                                 */
+#define FQSS_HD_LOSS_TILE 4096
+int64_t fqss_hd_loss_x_ws_doubles(int B, int S, int64_t N, int teacher);
+int fqss_hd_loss_x(const float* est, const float* fest, const float* src, const float* wt, double* ws, float* out, float* coef,
+                   float* gest, int B, int S, int64_t N, float kd_lambda, int kind, fqss_stream_t stream);
+
 /* Evaluation side (csrc/infer.hip): the SI-SNR matrix between S estimates and S targets (torchmetrics'
  * ScaleInvariantSignalNoiseRatio restated: zero-mean SI-SDR, eps 2^-23) with the re-ordering decision of swap_channel_order
  * (process.py:105-125) as map[d] = (source estimate, sign); the triangular weighted overlap-add of process.model_infer
