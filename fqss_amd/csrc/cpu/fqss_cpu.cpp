@@ -2,7 +2,7 @@
 // batch 2, 1 s ... plumbing, no GPU"; reference train.py:31: device = "cpu" if use_cpu).  Plain C++ (g++, OpenMP), host pointers, the
 // `stream` argument is ignored, every call is synchronous.  It serves the entry points the UN-FUSED ConvTasNet QAT step uses (the
 // per-layer kernels that the G1 layer fixtures pin: KDTrainStep(coded=False, batched_quantizers=False) with the module-path teacher)
-// and, of the evaluation side, the SDR (fqss_sdr), the STOI (fqss_stoi) and the batched chunked path (fqss_splitter2_rows, fqss_chunk_gather,
+// and, of the evaluation side, the SDR (fqss_sdr), the STOI (fqss_stoi) and the batched chunked path (fqss_splitter2_rows, fqss_chunk_gather_mc,
 // fqss_sisnr_chunks, fqss_infer_ola_chunks);
 // anything else is absent from this library and fqss_amd/_lib.py raises.  Arithmetic: the same op sequences as the HIP kernels
 // (fp32, one IEEE operation per operator: built with -ffp-contract=off; IEEE division; round-half-even), reductions in fp64.
@@ -1481,18 +1481,6 @@ static inline float tri_weight(int64_t t, int64_t seg) {      // process.py:166-
     return (t < h ? (float)(t + 1) : (float)(seg - t)) / mx;
 }
 
-int fqss_chunk_gather(const float* mix, float* out, int64_t L, int64_t seg, int64_t stride, int64_t k0, int G, fqss_stream_t) {
-    REQUIRE(mix && out, "null pointer");
-    REQUIRE(chunk_geometry_ok(L, seg, stride) && G > 0 && G <= 65535 && k0 >= 0 && k0 < chunk_count(L, stride),
-            "bad shape (1 <= stride <= seg, 0 <= k0 < ceil(L / stride), 1 <= G <= 65535)");
-    const int64_t N = chunk_count(L, stride);
-    for (int64_t g = 0; g < G; ++g) {
-        const int64_t k = k0 + g < N ? k0 + g : N - 1, n = L - k * stride;
-        for (int64_t t = 0; t < seg; ++t) out[g * seg + t] = t < n ? mix[k * stride + t] : 0.0f;
-    }
-    return FQSS_OK;
-}
-
 int fqss_sisnr_chunks(const float* est, const float* ref, float* db, int* map, int G, int S, int64_t seg, int64_t stride, int64_t k0, int64_t L,
                       int64_t ld_r, fqss_stream_t) {
     REQUIRE(est && ref && db && map, "null pointer");
@@ -1532,12 +1520,11 @@ int fqss_sisnr_chunks(const float* est, const float* ref, float* db, int* map, i
     return FQSS_OK;
 }
 
-// fqss_infer_ola_chunks and, with stats, fqss_infer_ola_chunks_affine: one loop, so that stats == NULL is the former's bits
-static int ola_chunks_run(const char* what, const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L,
-                          int64_t seg, int64_t stride, int64_t ld_chunk, int64_t ld_out) {
-    STOI_REQUIRE(chunks && out, "null pointer");      // (the macro that names the entry point by `what`)
-    STOI_REQUIRE(S > 0 && C > 0 && S * C <= 65535 && chunk_geometry_ok(L, seg, stride) && ld_chunk >= seg && ld_out >= L,
-                 "bad shape (1 <= stride <= seg, ld_chunk >= seg, ld_out >= L)");
+int fqss_infer_ola_chunks(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L, int64_t seg,
+                          int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t) {
+    REQUIRE(chunks && out, "null pointer");
+    REQUIRE(S > 0 && C > 0 && (int64_t)S * C <= 65535 && chunk_geometry_ok(L, seg, stride) && ld_chunk >= seg && ld_out >= L,
+            "bad shape (1 <= stride <= seg, ld_chunk >= seg, ld_out >= L)");
     const int64_t N = chunk_count(L, stride);
 #pragma omp parallel for collapse(2) schedule(static)
     for (int64_t d = 0; d < S; ++d)
@@ -1556,14 +1543,6 @@ static int ola_chunks_run(const char* what, const float* chunks, const int* map,
                 out[(d * C + c) * ld_out + t] = stats ? v * stats[1] + stats[0] : v;      // (-ffp-contract=off: two roundings)
             }
     return FQSS_OK;
-}
-int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S, int C, int64_t L, int64_t seg, int64_t stride,
-                          int64_t ld_chunk, int64_t ld_out, fqss_stream_t) {
-    return ola_chunks_run("fqss_infer_ola_chunks", chunks, map, nullptr, out, S, C, L, seg, stride, ld_chunk, ld_out);
-}
-int fqss_infer_ola_chunks_affine(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L, int64_t seg,
-                                 int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t) {
-    return ola_chunks_run("fqss_infer_ola_chunks_affine", chunks, map, stats, out, S, C, L, seg, stride, ld_chunk, ld_out);
 }
 
 // ------------------------------------------------------------------------------------------------ track evaluation

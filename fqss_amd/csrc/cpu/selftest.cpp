@@ -172,7 +172,7 @@ int main() {
         std::vector<float> rows((size_t)G * seg), sp2((size_t)G * 2 * seg), ck((size_t)(Nc + 1) * Sc * seg), dbc((size_t)G * Sc * Sc), oc((size_t)Sc * Lc);
         std::vector<int> mpc((size_t)(Nc + 1) * Sc * 2);
         std::vector<uint32_t> rmax(G, 0u);
-        CHECK(fqss_chunk_gather(mixc.data(), rows.data(), Lc, seg, hop, 3, G, nullptr) == 0);
+        CHECK(fqss_chunk_gather_mc(mixc.data(), nullptr, rows.data(), 1, Lc, Lc, seg, hop, 3, G, nullptr) == 0);
         for (int64_t t = 0; t < seg; ++t) CHECK(rows[seg + t] == (t < 10 ? mixc[4 * hop + t] : 0.0f) && rows[2 * seg + t] == rows[seg + t]);
         CHECK(fqss_splitter2_rows(rows.data(), sp2.data(), G, seg, rmax.data(), nullptr) == 0);
         for (auto v : sp2) CHECK(v >= -1.0f && v < 1.0f);
@@ -185,13 +185,13 @@ int main() {
         for (int64_t k0 = 0; k0 < Nc; k0 += G)
             CHECK(fqss_sisnr_chunks(ck.data() + k0 * Sc * seg, tgt.data(), dbc.data(), mpc.data() + k0 * Sc * 2, G, Sc, seg, hop, k0, Lc, Lc + 3, nullptr) == 0);
         for (int64_t k = 0; k < Nc; ++k) CHECK(mpc[k * 4] == 1 && mpc[k * 4 + 1] == -1 && mpc[k * 4 + 2] == 0 && mpc[k * 4 + 3] == -1);
-        CHECK(fqss_infer_ola_chunks(ck.data(), mpc.data(), oc.data(), Sc, 1, Lc, seg, hop, seg, Lc, nullptr) == 0);
+        CHECK(fqss_infer_ola_chunks(ck.data(), mpc.data(), nullptr, oc.data(), Sc, 1, Lc, seg, hop, seg, Lc, nullptr) == 0);
         for (int64_t t = 0; t < Lc; ++t) CHECK(fabsf(oc[t] + tgt[t]) <= 1e-6f && fabsf(oc[Lc + t] + tgt[Lc + 3 + t]) <= 1e-6f);
-        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, oc.data(), Sc, 1, Lc, seg, hop, seg, Lc, nullptr) == 0);
-        CHECK(fqss_chunk_gather(mixc.data(), rows.data(), Lc, seg, hop, Nc, G, nullptr) == FQSS_EINVAL);
-        CHECK(fqss_chunk_gather(mixc.data(), rows.data(), Lc, seg, seg + 1, 0, G, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, nullptr, oc.data(), Sc, 1, Lc, seg, hop, seg, Lc, nullptr) == 0);
+        CHECK(fqss_chunk_gather_mc(mixc.data(), nullptr, rows.data(), 1, Lc, Lc, seg, hop, Nc, G, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_chunk_gather_mc(mixc.data(), nullptr, rows.data(), 1, Lc, Lc, seg, seg + 1, 0, G, nullptr) == FQSS_EINVAL);
         CHECK(fqss_sisnr_chunks(ck.data(), tgt.data(), dbc.data(), mpc.data(), G, 17, seg, hop, 0, Lc, Lc + 3, nullptr) == FQSS_EINVAL);
-        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, oc.data(), Sc, 1, Lc, seg, 0, seg, Lc, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, nullptr, oc.data(), Sc, 1, Lc, seg, 0, seg, Lc, nullptr) == FQSS_EINVAL);
         CHECK(fqss_splitter2_rows(rows.data(), sp2.data(), G, seg, nullptr, nullptr) == FQSS_EINVAL);
     }
     // track evaluation: stats of a pitched stereo track, a normalised gather that runs past the short last chunk, the per-item raw
@@ -210,7 +210,7 @@ int main() {
         for (int64_t t = 10; t < seg; ++t) CHECK(ck[(4 * Ct + 1) * seg + t] == 0.0f && ck[(5 * Ct + 1) * seg + t] == 0.0f);
         CHECK(fqss_splitter2_raw_rows(ck.data(), sp.data(), G, Ct * seg, rmax.data(), nullptr) == 0);
         // chunks [N][S = 1][C][seg]: the overlap-add of the normalised chunks, de-normalised, is the track again
-        CHECK(fqss_infer_ola_chunks_affine(ck.data(), nullptr, st.data(), back.data(), 1, Ct, Lt, seg, hop, seg, Lt, nullptr) == 0);
+        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, st.data(), back.data(), 1, Ct, Lt, seg, hop, seg, Lt, nullptr) == 0);
         for (int c = 0; c < Ct; ++c)
             for (int64_t t = 0; t < Lt; ++t) CHECK(fabsf(back[c * Lt + t] - x[c * ldt + t]) <= 1e-5f);
         CHECK(fqss_nsdr(back.data(), x.data(), ws.data(), (int64_t)ws.size(), db.data(), Ct, Lt, Lt, ldt, nullptr) == 0);
@@ -219,7 +219,7 @@ int main() {
         CHECK(fqss_track_stats(x.data(), ws.data(), (int64_t)ws.size(), st.data(), Ct, Lt, Lt - 1, nullptr) == FQSS_EINVAL);
         CHECK(fqss_chunk_gather_mc(x.data(), nullptr, ck.data(), Ct, Lt, ldt, seg, hop, Nt, G, nullptr) == FQSS_EINVAL);
         CHECK(fqss_splitter2_raw_rows(ck.data(), sp.data(), G, Ct * seg, nullptr, nullptr) == FQSS_EINVAL);
-        CHECK(fqss_infer_ola_chunks_affine(ck.data(), nullptr, st.data(), back.data(), 1, Ct, Lt, seg, seg + 1, seg, Lt, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_infer_ola_chunks(ck.data(), nullptr, st.data(), back.data(), 1, Ct, Lt, seg, seg + 1, seg, Lt, nullptr) == FQSS_EINVAL);
         CHECK(fqss_nsdr(back.data(), x.data(), ws.data(), 1, db.data(), Ct, Lt, Lt, ldt, nullptr) == FQSS_EINVAL);
         CHECK(fqss_track_stats_ws_doubles(0) == 0 && fqss_nsdr_ws_doubles(0, Lt) == 0);
     }

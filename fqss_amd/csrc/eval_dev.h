@@ -1,6 +1,6 @@
-// eval_dev.h -- per-sample device functions that more than one file of the evaluation side computes through, so that the kernels that
+// eval_dev.h -- per-sample device functions that more than one kernel of the evaluation side computes through, so that the kernels that
 // must agree bit for bit carry ONE operation sequence (contraction is off: every operator is one IEEE operation):
-//   the weighted overlap-add of infer.hip (k_infer_ola, k_infer_ola_chunks) and of track_eval.hip (k_infer_ola_chunks_affine),
+//   the weighted overlap-add of infer.hip (k_infer_ola, k_infer_ola_chunks),
 //   the normalize=False splitter of codec.hip (k_splitter2_raw) and of track_eval.hip (k_splitter2_raw_rows).
 #pragma once
 #include "fqss_dev.h"

@@ -49,7 +49,7 @@ __global__ void k_sisnr_finish(const double* __restrict__ mom, float* __restrict
     }
 }
 
-// tri_weight, ola_step and the gather form's per-sample walk (ola_chunks_sample): eval_dev.h, shared with track_eval.hip
+// tri_weight, ola_step and the gather form's per-sample walk (ola_chunks_sample): eval_dev.h
 
 // out[d][c][start + t] += w[t] * sign_d * chunk[src_d][c][t];  sum_weight[start + t] += w[t]   (t < n)
 __global__ __launch_bounds__(256) void k_infer_ola(const float* __restrict__ chunk, const int* __restrict__ map, float* __restrict__ out,
@@ -74,17 +74,6 @@ __global__ __launch_bounds__(256) void k_infer_normalize(float* __restrict__ out
 
 // ---- the batched form of the chunked path: G chunks of one utterance per model call (process.model_infer(chunk_batch=G)) ----
 // chunk k covers mix[k * stride : k * stride + seg]; N = ceil(L / stride) chunks; n_k = min(seg, L - k * stride)
-
-// out[g][t] = mix[(k0 + g) * stride + t], zero past L; rows past the last chunk repeat it (one [G, 1, seg] shape serves every group)
-__global__ __launch_bounds__(256) void k_chunk_gather(const float* __restrict__ mix, float* __restrict__ out, int64_t L, int64_t seg,
-                                                       int64_t stride, int64_t k0, int64_t N) {
-    int64_t k = k0 + blockIdx.y;
-    if (k > N - 1) k = N - 1;
-    const float* src = mix + k * stride;
-    const int64_t n = L - k * stride;       // >= 1
-    float* dst = out + (int64_t)blockIdx.y * seg;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < seg; t += (int64_t)gridDim.x * 256) dst[t] = t < n ? src[t] : 0.0f;
-}
 
 // SI-SNR matrix and re-ordering map of every chunk of a group in one launch: one workgroup per chunk, one wave per (estimate, target)
 // pair (round robin), the five fp64 moments summed per lane in index order and over the lanes on the fixed DPP tree -- no atomics, the
@@ -134,13 +123,19 @@ __global__ __launch_bounds__(256) void k_sisnr_chunks(const float* __restrict__ 
 
 // the overlap-add as a gather: every output sample walks the chunks that cover it in increasing k -- the order in which fqss_infer_ola
 // is called chunk after chunk -- through the same ola_step / tri_weight, then divides by its weight sum: bit for bit fqss_infer_ola x N
-// + fqss_infer_normalize, without the zeroed output, the weight buffer and the read-modify-write.  chunks [N][S][C][ld_chunk]
-__global__ __launch_bounds__(256) void k_infer_ola_chunks(const float* __restrict__ chunks, const int* __restrict__ map, float* __restrict__ out,
-                                                           int S, int C, int64_t L, int64_t seg, int64_t stride, int64_t N, int64_t ld_chunk,
-                                                           int64_t ld_out) {
+// + fqss_infer_normalize, without the zeroed output, the weight buffer and the read-modify-write.  chunks [N][S][C][ld_chunk].
+// stats: the de-normalisation in the store, v * std + mean, a multiplication and an addition (contraction is off)
+__global__ __launch_bounds__(256) void k_infer_ola_chunks(const float* __restrict__ chunks, const int* __restrict__ map,
+                                                           const float* __restrict__ stats, float* __restrict__ out, int S, int C, int64_t L,
+                                                           int64_t seg, int64_t stride, int64_t N, int64_t ld_chunk, int64_t ld_out) {
     const int dc = blockIdx.y, d = dc / C, c = dc % C;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < L; t += (int64_t)gridDim.x * 256)
-        out[((int64_t)d * C + c) * ld_out + t] = ola_chunks_sample(chunks, map, S, C, d, c, t, seg, stride, N, ld_chunk);
+    const bool affine = stats != nullptr;
+    const float mean = affine ? stats[0] : 0.0f, sd = affine ? stats[1] : 1.0f;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < L; t += (int64_t)gridDim.x * 256) {
+        float v = ola_chunks_sample(chunks, map, S, C, d, c, t, seg, stride, N, ld_chunk);
+        if (affine) v = v * sd + mean;
+        out[((int64_t)d * C + c) * ld_out + t] = v;
+    }
 }
 
 }  // namespace fqss
@@ -180,19 +175,8 @@ extern "C" int fqss_infer_normalize(float* out, const float* sum_weight, int64_t
     return launch_status("fqss_infer_normalize");
 }
 
-// the chunk geometry shared by the three batched entry points: stride in [1, seg] (every sample is covered), N = ceil(L / stride)
+// the chunk geometry shared by the batched entry points: stride in [1, seg] (every sample is covered), N = ceil(L / stride)
 static inline bool chunk_geometry_ok(int64_t L, int64_t seg, int64_t stride) { return L > 0 && seg > 0 && stride > 0 && stride <= seg; }
-
-extern "C" int fqss_chunk_gather(const float* mix, float* out, int64_t L, int64_t seg, int64_t stride, int64_t k0, int G, fqss_stream_t stream) {
-    FQSS_REQUIRE(mix && out, "null pointer");
-    FQSS_REQUIRE(chunk_geometry_ok(L, seg, stride) && G > 0 && G <= 65535 && k0 >= 0 && k0 < cdiv(L, stride),
-                 "bad shape (1 <= stride <= seg, 0 <= k0 < ceil(L / stride), 1 <= G <= 65535)");
-    int64_t gx = cdiv(seg, 1024);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(k_chunk_gather, dim3((unsigned)gx, (unsigned)G), dim3(256), 0, (hipStream_t)stream, mix, out, L, seg, stride, k0,
-                       cdiv(L, stride));
-    return launch_status("fqss_chunk_gather");
-}
 
 extern "C" int fqss_sisnr_chunks(const float* est, const float* ref, float* db, int* map, int G, int S, int64_t seg, int64_t stride, int64_t k0,
                                  int64_t L, int64_t ld_r, fqss_stream_t stream) {
@@ -205,14 +189,14 @@ extern "C" int fqss_sisnr_chunks(const float* est, const float* ref, float* db, 
     return launch_status("fqss_sisnr_chunks");
 }
 
-extern "C" int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S, int C, int64_t L, int64_t seg, int64_t stride,
-                                     int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream) {
+extern "C" int fqss_infer_ola_chunks(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L, int64_t seg,
+                                     int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream) {
     FQSS_REQUIRE(chunks && out, "null pointer");
-    FQSS_REQUIRE(S > 0 && C > 0 && S * C <= 65535 && chunk_geometry_ok(L, seg, stride) && ld_chunk >= seg && ld_out >= L,
+    FQSS_REQUIRE(S > 0 && C > 0 && (int64_t)S * C <= 65535 && chunk_geometry_ok(L, seg, stride) && ld_chunk >= seg && ld_out >= L,
                  "bad shape (1 <= stride <= seg, ld_chunk >= seg, ld_out >= L)");
     int64_t gx = cdiv(L, 1024);
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(k_infer_ola_chunks, dim3((unsigned)gx, (unsigned)(S * C)), dim3(256), 0, (hipStream_t)stream, chunks, map, out, S, C, L,
-                       seg, stride, cdiv(L, stride), ld_chunk, ld_out);
+    hipLaunchKernelGGL(k_infer_ola_chunks, dim3((unsigned)gx, (unsigned)(S * C)), dim3(256), 0, (hipStream_t)stream, chunks, map, stats, out, S,
+                       C, L, seg, stride, cdiv(L, stride), ld_chunk, ld_out);
     return launch_status("fqss_infer_ola_chunks");
 }

@@ -1,6 +1,7 @@
 // track_eval.hip -- whole-track evaluation of the HTDemucs recipe on the device (val.py:95-131 of the reference, `val_musdbhq_NSDR`;
 // calc_nsdr of its process.py:70-75): the statistics the track is normalised by, the multi-channel chunk batches, the per-item
-// normalize=False splitter of a batch, the overlap-add with the de-normalisation in its store, and the nSDR.  Statements: include/fqss.h.
+// normalize=False splitter of a batch, and the nSDR (the overlap-add with the de-normalisation in its store: fqss_infer_ola_chunks,
+// infer.hip).  Statements: include/fqss.h.
 //
 // How the sums are formed (fqss_track_stats, fqss_nsdr): a tile is FQSS_TRACK_TILE = 4096 samples = 256 lanes x 4 visits x 4 consecutive
 // samples.  A lane adds its 16 samples in fp64 in (visit, sample) order, the workgroup adds its lanes on the fixed DPP tree
@@ -126,22 +127,6 @@ __global__ __launch_bounds__(256) void k_splitter2_raw_rows(const float* __restr
     }
 }
 
-// ---- fqss_infer_ola_chunks_affine ----
-// k_infer_ola_chunks (infer.hip) through the same ola_chunks_sample, the de-normalisation in the store: v * std + mean, a
-// multiplication and an addition (contraction is off)
-__global__ __launch_bounds__(256) void k_infer_ola_chunks_affine(const float* __restrict__ chunks, const int* __restrict__ map,
-                                                                  const float* __restrict__ stats, float* __restrict__ out, int S, int C, int64_t L,
-                                                                  int64_t seg, int64_t stride, int64_t N, int64_t ld_chunk, int64_t ld_out) {
-    const int dc = blockIdx.y, d = dc / C, c = dc % C;
-    const bool affine = stats != nullptr;
-    const float mean = affine ? stats[0] : 0.0f, sd = affine ? stats[1] : 1.0f;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < L; t += (int64_t)gridDim.x * 256) {
-        float v = ola_chunks_sample(chunks, map, S, C, d, c, t, seg, stride, N, ld_chunk);
-        if (affine) v = v * sd + mean;
-        out[((int64_t)d * C + c) * ld_out + t] = v;
-    }
-}
-
 // ---- fqss_nsdr ----
 // grid (tiles, P): ws[p][0][tile] = sum ref^2, ws[p][1][tile] = sum (ref - est)^2 over the tile, everything in fp64
 template <bool VEC>
@@ -232,18 +217,6 @@ extern "C" int fqss_splitter2_raw_rows(const float* x, float* out, int B, int64_
     hipLaunchKernelGGL(k_rows_absmax, grid, dim3(256), 0, (hipStream_t)stream, x, B, N, row_max);
     hipLaunchKernelGGL(k_splitter2_raw_rows, grid, dim3(256), 0, (hipStream_t)stream, x, out, B, N, row_max);
     return launch_status("fqss_splitter2_raw_rows");
-}
-
-extern "C" int fqss_infer_ola_chunks_affine(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L,
-                                            int64_t seg, int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream) {
-    FQSS_REQUIRE(chunks && out, "null pointer");
-    FQSS_REQUIRE(S > 0 && C > 0 && (int64_t)S * C <= 65535 && L > 0 && seg > 0 && stride > 0 && stride <= seg && ld_chunk >= seg && ld_out >= L,
-                 "bad shape (1 <= stride <= seg, ld_chunk >= seg, ld_out >= L)");
-    int64_t gx = cdiv(L, 1024);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(k_infer_ola_chunks_affine, dim3((unsigned)gx, (unsigned)(S * C)), dim3(256), 0, (hipStream_t)stream, chunks, map, stats,
-                       out, S, C, L, seg, stride, cdiv(L, stride), ld_chunk, ld_out);
-    return launch_status("fqss_infer_ola_chunks_affine");
 }
 
 extern "C" int64_t fqss_nsdr_ws_doubles(int P, int64_t N) { return P > 0 && P <= 65535 && tiles_ok(N) ? 2 * (int64_t)P * cdiv(N, kTile) : 0; }

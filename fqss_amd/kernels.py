@@ -2897,21 +2897,6 @@ def istft_bwd(g, n_fft, hop, pad, T):
     return gz
 
 
-def hd_kd_loss(est, fest, src, weights, kd_lambda, want_grad=True):
-    """htdemucs solver loss (solver.py:333-366): est / fest / src [B, S, C, T] -> (loss [1], task [S], kd [S], w [B, S], dloss/dest)"""
-    _need_gpu(est, fest, src, weights)
-    est, fest, src = est.contiguous(), fest.contiguous(), src.contiguous()
-    B, S = est.shape[0], est.shape[1]
-    N = est.numel() // (B * S)
-    assert fest.shape == est.shape and src.shape == est.shape and weights.numel() == S
-    sums = torch.zeros(B * S * 5, device=est.device, dtype=torch.float64)
-    out = torch.empty(1 + 2 * S + B * S, device=est.device, dtype=torch.float32)
-    coef = torch.empty(B * S * 2, device=est.device, dtype=torch.float32)
-    g = torch.empty_like(est) if want_grad else None
-    _lib.call("fqss_hd_kd_loss", _p(est), _p(fest), _p(src), _p(weights), _p(sums), _p(out), _p(coef), _p(g), B, S, N, float(kd_lambda), _stream())
-    return out[:1], out[1:1 + S], out[1 + S:1 + 2 * S], out[1 + 2 * S:].view(B, S), g
-
-
 HD_LOSS_KINDS = {"l1": 0, "mse": 1}
 HdLoss = collections.namedtuple("HdLoss", "loss reco nsdr loss_s reco_s nsdr_s kd_s w gest")
 
@@ -3037,15 +3022,6 @@ def infer_normalize(out, sum_weight):
     _lib.call("fqss_infer_normalize", _p(out), _p(sum_weight), out.numel() // L, L, L, _stream())
 
 
-def chunk_gather(mix, seg, stride, k0, G):
-    """mix [1, L] or [L] -> [G, 1, seg]: row g = mix[(k0 + g) * stride : ... + seg], zero past L; rows past the last chunk repeat it"""
-    _need_gpu(mix)
-    assert mix.numel() == mix.shape[-1] and mix.is_contiguous(), "chunk_gather: one dense channel"
-    out = torch.empty(G, 1, seg, device=mix.device, dtype=torch.float32)
-    _lib.call("fqss_chunk_gather", _p(mix), _p(out), mix.shape[-1], seg, stride, k0, G, _stream())
-    return out
-
-
 def sisnr_chunks(est, ref, stride, k0, db=None, mp=None):
     """est [G, S, seg] (chunks k0 .. k0 + G - 1 of the model's output), ref [S, L] (the whole target) -> per-chunk SI-SNR matrices
     [G, S, S] and swap_channel_order maps [G, S, 2]; `mp`: a dense [G, S, 2] int32 slice to fill (the utterance's map table)"""
@@ -3066,7 +3042,7 @@ def sisnr_chunks(est, ref, stride, k0, db=None, mp=None):
 def infer_ola_chunks(chunks, mp, length, stride, stats=None):
     """chunks [N.., S, (C,) seg] (at least ceil(length / stride) chunks), mp [N.., S, 2] int32 or None -> [S, (C,) length]: the
     triangular overlap-add of infer_ola over every chunk in order and infer_normalize, bit for bit, in one launch.  stats (track_stats'
-    (mean, std) on the device): every sample leaves as v * std + mean (fqss_infer_ola_chunks_affine)"""
+    (mean, std) on the device): every sample leaves as v * std + mean"""
     _need_gpu(chunks, stats)
     S, seg = chunks.shape[1], chunks.shape[-1]
     C = chunks.shape[2] if chunks.dim() == 4 else 1
@@ -3074,11 +3050,8 @@ def infer_ola_chunks(chunks, mp, length, stride, stats=None):
     assert chunks.is_contiguous() and chunks.shape[0] >= n_chunks, "infer_ola_chunks: dense chunks, one per hop"
     assert mp is None or (mp.is_contiguous() and mp.dtype == torch.int32 and mp.shape[0] >= n_chunks and tuple(mp.shape[1:]) == (S, 2))
     out = torch.empty((S, C, length) if chunks.dim() == 4 else (S, length), device=chunks.device, dtype=torch.float32)
-    if stats is None:
-        _lib.call("fqss_infer_ola_chunks", _p(chunks), _p(mp), _p(out), S, C, length, seg, stride, seg, length, _stream())
-    else:
-        assert stats.numel() == 2 and stats.is_contiguous(), "infer_ola_chunks: stats is (mean, std)"
-        _lib.call("fqss_infer_ola_chunks_affine", _p(chunks), _p(mp), _p(stats), _p(out), S, C, length, seg, stride, seg, length, _stream())
+    assert stats is None or (stats.numel() == 2 and stats.is_contiguous()), "infer_ola_chunks: stats is (mean, std)"
+    _lib.call("fqss_infer_ola_chunks", _p(chunks), _p(mp), _p(stats), _p(out), S, C, length, seg, stride, seg, length, _stream())
     return out
 
 

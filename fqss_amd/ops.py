@@ -1306,10 +1306,10 @@ class HdKDLoss(Function):
 
     @staticmethod
     def forward(ctx, est, fest, src, weights, kd_lambda):
-        loss, task, kd, w, g = K.hd_kd_loss(est, fest, src, weights, kd_lambda, want_grad=True)
-        ctx.save_for_backward(g)
-        ctx.mark_non_differentiable(task, kd, w)
-        return loss.reshape(()), task, kd, w
+        r = K.hd_loss_x(est, fest, src, weights, kd_lambda, kind="l1", want_grad=True)
+        ctx.save_for_backward(r.gest)
+        ctx.mark_non_differentiable(r.reco_s, r.kd_s, r.w)
+        return r.loss.reshape(()), r.reco_s, r.kd_s, r.w      # reco_s: the task term alone
 
     @staticmethod
     def backward(ctx, gl, *_):

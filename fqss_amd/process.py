@@ -79,8 +79,8 @@ def swap_channel_order(sep_tensor, clean_tensor):
 def _model_infer_batched(model, mix, num_srcs, segment, overlap, target, chunk_batch, stats=None):
     """the chunks of one utterance through the model `chunk_batch` at a time: what the chunk-by-chunk loop of `model_infer` computes
     (per-chunk splitter threshold, per-chunk re-ordering, the same overlap-add in the same order) in ceil(N / G) forwards instead of N;
-    nothing is read back to the host.  Multi-channel mixtures (no target; the model declares `audio_channels`) go through
-    fqss_chunk_gather_mc and the forward runs under ops.split_per_item("items"); `stats` ((mean, std) on the device,
+    nothing is read back to the host.  Multi-channel mixtures (no target; the model declares `audio_channels`) run the forward under
+    ops.split_per_item("items"); `stats` ((mean, std) on the device,
     kernels.track_stats) normalises the chunks in the gather and de-normalises the result in the overlap-add's store."""
     G = int(chunk_batch)
     if G < 1:
@@ -94,9 +94,6 @@ def _model_infer_batched(model, mix, num_srcs, segment, overlap, target, chunk_b
     stride = int((1 - overlap) * segment)
     if not 1 <= stride <= segment:
         raise ValueError(f"chunk_batch needs 1 <= int((1 - overlap) * segment) <= segment, got a hop of {stride}")
-    multi = channels > 1 or stats is not None
-    if not multi:
-        mix = mix.contiguous()
     n_chunks = len(range(0, length, stride))
     n_pad = -(-n_chunks // G) * G
     want_map = target is not None and num_srcs > 1
@@ -105,7 +102,7 @@ def _model_infer_batched(model, mix, num_srcs, segment, overlap, target, chunk_b
     shape = (num_srcs, channels) if channels > 1 else (num_srcs,)
     buf = None
     for k0 in range(0, n_chunks, G):
-        chunks = K.chunk_gather_mc(mix, segment, stride, k0, G, stats=stats) if multi else K.chunk_gather(mix, segment, stride, k0, G)
+        chunks = K.chunk_gather_mc(mix, segment, stride, k0, G, stats=stats)
         with torch.no_grad(), ops.split_per_item("items" if channels > 1 else True):
             y = model(chunks).detach()
         y = y.reshape(G, *shape, y.shape[-1])

@@ -516,8 +516,7 @@ class KDTrainStep:
         (solver.py:333-366: L1 task + SDR-weighted L1 distillation, per-source weights).  clip <= 0: no clipping (htdemucs.yaml:84).
         loss_kind ("l1_sdr" only): "l1" | "mse", the solver's optim.loss.  "mse" has no distillation term (solver.py:364-368): the step
         keeps no teacher whatever fmodel and kd_lambda say.  fmodel=None: a teacher-free step (kd_lambda must be 0) -- no teacher is
-        held and no teacher forward runs, eagerly or in the captured graphs; its l1_sdr loss node is fqss_hd_loss_x, as is mse's.  With
-        a teacher and l1 the loss node stays fqss_hd_kd_loss.
+        held and no teacher forward runs, eagerly or in the captured graphs.  Every l1_sdr loss node is fqss_hd_loss_x.
         batched_quantizers=False keeps every quantizer on its own launches (no QuantTables / codes-only dataflow);
         fast=False: quantizing layers also write their fp32 outputs (no carriers); coded=False: no layer output carries codes,
         every layer runs its un-fused fp32 kernels (the reference dataflow the tests pin the fused step against).
@@ -927,18 +926,17 @@ class KDTrainStep:
         if self.loss_kind == "l1_sdr":
             if self.source_weights is None:
                 self.source_weights = torch.ones(tgt.shape[1], device=tgt.device)
-        if self.loss_kind == "l1_sdr" and teacher_free:
-            # mse (solver.py:364-368) or l1 without the distillation term: the loss family's entry point, nSDR beside the loss
-            r = K.hd_loss_x(est.detach(), None, tgt, self.source_weights, 0.0, kind=self.hd_kind, want_grad=True)
+        if self.loss_kind == "l1_sdr":
+            # l1 with the teacher's distillation term, l1 without it, or mse (solver.py:333-368): one entry point, nSDR beside the loss
+            lam = 0.0 if teacher_free else self.kd_lambda
+            r = K.hd_loss_x(est.detach(), fest, tgt, self.source_weights, lam, kind=self.hd_kind, want_grad=True)
             gest = r.gest
-            if self.grad_at is not None:
-                gest = K.hd_loss_x(self.grad_at, None, tgt, self.source_weights, 0.0, kind=self.hd_kind, want_grad=True).gest
-            res = dict(loss=r.loss, task=r.loss_s, kd=r.kd_s, w=r.w, reco=r.reco, nsdr=r.nsdr, nsdr_s=r.nsdr_s, gnorm=a.gnorm, est=est.detach())
-        elif self.loss_kind == "l1_sdr":
-            loss, task, kd, w, gest = K.hd_kd_loss(est.detach(), fest, tgt, self.source_weights, self.kd_lambda, want_grad=True)
             if self.grad_at is not None:       # tests: dloss/dest taken at a given output (the L1 loss has a sign gradient)
-                gest = K.hd_kd_loss(self.grad_at, fest, tgt, self.source_weights, self.kd_lambda, want_grad=True)[4]
-            res = dict(loss=loss, task=task, kd=kd, w=w, gnorm=a.gnorm, est=est.detach())
+                gest = K.hd_loss_x(self.grad_at, fest, tgt, self.source_weights, lam, kind=self.hd_kind, want_grad=True).gest
+            # with a teacher loss_s also holds the distillation term and the kernel's reco_s is the L1 term alone: `task` is that term,
+            # and `reco` the solver's (solver.py:363: the loss itself)
+            task, reco = (r.loss_s, r.reco) if teacher_free else (r.reco_s, r.loss)
+            res = dict(loss=r.loss, task=task, kd=r.kd_s, w=r.w, reco=reco, nsdr=r.nsdr, nsdr_s=r.nsdr_s, gnorm=a.gnorm, est=est.detach())
         elif teacher_free:
             # mysystem.py:153-156: PITLossWrapper(pairwise_neg_sisdr) on the student alone
             out, sisdr, gest = K.pit_sisdr_loss(est.detach(), tgt, want_grad=True)

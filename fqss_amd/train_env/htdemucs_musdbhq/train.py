@@ -183,9 +183,8 @@ class Solver:
             if train:
                 self.step.maybe_capture(mix, sources)
                 r = self.step(mix, sources)
-                # a teacher-free step returns the solver's `reco` (mse: the mean root, solver.py:367-368); the L1 + teacher step logs
-                # its loss under both names, as it always has
-                tot[:2] += torch.cat([r["loss"], r.get("reco", r["loss"])]).double()
+                # the solver's `reco` (solver.py:363-368): the loss itself for l1, the mean root for mse
+                tot[:2] += torch.cat([r["loss"], r["reco"]]).double()
             else:
                 with torch.no_grad():
                     est = self.model(mix)

@@ -1200,18 +1200,14 @@ int fqss_istft_bwd(const float* g, float* gz, const float* win, const float* env
                    int64_t ld_g, int N, int hop, int T, int pad, fqss_stream_t stream);
 int fqss_transpose2d(const float* x, float* y, int64_t batch, int64_t R, int64_t C, fqss_stream_t stream);
 
-/* Training loss of the htdemucs environment (csrc/hd_loss.hip; solver.py:333-366 with demucs' new_sdr): L1 task loss + SDR-weighted
- * L1 distillation loss per source, source weights wt [S].  est / fest / src [B][S][N] dense.  sums: B*S*5 doubles zeroed by the
- * caller; out: [loss, task_s.., kd_s.., w_bs..] = 1 + 2S + B*S floats; coef: B*S*2 floats of scratch; gest (optional) = dloss/dest. */
-int fqss_hd_kd_loss(const float* est, const float* fest, const float* src, const float* wt, double* sums, float* out, float* coef,
-                    float* gest, int B, int S, int64_t N, float kd_lambda, fqss_stream_t stream);
-
-/* The loss family around it (csrc/hd_loss.hip; solver.py:333-390): l1 or mse, with or without a teacher, and the nSDR the solver's
- * validation logs, from one pass.  est / src (/ fest) [B][S][N] dense, N = channels * samples; wt [S].  Per item (b, s), in fp64 (the
- * differences are formed in fp64, i.e. exactly): A = sum |est - src|, Q = sum (est - src)^2, P = sum src^2, and with a teacher
- * K = sum |est - fest|, F = sum (src - fest)^2.
- *   kind 0 (l1), fest given: fqss_hd_kd_loss' statement -- task_s = mean_b A / N, w_bs = exp((sdr(src, fest) - sdr(src, est)) / 10) by
- *     its fp32 operation sequence, kd_s = mean_b w_bs K / N, loss_s = (1 - lambda) task_s + lambda kd_s, reco_s = task_s.
+/* Losses of the htdemucs environment (csrc/hd_loss.hip; solver.py:333-390 with demucs' new_sdr): l1 or mse, with or without a teacher,
+ * and the nSDR the solver's validation logs, from one pass.  est / src (/ fest) [B][S][N] dense, N = channels * samples; source
+ * weights wt [S].  Per item (b, s), in fp64 (the differences are formed in fp64, i.e. exactly): A = sum |est - src|,
+ * Q = sum (est - src)^2, P = sum src^2, and with a teacher K = sum |est - fest|, F = sum (src - fest)^2.
+ *   kind 0 (l1), fest given (solver.py:333-366: L1 task loss + SDR-weighted L1 distillation loss per source): task_s = mean_b A / N;
+ *     w_bs = exp((sdr(src, fest) - sdr(src, est)) / 10), detached, in fp32: sdr(src, x) = 10 * log10f((float)((P + 1e-7) / (X + 1e-7)))
+ *     with X = F or Q (the quotient in fp64, rounded once), w_bs = expf((sdr_f - sdr_q) / 10); kd_s = mean_b w_bs K / N,
+ *     loss_s = (1 - lambda) task_s + lambda kd_s, reco_s = task_s.
  *   kind 0, fest NULL (kd_lambda must be 0): loss_s = reco_s = mean_b A / N.
  *   kind 1 (mse, solver.py:364-368; fest must be NULL -- the reference has no distillation term there): loss_s = mean_b Q / N,
  *     reco_s = mean_b sqrt(Q / N).
@@ -1223,7 +1219,7 @@ int fqss_hd_kd_loss(const float* est, const float* fest, const float* src, const
  * Sums: one fp64 partial per tile of FQSS_HD_LOSS_TILE samples and item STORED into ws, added in tile order by one workgroup: no
  *   atomics, nothing for the caller to clear, the same bits on every run and stream, with 16-byte or one-sample requests alike.
  *   ws: at least fqss_hd_loss_x_ws_doubles(B, S, N, fest != NULL) doubles (0 for a shape that is refused or empty), uninitialised.
- * B * S <= 65535 as fqss_hd_kd_loss.  B = 0 or N = 0: FQSS_OK, nothing is written.  A refused call writes nothing.
+ * B * S <= 65535.  B = 0 or N = 0: FQSS_OK, nothing is written.  A refused call writes nothing.
  * Cost: not measured.  The one finishing workgroup adds B * S * (3 or 5) * ceil(N / FQSS_HD_LOSS_TILE) partials, four sums at a time,
  *   and forms a source in one thread over its B items: sized for the recipe (B * S = 16, a few hundred tiles); a serial tail near the
  *   B * S limit.                                                                                                                 */
@@ -1245,19 +1241,18 @@ int fqss_infer_normalize(float* out, const float* sum_weight, int64_t rows, int6
 /* The batched form of the chunked path (process.model_infer(chunk_batch=G)): G chunks of one utterance go through the model as one
  * batch.  Chunk k covers samples [k * stride, k * stride + seg) of the L-sample utterance, 1 <= stride <= seg; there are
  * N = ceil(L / stride) chunks and chunk k holds n_k = min(seg, L - k * stride) samples.  No floating-point atomics: every result is
- * the same bits from run to run.
- *  fqss_chunk_gather      mix [L] -> out [G][seg]: row g = chunk k0 + g, zero past L; rows past chunk N - 1 repeat chunk N - 1.
+ * the same bits from run to run.  The chunk batches themselves are cut by fqss_chunk_gather_mc (track evaluation, below).
  *  fqss_sisnr_chunks      est [G][S][seg] (dense), ref [S][L] (row stride ld_r) -> db [G][S][S], map [G][S][2]: the matrix and map
  *                         of fqss_sisnr_matrix between est[g][p][:n_k] and ref[q][k * stride : k * stride + n_k], k = k0 + g
  *                         (rows past chunk N - 1 are compared as chunk N - 1); S <= 16.
  *  fqss_infer_ola_chunks  chunks [N][S][C][ld_chunk], map [N][S][2] or NULL -> out [S][C][L] (row stride ld_out) =
  *                         fqss_infer_ola over k = 0 .. N - 1 followed by fqss_infer_normalize, bit for bit, as a gather: no zeroed
- *                         output, no weight buffer.                                                                             */
-int fqss_chunk_gather(const float* mix, float* out, int64_t L, int64_t seg, int64_t stride, int64_t k0, int G, fqss_stream_t stream);
+ *                         output, no weight buffer.  stats (optional, fqss_track_stats' pair on the device): each sample v is then
+ *                         stored as v * std + mean (an fp32 multiplication and an fp32 addition, not fused; val.py:120).         */
 int fqss_sisnr_chunks(const float* est, const float* ref, float* db, int* map, int G, int S, int64_t seg, int64_t stride, int64_t k0,
                       int64_t L, int64_t ld_r, fqss_stream_t stream);
-int fqss_infer_ola_chunks(const float* chunks, const int* map, float* out, int S, int C, int64_t L, int64_t seg, int64_t stride,
-                          int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream);
+int fqss_infer_ola_chunks(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L, int64_t seg,
+                          int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream);
 
 /* Signal-to-distortion ratio of the evaluation side (csrc/sdr.hip; process.metric_evaluation, process.py:129-152: torchmetrics'
  * SignalDistortionRatio = fast_bss_eval's sdr, third party, restated from its published definition).  P pairs est[p][:L], ref[p][:L]
@@ -1574,7 +1569,8 @@ int fqss_tgemm_desc(const FqssTGemmDesc* d, fqss_stream_t stream);
 
 /* Track evaluation of the HTDemucs recipe (csrc/track_eval.hip; val.py:95-131 of the reference, `val_musdbhq_NSDR`, and calc_nsdr of
  * its process.py:70-75): normalise a multi-channel track by the mean / std of its channel mean, cut it into batches of chunks, run
- * the per-item normalize=False splitter on a batch, overlap-add and de-normalise the estimates, and score them -- all on the device.
+ * the per-item normalize=False splitter on a batch, overlap-add and de-normalise the estimates (fqss_infer_ola_chunks with stats,
+ * above), and score them -- all on the device.
  * fp32 in; every sum is formed in fp64 in a fixed order; no floating-point atomics: every result is the same bits from run to run.
  * "fp32 division" below is the IEEE-754 correctly rounded quotient.  A refused call returns FQSS_EINVAL and writes nothing.
  * FQSS_TRACK_TILE: samples of one tile partial of fqss_track_stats and fqss_nsdr.
@@ -1586,17 +1582,17 @@ int fqss_tgemm_desc(const FqssTGemmDesc* d, fqss_stream_t stream);
  *   partial per tile of FQSS_TRACK_TILE samples into ws, then one workgroup adds the partials in tile order.  Stated as fp64-then-round:
  *   NOT bit parity with torch's fp32 mean / std, whose summation order is not specified (it agrees to fp32 rounding noise).
  *   ws: at least fqss_track_stats_ws_doubles(L) = 2 * ceil(L / FQSS_TRACK_TILE) doubles (0 for an L that is refused), uninitialised.
- * fqss_chunk_gather_mc  mix [C][L] (row stride ld) -> out [G][C][seg]: out[g][c][t] = mix[c][(k0 + g) * stride + t] with the chunk
- *   geometry of fqss_chunk_gather (rows past chunk N - 1 repeat chunk N - 1).  stats (optional, fqss_track_stats' pair): an in-range
- *   sample v is written as (v - mean) / std, one fp32 subtraction and one fp32 division.  Samples past L are written as 0 with or
- *   without stats (the reference normalises the track and zero-pads the chunk afterwards).  stats == NULL, C = 1: fqss_chunk_gather's
- *   bits.  16-byte requests when seg, stride, ld are multiples of 4 and mix, out are 16-byte aligned; one sample per request otherwise.
+ * fqss_chunk_gather_mc  mix [C][L] (row stride ld) -> out [G][C][seg]: out[g][c][t] = mix[c][k * stride + t], k = min(k0 + g, N - 1).
+ *   Chunk k covers samples [k * stride, k * stride + seg) of the track, 1 <= stride <= seg; there are N = ceil(L / stride) chunks,
+ *   0 <= k0 < N, and rows past chunk N - 1 repeat chunk N - 1 (one [G][C][seg] shape serves every group).  stats (optional,
+ *   fqss_track_stats' pair): an in-range sample v is written as (v - mean) / std, one fp32 subtraction and one fp32 division; stats ==
+ *   NULL: v itself.  Samples past L are written as 0 with or without stats (the reference normalises the track and zero-pads the chunk
+ *   afterwards).  16-byte requests when seg, stride, ld are multiples of 4 and mix, out are 16-byte aligned; one sample per request
+ *   otherwise.  G * C <= 65535.
  * fqss_splitter2_raw_rows  fqss_splitter2_raw with one threshold per item: x [B][N] -> out [B][2][N], thr_b = max|x[b][:]|; row_max:
  *   B words zeroed by the caller, left holding the bit images of thr_b.  Row b is, bit for bit, fqss_splitter2_raw of item b alone;
  *   an all-zero item is NaN in its own row only.  (The normalised per-item form of a multi-channel item is fqss_splitter2_rows on
  *   the flattened item.)
- * fqss_infer_ola_chunks_affine  fqss_infer_ola_chunks, each sample v then stored as v * std + mean (an fp32 multiplication and an
- *   fp32 addition, not fused; val.py:120) with (mean, std) read from stats on the device.  stats == NULL: fqss_infer_ola_chunks' bits.
  * fqss_nsdr  P rows est[p][:N], ref[p][:N] (row strides ld_e, ld_r >= N) -> db[p] = 10 log10((num + 1e-7) / (den + 1e-7)) in fp64,
  *   num = sum ref^2, den = sum (ref - est)^2, the difference and both squares in fp64 (calc_nsdr; demucs' new_sdr when a row is one
  *   (batch, source) item of C * L contiguous samples).  One (num, den) partial per tile of FQSS_TRACK_TILE samples and row into ws, added
@@ -1608,8 +1604,6 @@ int fqss_track_stats(const float* x, double* ws, int64_t ws_doubles, float* stat
 int fqss_chunk_gather_mc(const float* mix, const float* stats, float* out, int C, int64_t L, int64_t ld, int64_t seg, int64_t stride,
                          int64_t k0, int G, fqss_stream_t stream);
 int fqss_splitter2_raw_rows(const float* x, float* out, int B, int64_t N, uint32_t* row_max, fqss_stream_t stream);
-int fqss_infer_ola_chunks_affine(const float* chunks, const int* map, const float* stats, float* out, int S, int C, int64_t L, int64_t seg,
-                                 int64_t stride, int64_t ld_chunk, int64_t ld_out, fqss_stream_t stream);
 int64_t fqss_nsdr_ws_doubles(int P, int64_t N);
 int fqss_nsdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t N, int64_t ld_e, int64_t ld_r,
               fqss_stream_t stream);

@@ -2,8 +2,8 @@
 
 Gates, relative to a field's largest value.  Without a teacher every field of `out` is an fp64 value rounded once to fp32 (2^-24):
 2 x 2^-24; kd_s is exactly 0, w exactly 1; the gradient is one fp32 coefficient times an exact sign or one fp32 difference: 4 x 2^-24.
-With a teacher w goes through fqss_hd_kd_loss' fp32 log10f / expf sequence, and kd_s, loss (all of it where the task term vanishes, as
-at N = 1 here) and the gradient inherit it: the bounds tests/test_gpu_norm_kernels.py records for fqss_hd_kd_loss, w 3e-6 and kd 1.4e-6,
+With a teacher w goes through the statement's fp32 log10f / expf sequence, and kd_s, loss (all of it where the task term vanishes, as
+at N = 1 here) and the gradient inherit it: the bounds tests/test_gpu_norm_kernels.py records for the l1 + teacher case, w 3e-6 and kd 1.4e-6,
 and 1.8e-6 for the gradient.  Measured on an MI355X, largest over the cases: without a teacher 4.1e-8 (fields), 7.6e-8 (mse gradient),
 3.0e-8 (l1 gradient); with one w 9.7e-7, kd_s 5.6e-7, loss 5.3e-7, gradient 5.1e-7, reco / nsdr 3.9e-8 -- the gates are 2.5 .. 3.5 x.
 The CPU backend (fp64 sums in index order): 5.0e-7, 5.6e-7, 5.3e-7, 5.1e-7."""

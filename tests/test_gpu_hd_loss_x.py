@@ -15,18 +15,6 @@ def test_hd_loss_x_against_fp64(kind, teacher, want_grad, shape):
     H.check_case(kind, teacher, shape, want_grad, "cuda")
 
 
-def test_hd_loss_x_l1_with_teacher_agrees_with_hd_kd_loss():
-    """the same statement through two summation orders, to the bounds tests/test_gpu_norm_kernels.py records for fqss_hd_kd_loss
-    (measured on an MI355X: every field and the gradient equal)"""
-    from fqss_amd import kernels as K
-    ops = H.case(4, 4, 2 * H.TILE + 1027, device="cuda")
-    x = K.hd_loss_x(*ops)
-    loss, task, kd, w, gest = K.hd_kd_loss(*ops)
-    for n, a, b, tol in (("loss", x.loss, loss, 2.5e-7), ("task", x.reco_s, task, 1.6e-7), ("kd", x.kd_s, kd, 1.4e-6), ("w", x.w, w, 3e-6),
-                         ("gest", x.gest, gest, 3.5e-6)):
-        assert H.rel_err(a, b.cpu().numpy()) <= tol, (n, H.rel_err(a, b.cpu().numpy()))
-
-
 def test_hd_loss_x_refusals():
     H.check_refusals("cuda")
 

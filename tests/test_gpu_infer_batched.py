@@ -1,5 +1,5 @@
 """The batched chunked-inference path on the GPU: `process.model_infer(chunk_batch=G)` and its four entry points (fqss_splitter2_rows,
-fqss_chunk_gather, fqss_sisnr_chunks, fqss_infer_ola_chunks) against the chunk-by-chunk path they replace -- bit for bit where the
+fqss_chunk_gather_mc, fqss_sisnr_chunks, fqss_infer_ola_chunks) against the chunk-by-chunk path they replace -- bit for bit where the
 arithmetic is the same (splitter, overlap-add, re-ordering maps), within the bounds of tests/test_infer_batched_cpu.py against the
 fp64 checkers of tests/helpers_infer_batched.py elsewhere."""
 import numpy as np
@@ -89,12 +89,16 @@ def test_sisnr_chunks_equals_per_chunk_sisnr_matrix(S):
 
 
 def test_chunk_gather_on_the_gpu():
+    """one channel through fqss_chunk_gather_mc.  (2000, 1000, 0.0): L, seg and the hop are multiples of 4, the 16-byte form; every other
+    geometry has a hop or a segment that is not, the one-sample form"""
     from fqss_amd import kernels as K
+    assert any(L % 4 == 0 and seg % 4 == 0 and H.geometry(L, seg, o)[0] % 4 == 0 for L, seg, o in H.GEOMETRIES)
+    assert any(seg % 2 == 1 or H.geometry(L, seg, o)[0] % 2 == 1 for L, seg, o in H.GEOMETRIES)
     for L, seg, overlap in H.GEOMETRIES:
         stride, N, _ = H.geometry(L, seg, overlap)
         mix = np.random.RandomState(7).randn(1, L).astype(np.float32)
         for G, k0 in ((N + 3, 0), (2, N - 1)):                         # both run past the last chunk
-            got = K.chunk_gather(T(mix).cuda(), seg, stride, k0, G)
+            got = K.chunk_gather_mc(T(mix).cuda(), seg, stride, k0, G)
             assert np.array_equal(got.cpu().numpy(), H.gather_ref(mix, seg, stride, k0, G)), (L, seg, overlap, G)
 
 
@@ -220,20 +224,20 @@ def test_refusals_on_the_gpu(tiny):
     f = torch.zeros(4096, device="cuda")
     i = torch.zeros(64, device="cuda", dtype=torch.int32)
     p, q, st = f.data_ptr(), i.data_ptr(), torch.cuda.current_stream().cuda_stream
-    bad = [("fqss_chunk_gather", (None, p, 3100, 1000, 750, 0, 2, st)),
-           ("fqss_chunk_gather", (p, p, 3100, 1000, 750, 5, 2, st)),
-           ("fqss_chunk_gather", (p, p, 3100, 1000, 1001, 0, 2, st)),
-           ("fqss_chunk_gather", (p, p, 3100, 1000, 750, 0, 0, st)),
+    bad = [("fqss_chunk_gather_mc", (None, None, p, 1, 3100, 3100, 1000, 750, 0, 2, st)),
+           ("fqss_chunk_gather_mc", (p, None, p, 1, 3100, 3100, 1000, 750, 5, 2, st)),
+           ("fqss_chunk_gather_mc", (p, None, p, 1, 3100, 3100, 1000, 1001, 0, 2, st)),
+           ("fqss_chunk_gather_mc", (p, None, p, 1, 3100, 3100, 1000, 750, 0, 0, st)),
            ("fqss_splitter2_rows", (p, p, 2, 100, None, st)),
            ("fqss_splitter2_rows", (p, p, 2, 0, q, st)),
            ("fqss_sisnr_chunks", (p, None, p, q, 2, 2, 100, 75, 0, 310, 310, st)),
            ("fqss_sisnr_chunks", (p, p, p, q, 2, 17, 100, 75, 0, 310, 310, st)),
            ("fqss_sisnr_chunks", (p, p, p, q, 2, 2, 100, 75, 0, 310, 309, st)),
            ("fqss_sisnr_chunks", (p, p, p, q, 0, 2, 100, 75, 0, 310, 310, st)),
-           ("fqss_infer_ola_chunks", (p, q, None, 2, 1, 310, 100, 75, 100, 310, st)),
-           ("fqss_infer_ola_chunks", (p, q, p, 2, 1, 310, 100, 75, 99, 310, st)),
-           ("fqss_infer_ola_chunks", (p, q, p, 2, 1, 310, 100, 0, 100, 310, st)),
-           ("fqss_infer_ola_chunks", (p, q, p, 2, 1, 310, 100, 101, 100, 310, st))]
+           ("fqss_infer_ola_chunks", (p, q, None, None, 2, 1, 310, 100, 75, 100, 310, st)),
+           ("fqss_infer_ola_chunks", (p, q, None, p, 2, 1, 310, 100, 75, 99, 310, st)),
+           ("fqss_infer_ola_chunks", (p, q, None, p, 2, 1, 310, 100, 0, 100, 310, st)),
+           ("fqss_infer_ola_chunks", (p, q, None, p, 2, 1, 310, 100, 101, 100, 310, st))]
     for name, args in bad:
         with pytest.raises(_lib.FqssError, match=name):
             _lib.call(name, *args)

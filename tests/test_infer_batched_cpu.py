@@ -1,4 +1,4 @@
-"""The batched chunked-inference path without a GPU: fqss_splitter2_rows, fqss_chunk_gather, fqss_sisnr_chunks and
+"""The batched chunked-inference path without a GPU: fqss_splitter2_rows, fqss_chunk_gather_mc, fqss_sisnr_chunks and
 fqss_infer_ola_chunks on the CPU backend (fqss_amd/csrc/cpu/libfqss_cpu.so, `_lib.set_backend("cpu")`) against NumPy, and
 `process.model_infer(chunk_batch=G)` against the oracle's chunk-by-chunk loop.
 
@@ -54,7 +54,7 @@ def test_chunk_gather_equals_slicing(cpu_backend, L, seg, overlap):
     mix = np.random.RandomState(1).randn(1, L).astype(np.float32)
     for G in (1, 2, N, N + 3):                                       # N + 3 and the last group of 2 run past the last chunk
         for k0 in range(0, N, G):
-            got = K.chunk_gather(T(mix), seg, stride, k0, G)
+            got = K.chunk_gather_mc(T(mix), seg, stride, k0, G)
             assert got.shape == (G, 1, seg) and np.array_equal(got.numpy(), H.gather_ref(mix, seg, stride, k0, G)), (G, k0)
 
 
@@ -167,21 +167,21 @@ def test_refusals(cpu_backend):
     f = torch.zeros(4096)
     i = torch.zeros(64, dtype=torch.int32)
     p, q = f.data_ptr(), i.data_ptr()
-    bad = [("fqss_chunk_gather", (None, p, 3100, 1000, 750, 0, 2, None)),
-           ("fqss_chunk_gather", (p, p, 3100, 1000, 750, 5, 2, None)),           # k0 past the last chunk
-           ("fqss_chunk_gather", (p, p, 3100, 1000, 1001, 0, 2, None)),          # hop > segment
-           ("fqss_chunk_gather", (p, p, 3100, 1000, 0, 0, 2, None)),
-           ("fqss_chunk_gather", (p, p, 3100, 1000, 750, 0, 0, None)),
+    bad = [("fqss_chunk_gather_mc", (None, None, p, 1, 3100, 3100, 1000, 750, 0, 2, None)),
+           ("fqss_chunk_gather_mc", (p, None, p, 1, 3100, 3100, 1000, 750, 5, 2, None)),           # k0 past the last chunk
+           ("fqss_chunk_gather_mc", (p, None, p, 1, 3100, 3100, 1000, 1001, 0, 2, None)),          # hop > segment
+           ("fqss_chunk_gather_mc", (p, None, p, 1, 3100, 3100, 1000, 0, 0, 2, None)),
+           ("fqss_chunk_gather_mc", (p, None, p, 1, 3100, 3100, 1000, 750, 0, 0, None)),
            ("fqss_splitter2_rows", (p, p, 2, 100, None, None)),
            ("fqss_splitter2_rows", (p, p, 0, 100, q, None)),
            ("fqss_sisnr_chunks", (p, p, p, None, 2, 2, 100, 75, 0, 310, 310, None)),
            ("fqss_sisnr_chunks", (p, p, p, q, 2, 17, 100, 75, 0, 310, 310, None)),   # S > 16
            ("fqss_sisnr_chunks", (p, p, p, q, 2, 2, 100, 75, 0, 310, 309, None)),    # ld_r < L
            ("fqss_sisnr_chunks", (p, p, p, q, 2, 2, 100, 75, 5, 310, 310, None)),
-           ("fqss_infer_ola_chunks", (None, q, p, 2, 1, 310, 100, 75, 100, 310, None)),
-           ("fqss_infer_ola_chunks", (p, q, p, 2, 1, 310, 100, 75, 99, 310, None)),  # ld_chunk < seg
-           ("fqss_infer_ola_chunks", (p, q, p, 2, 1, 310, 100, 75, 100, 309, None)),
-           ("fqss_infer_ola_chunks", (p, q, p, 2, 1, 310, 100, 101, 100, 310, None))]
+           ("fqss_infer_ola_chunks", (None, q, None, p, 2, 1, 310, 100, 75, 100, 310, None)),
+           ("fqss_infer_ola_chunks", (p, q, None, p, 2, 1, 310, 100, 75, 99, 310, None)),  # ld_chunk < seg
+           ("fqss_infer_ola_chunks", (p, q, None, p, 2, 1, 310, 100, 75, 100, 309, None)),
+           ("fqss_infer_ola_chunks", (p, q, None, p, 2, 1, 310, 100, 101, 100, 310, None))]
     for name, args in bad:
         with pytest.raises(_lib.FqssError, match=name):
             _lib.call(name, *args)

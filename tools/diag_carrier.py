@@ -17,7 +17,7 @@ with torch.no_grad():
 with ops.fast_codes(True):
     est = model(mix)
 print("est finite:", bool(torch.isfinite(est).all()))
-_, _, _, _, gest = K.hd_kd_loss(est.detach(), fest, src, torch.ones(2, device="cuda"), 0.1)
+gest = K.hd_loss_x(est.detach(), fest, src, torch.ones(2, device="cuda"), 0.1).gest
 est.backward(gest)
 bad = [k for k, p in model.named_parameters() if p.grad is not None and not bool(torch.isfinite(p.grad).all())]
 print(len(bad), "parameters with non-finite gradients")

@@ -19,8 +19,9 @@ def main():
         fest = fmodel(mix)
     est = model(mix)
     from fqss_amd import kernels as K
-    loss, task, kd, w, gest = K.hd_kd_loss(T(g["o1.est"]).cuda(), fest, src, torch.ones(2, device="cuda"), 0.1)   # teacher-forced dL/dest
-    est.backward(gest)
+    r = K.hd_loss_x(T(g["o1.est"]).cuda(), fest, src, torch.ones(2, device="cuda"), 0.1)   # teacher-forced dL/dest
+    loss = r.loss
+    est.backward(r.gest)
     print("observer step 1: loss", loss.item(), float(g["o1.loss"]), "est err", float((est.detach().cpu() - T(g["o1.est"])).abs().max()))
     rows = []
     for k, p in model.named_parameters():

@@ -2,7 +2,7 @@
 """Time of the separation of one stereo track as val.py's nSDR mode runs it (GPU box): a full-size quantized HTDemucsQ, 60 s of
 synthetic stereo at 44.1 kHz, segment 343980, overlap 0.25 (11 chunks), normalised by kernels.track_stats and scored by kernels.nsdr
 -- chunk by chunk (the normalisation as tensor operations) against chunk_batch=G (the normalisation inside fqss_chunk_gather_mc /
-fqss_infer_ola_chunks_affine).  Every variant is warmed up first; then the variants take turns, each call timed with device events,
+fqss_infer_ola_chunks).  Every variant is warmed up first; then the variants take turns, each call timed with device events,
 and the median of the repeats is reported with the quartiles.  The chunk-by-chunk path of the same run is the yardstick.
 
   python tools/track_eval_probe.py [--repeats 5] [--batches 2,4] [--seconds 60] [--out FILE.json]"""
