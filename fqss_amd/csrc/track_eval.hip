@@ -8,6 +8,10 @@
 // (block_sum), and the tile's partial goes to the workspace; one workgroup then adds the partials in tile order on the same tree.  The
 // order is a function of the shape alone -- the 16-byte and the one-sample load forms visit the same samples in the same order -- so a
 // result does not depend on alignment, grid or run.  No floating-point atomics anywhere.
+//
+// fqss_frame_sdr (the window-wise SDR of museval's default branch and its median over the track) keeps the same discipline with a window,
+// not a tile, as the unit: one workgroup per (window, source) adds all channels of its window, one workgroup per source sorts the
+// windows' values in LDS and takes the middle.
 #include "eval_dev.h"
 
 namespace fqss {
@@ -165,6 +169,100 @@ __global__ __launch_bounds__(256) void k_nsdr_finish(const double* __restrict__ 
     if (threadIdx.x == 0) db[p] = 10.0 * log10((num + 1e-7) / (den + 1e-7));
 }
 
+// ---- fqss_frame_sdr ----
+// grid (W, S): one workgroup owns window w of source s across all C channels.  A lane takes the quads tid, tid + 256, .. of the window,
+// channel after channel, and keeps num, den and the two "saw a non-zero sample" marks (0 or 1: their sums on the same tree are exact) in
+// registers.  ws[0][s][w] = num, ws[1][s][w] = den, ws[2][s][w] = (reference not silent) + 2 * (estimate not silent)
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_fsdr_windows(const float* __restrict__ est, const float* __restrict__ ref, double* __restrict__ ws,
+                                                       int C, int64_t win, int64_t hop, int64_t ld_e, int64_t ld_r, int64_t W) {
+    __shared__ double smem[4 * 4];
+    const int64_t w = blockIdx.x, s = blockIdx.y, SW = (int64_t)gridDim.y * W;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < C; ++c) {
+        const float *e = est + (s * C + c) * ld_e + w * hop, *r = ref + (s * C + c) * ld_r + w * hop;
+#pragma unroll 2
+        for (int64_t i = (int64_t)threadIdx.x * 4; i < win; i += 1024) {
+            float ve[4], vr[4];
+            load_quad<VEC>(e, i, win, ve);      // past the window: 0 and 0, which add nothing and mark nothing
+            load_quad<VEC>(r, i, win, vr);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double rr = (double)vr[q], dd = rr - (double)ve[q];
+                acc[0] += rr * rr;
+                acc[1] += dd * dd;
+                if (vr[q] != 0.0f) acc[2] = 1.0;
+                if (ve[q] != 0.0f) acc[3] = 1.0;
+            }
+        }
+    }
+    block_sum<double, 4>(acc, smem);
+    if (threadIdx.x == 0) {
+        ws[0 * SW + s * W + w] = acc[0];
+        ws[1 * SW + s * W + w] = acc[1];
+        ws[2 * SW + s * W + w] = (acc[2] > 0.0 ? 1.0 : 0.0) + (acc[3] > 0.0 ? 2.0 : 0.0);
+    }
+}
+
+// the monotone 64-bit integer image of a double: negative values with all bits flipped, the others with the sign bit set, so that
+// unsigned order is numeric order with +inf above every finite value; every NaN is the one key above +inf
+constexpr unsigned long long kFsdrNanKey = ~0ull;
+__device__ __forceinline__ unsigned long long fsdr_key(double v) {
+    if (v != v) return kFsdrNanKey;
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+__device__ __forceinline__ double fsdr_unkey(unsigned long long k) {
+    return __builtin_bit_cast(double, (k >> 63) ? (k & ~(1ull << 63)) : ~k);
+}
+
+// grid (S), 1024 threads, n keys in LDS (n: the power of two >= max(W, 1)).  Every window's validity and dB value from the workspace
+// (stored to frames when given), its key into LDS, the padding as NaN keys; a bitonic sort; then the ONE lane that sees the last
+// non-NaN key next to a NaN key (or to the end) knows K = its index + 1 and takes the middle.  No counter: the keys fill the 64 KB.
+constexpr int kFsdrThreads = 1024;
+__global__ __launch_bounds__(kFsdrThreads) void k_fsdr_median(const double* __restrict__ ws, double* __restrict__ frames,
+                                                               double* __restrict__ med, int S, int64_t W, int n) {
+    extern __shared__ unsigned long long key[];
+    const int64_t s = blockIdx.x, SW = (int64_t)S * W;
+    const double nan = __builtin_nan("");
+    for (int i = threadIdx.x; i < n; i += kFsdrThreads) {
+        unsigned long long k = kFsdrNanKey;
+        if (i < W) {
+            bool valid = true;
+            for (int t = 0; t < S; ++t) valid = valid && ws[2 * SW + t * W + i] == 3.0;
+            double v = nan;
+            if (valid) {
+                const double num = ws[s * W + i], den = ws[SW + s * W + i];
+                v = den == 0.0 ? __builtin_inf() : 10.0 * log10(num / den);
+            }
+            if (frames != nullptr) frames[s * W + i] = v;
+            k = fsdr_key(v);
+        }
+        key[i] = k;
+    }
+    __syncthreads();
+    for (int k2 = 2; k2 <= n; k2 <<= 1) {
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (n >> 1); t += kFsdrThreads) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;      // the t-th pair (i, i + j) of this round
+                const unsigned long long a = key[i], b = key[p];
+                if ((a > b) == ((i & k2) == 0)) {
+                    key[i] = b;
+                    key[p] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = threadIdx.x; i < n; i += kFsdrThreads) {
+        if (key[i] != kFsdrNanKey && (i + 1 == n || key[i + 1] == kFsdrNanKey)) {
+            const int K = i + 1;
+            med[s] = (K & 1) ? fsdr_unkey(key[K >> 1]) : 0.5 * (fsdr_unkey(key[(K >> 1) - 1]) + fsdr_unkey(key[K >> 1]));
+        }
+    }
+    if (threadIdx.x == 0 && key[0] == kFsdrNanKey) med[s] = nan;      // K = 0
+}
+
 }  // namespace fqss
 
 using namespace fqss;
@@ -234,4 +332,40 @@ extern "C" int fqss_nsdr(const float* est, const float* ref, double* ws, int64_t
         hipLaunchKernelGGL(k_nsdr_tiles<false>, grid, dim3(256), 0, (hipStream_t)stream, est, ref, ws, N, ld_e, ld_r, ntiles);
     hipLaunchKernelGGL(k_nsdr_finish, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, ws, ntiles, db);
     return launch_status("fqss_nsdr");
+}
+
+static_assert(FQSS_FSDR_MAX_WINDOWS * sizeof(unsigned long long) <= 65536 && (FQSS_FSDR_MAX_WINDOWS & (FQSS_FSDR_MAX_WINDOWS - 1)) == 0,
+              "the padded keys of one source are a power of two and fit in the 64 KB of LDS one workgroup may ask for");
+static inline bool fsdr_shape_ok(int S, int C, int64_t L, int64_t win, int64_t hop) {
+    return S >= 1 && S <= 65535 && C >= 1 && L >= 0 && win >= 1 && hop >= 1;
+}
+static inline int64_t fsdr_windows(int64_t L, int64_t win, int64_t hop) { return L >= win ? (L - win) / hop + 1 : 0; }
+
+extern "C" int64_t fqss_frame_sdr_ws_doubles(int S, int C, int64_t L, int64_t win, int64_t hop) {
+    if (!fsdr_shape_ok(S, C, L, win, hop)) return 0;
+    const int64_t W = fsdr_windows(L, win, hop);
+    return W <= FQSS_FSDR_MAX_WINDOWS ? 3 * (int64_t)S * W : 0;
+}
+
+extern "C" int fqss_frame_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* frames, double* med, int S, int C,
+                              int64_t L, int64_t win, int64_t hop, int64_t ld_e, int64_t ld_r, fqss_stream_t stream) {
+    FQSS_REQUIRE(fsdr_shape_ok(S, C, L, win, hop), "bad shape (1 <= S <= 65535, C >= 1, L >= 0, win >= 1, hop >= 1)");
+    FQSS_REQUIRE(ld_e >= L && ld_r >= L, "row stride shorter than a row (ld_e, ld_r >= L)");
+    const int64_t W = fsdr_windows(L, win, hop);
+    FQSS_REQUIRE(W <= FQSS_FSDR_MAX_WINDOWS, "more than FQSS_FSDR_MAX_WINDOWS windows");
+    FQSS_REQUIRE(ws_doubles >= fqss_frame_sdr_ws_doubles(S, C, L, win, hop), "workspace shorter than fqss_frame_sdr_ws_doubles");
+    FQSS_REQUIRE(med && (W == 0 || (est && ref && ws)), "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (W > 0) {
+        const dim3 grid((unsigned)W, (unsigned)S);
+        if (aligned16(est) && aligned16(ref) && mult4(ld_e) && mult4(ld_r) && mult4(hop))      // every window of every row starts on 16 bytes
+            hipLaunchKernelGGL(k_fsdr_windows<true>, grid, dim3(256), 0, st, est, ref, ws, C, win, hop, ld_e, ld_r, W);
+        else
+            hipLaunchKernelGGL(k_fsdr_windows<false>, grid, dim3(256), 0, st, est, ref, ws, C, win, hop, ld_e, ld_r, W);
+    }
+    int n = 1;
+    while (n < W) n <<= 1;
+    hipLaunchKernelGGL(k_fsdr_median, dim3((unsigned)S), dim3(kFsdrThreads), (size_t)n * sizeof(unsigned long long), st, ws, frames, med, S,
+                       W, n);
+    return launch_status("fqss_frame_sdr");
 }

@@ -3098,6 +3098,29 @@ def nsdr(est, ref):
     return db
 
 
+FSDR_MAX_WINDOWS, = _h("FSDR_MAX_WINDOWS")      # windows of one frame_sdr call: the sort keys of a source lie in one workgroup's LDS
+
+
+def frame_sdr(est, ref, win, hop=None):
+    """est, ref [S, C, L] (rows may be pitched), windows of `win` samples every `hop` (None: win) -> (med [S], frames [S, W]), fp64 on
+    the device: frames[s, w] = 10 log10(sum ref^2 / sum (ref - est)^2) over the window's channels, NaN where any source's reference or
+    estimate is all zero in the window, +inf where est == ref; med[s] the median of the row's non-NaN values, NaN when there is none
+    (museval's window SDR and its median over a track; fqss_frame_sdr in include/fqss.h)"""
+    _need_gpu(est, ref)
+    assert est.dim() == 3 and est.shape == ref.shape, "frame_sdr: est and ref are [sources, channels, length] of one shape"
+    S, C, L = est.shape
+    win, hop = int(win), int(win if hop is None else hop)
+    est, _, _, ld_e = as_rowmat(est)
+    ref, _, _, ld_r = as_rowmat(ref)
+    W = (L - win) // hop + 1 if win >= 1 and hop >= 1 and L >= win else 0       # a win or hop below 1 is refused by the library
+    n_ws = _lib.query("fqss_frame_sdr_ws_doubles", S, C, L, win, hop)
+    ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
+    med = torch.empty(S, device=est.device, dtype=torch.float64)
+    frames = torch.empty(S, W, device=est.device, dtype=torch.float64)
+    _lib.call("fqss_frame_sdr", _p(est), _p(ref), _p(ws), n_ws, _p(frames), _p(med), S, C, L, win, hop, ld_e, ld_r, _stream())
+    return med, frames
+
+
 # ------------------------------------------------------------------ affine form of the quantizers (csrc/export_q.hip)
 def fq_affine(x, scale, zero_point, axis, qmin, qmax, want_codes=False):
     """torch.fake_quantize_per_(tensor|channel)_affine on the device; scale [C] fp32, zero_point [C] int32 (C = 1: per tensor, axis

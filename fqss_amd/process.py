@@ -166,6 +166,13 @@ def calc_nsdr(ref, sig):
     return K.nsdr(sig.reshape(-1, sig.shape[-2] * sig.shape[-1]), ref.reshape(-1, ref.shape[-2] * ref.shape[-1])).reshape(lead)
 
 
+def calc_frame_sdr(ref, sig, win, hop=None):
+    """the SDR that museval reports for a track (third party, absent: the definition restated, fqss_frame_sdr in include/fqss.h): ref, sig
+    [S, C, L] -> (med [S], frames [S, W]) fp64 on the device; frames is 10 log10(sum ref^2 / sum (ref - sig)^2) over windows of `win`
+    samples every `hop` (None: win), NaN where any source is silent in the window; med is the row's median over its non-NaN windows."""
+    return K.frame_sdr(sig, ref, win, hop)
+
+
 def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):
     """SDR in dB between matching rows of est / ref [..., L] (torchmetrics' SignalDistortionRatio with its defaults, third party: the
     fast_bss_eval definition restated -- both signals normalised, `filter_length` lags of auto- and cross-correlation, a Toeplitz solve;

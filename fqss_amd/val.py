@@ -6,9 +6,11 @@ s1..s3; whole utterances, resampled on the device); `synthetic` evaluates seeded
 absent) is printed as nan unless `testing_cfg.stoi: true` asks for fqss_stoi, the restated definition, at the utterance's rate;
 `testing_cfg.stoi_extended: true` beside it puts the extended measure (ESTOI, fqss_stoi_x) into the same slot.
 `dataset_cfg.name: musdbhq` with `testing_cfg.NSDR: true` is the reference's `val_musdbhq_NSDR` (val.py:95-131) over folders of WAV
-stems (`val_musdbhq_nsdr` below: the `musdb` package is not needed for it); without NSDR the branch needs `museval` (absent): refused.
-`val()` returns (SI-SDR, improvement), or the nSDR tuple of the musdbhq branch; the SDR and the STOI of the run are in the printed
-result line."""
+stems (`val_musdbhq_nsdr` below: the `musdb` package is not needed for it); without NSDR the branch needs `museval` (absent): refused,
+unless `testing_cfg.frame_sdr: true` asks for museval's SDR restated -- the median over one-second windows, fqss_frame_sdr
+(`val_musdbhq_frames` below; SIR / SAR / ISR are not computed).
+`val()` returns (SI-SDR, improvement), or the nSDR / SDR tuple of the musdbhq branch; the SDR and the STOI of the run are in the
+printed result line."""
 import argparse
 import glob
 import os
@@ -119,19 +121,13 @@ def _read_stereo_wav(path, rate, channels, device):
     return torch.from_numpy(pcm.copy()).to(device).t().contiguous().float().div_(32768.0)
 
 
-def val_musdbhq_nsdr(model, testing_cfg, device):
-    """val_musdbhq_NSDR of the reference (val.py:95-131) on the device: per track, normalise the mixture by the mean / std of its
-    channel mean (fqss_track_stats), separate it chunk by chunk, de-normalise, and score every source with calc_nsdr (fqss_nsdr: one
-    launch sequence and one read-back per track).  Tracks are the sub-folders of `<test_dir>/test` when that folder exists, else of
-    `<test_dir>`; each holds mixture.wav and <source>.wav for every model.sources, 16-bit PCM at `testing_cfg.samplerate` (44100) with
-    the model's channel count.  `testing_cfg.chunk_batch: G` sends G chunks per forward with the normalisation inside the gather and
-    the overlap-add (process.model_infer(chunk_batch=G, stats=...)); absent, the chunks go one by one and both are tensor operations.
-    Prints the reference's progress lines; returns (mean over sources, per-source means..).
-    Differences from the reference: it asserts exactly 50 tracks (the MUSDB18-HQ test set) -- here an empty folder raises and any
-    other count is printed; the files are read by the `wave` module, not by `musdb` (parity with that reader is not pinned); mean and
-    std are fp64 sums rounded once, not torch's fp32 reductions."""
-    import numpy as np
-    from .process import calc_nsdr
+def _musdbhq_tracks(model, testing_cfg, device):
+    """the track walk that val_musdbhq_nsdr and val_musdbhq_frames share: per track, normalise the mixture by the mean / std of its
+    channel mean (fqss_track_stats), separate it chunk by chunk, de-normalise, read the stems.  Tracks are the sub-folders of
+    `<test_dir>/test` when that folder exists, else of `<test_dir>`; each holds mixture.wav and <source>.wav for every model.sources,
+    16-bit PCM at `testing_cfg.samplerate` (44100) with the model's channel count.  `testing_cfg.chunk_batch: G` sends G chunks per
+    forward with the normalisation inside the gather and the overlap-add (process.model_infer(chunk_batch=G, stats=...)); absent, the
+    chunks go one by one and both are tensor operations.  Yields (j, number of tracks, refs [S, C, L], separations [S, C, L])."""
     from .train_env.htdemucs_musdbhq.wav_dataset import MIXTURE, _list_tracks
     root = testing_cfg["test_dir"]
     if os.path.isdir(os.path.join(root, "test")):
@@ -143,7 +139,6 @@ def val_musdbhq_nsdr(model, testing_cfg, device):
     sources = list(model.sources)
     rate, channels = int(testing_cfg.get("samplerate", 44100)), int(getattr(model, "audio_channels", 2))
     segment, overlap, G = testing_cfg.get("segment_samples", None), testing_cfg.get("overlap", 0.25), testing_cfg.get("chunk_batch")
-    sdrs = np.zeros((len(sources), len(tracks)))
     for j, name in enumerate(tracks):
         read = lambda stem: _read_stereo_wav(os.path.join(root, name, stem + ".wav"), rate, channels, device)
         mix = read(MIXTURE)
@@ -156,12 +151,57 @@ def val_musdbhq_nsdr(model, testing_cfg, device):
         refs = torch.stack([read(src) for src in sources])
         if refs.shape != separations.shape:
             raise ValueError(f"{os.path.join(root, name)}: stems {tuple(refs.shape)}, separations {tuple(separations.shape)}")
+        yield j, len(tracks), refs, separations
+
+
+def _print_track(model, j, n_tracks, column):
+    if j % 10 == 0:
+        print("\n****** Track {}/{} ******".format(j + 1, n_tracks))
+        for src, v in zip(model.sources, column):
+            print("{}: SDR={:0.3f}".format(src, v))
+
+
+def val_musdbhq_nsdr(model, testing_cfg, device):
+    """val_musdbhq_NSDR of the reference (val.py:95-131) on the device: every source of every track of _musdbhq_tracks scored with
+    calc_nsdr (fqss_nsdr: one launch sequence and one read-back per track).
+    Prints the reference's progress lines; returns (mean over sources, per-source means..).
+    Differences from the reference: it asserts exactly 50 tracks (the MUSDB18-HQ test set) -- here an empty folder raises and any
+    other count is printed; the files are read by the `wave` module, not by `musdb` (parity with that reader is not pinned); mean and
+    std are fp64 sums rounded once, not torch's fp32 reductions."""
+    import numpy as np
+    from .process import calc_nsdr
+    sdrs = None
+    for j, n_tracks, refs, separations in _musdbhq_tracks(model, testing_cfg, device):
+        if sdrs is None:
+            sdrs = np.zeros((refs.shape[0], n_tracks))
         sdrs[:, j] = calc_nsdr(refs, separations).tolist()          # the track's one read-back
-        if j % 10 == 0:
-            print("\n****** Track {}/{} ******".format(j + 1, len(tracks)))
-            for i, src in enumerate(sources):
-                print("{}: SDR={:0.3f}".format(src, sdrs[i, j]))
+        _print_track(model, j, n_tracks, sdrs[:, j])
     sdrs = np.mean(sdrs, axis=1)
+    return (float(np.mean(sdrs)),) + tuple(float(v) for v in sdrs)
+
+
+def val_musdbhq_frames(model, testing_cfg, device):
+    """the SDR of the reference's val_musdbhq (val.py:134-181: museval.eval_mus_track per track, agg_frames_tracks_scores over them) on
+    the device, SDR only: every track of _musdbhq_tracks scored with calc_frame_sdr (fqss_frame_sdr: two launches and one read-back per
+    track) in windows of `testing_cfg.frame_win_s` seconds (1.0) every `testing_cfg.frame_hop_s` seconds (the window), each
+    int(seconds * samplerate) samples; per source the nanmedian over the tracks' medians, then the mean over sources.
+    Returns (mean over sources, per-source values..).  museval is a third-party package that is absent: the window SDR and the
+    silence rule are restated in include/fqss.h and parity with the package is not pinned; its SIR / SAR / ISR are not computed."""
+    import warnings
+    import numpy as np
+    from .process import calc_frame_sdr
+    rate = int(testing_cfg.get("samplerate", 44100))
+    win_s = float(testing_cfg.get("frame_win_s", 1.0))
+    win, hop = int(win_s * rate), int(float(testing_cfg.get("frame_hop_s", win_s)) * rate)
+    sdrs = None
+    for j, n_tracks, refs, separations in _musdbhq_tracks(model, testing_cfg, device):
+        if sdrs is None:
+            sdrs = np.zeros((refs.shape[0], n_tracks))
+        sdrs[:, j] = calc_frame_sdr(refs, separations, win, hop)[0].tolist()          # the track's one read-back
+        _print_track(model, j, n_tracks, sdrs[:, j])
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)              # a source without a valid window in any track: NaN, as museval
+        sdrs = np.nanmedian(sdrs, axis=1)
     return (float(np.mean(sdrs)),) + tuple(float(v) for v in sdrs)
 
 
@@ -186,8 +226,13 @@ def val(argv=None):
         sisnr, imp, sdr, stoi = val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "musdbhq":
         if not testing_cfg.get("NSDR", False):
+            if testing_cfg.get("frame_sdr", False):
+                res = val_musdbhq_frames(model, testing_cfg, "cuda")
+                print(",".join(["SDR={:0.2f}".format(res[0])] + ["SDR_{}={:0.2f}".format(s.upper(), v) for s, v in zip(model.sources, res[1:])]))
+                return res
             raise NotImplementedError("dataset musdbhq: val.py:134-178 scores with the third-party `museval` package (absent here); "
-                                      "testing_cfg.NSDR: true is served (val_musdbhq_nsdr)")
+                                      "testing_cfg.NSDR: true is served (val_musdbhq_nsdr), and testing_cfg.frame_sdr: true gives "
+                                      "museval's SDR restated (val_musdbhq_frames)")
         res = val_musdbhq_nsdr(model, testing_cfg, "cuda")
         # the reference's line, its SNDR_VOCALS spelling included (val.py:221)
         print(",".join(["NSDR={:0.2f}".format(res[0])] + ["{}_{}={:0.2f}".format("SNDR" if s == "vocals" else "NSDR", s.upper(), v)

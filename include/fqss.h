@@ -1608,6 +1608,41 @@ int64_t fqss_nsdr_ws_doubles(int P, int64_t N);
 int fqss_nsdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t N, int64_t ld_e, int64_t ld_r,
               fqss_stream_t stream);
 
+/* Frame-wise SDR of a track (csrc/track_eval.hip): the SDR of `museval`'s bss_eval with image criteria, window by window, and its
+ * median over the windows of the track -- the default branch of the reference's val.py:218-224 (`val_musdbhq`), SDR only.  In that
+ * decomposition e_spat + e_interf + e_artif = estimate - reference inside every window, so a window's SDR is
+ * 10 log10(sum ref^2 / sum (est - ref)^2) over all channels ("chunk SDR" of the MDX / SDX challenges).  SIR, SAR and ISR (the
+ * 512-tap distortion filters) are not computed.  `museval` is a third-party package that is absent: the equivalence is restated from
+ * its published source, THIS statement is the definition, and parity with the package itself is not pinned.
+ *
+ * fqss_frame_sdr  est, ref [S][C] rows of L fp32 samples (row s * C + c, row strides ld_e, ld_r >= L) -> frames [S][W] (optional) and
+ *   med [S], fp64.
+ *   Windows: W = L >= win ? (L - win) / hop + 1 : 0; window w is the samples [w * hop, w * hop + win) of every channel, a tail shorter
+ *   than a window is dropped, hop may be smaller or larger than win.
+ *   Sums: num[s][w] = sum_c sum_t ref^2, den[s][w] = sum_c sum_t (ref - est)^2, the difference and both squares in fp64.  No epsilon is
+ *   added (fqss_nsdr adds 1e-7 to both; this is museval's form).
+ *   Silence: silent_ref[s][w] when EVERY reference sample of the window, in every channel, equals 0; silent_est[s][w] the same of the
+ *   estimate.  valid[w] when no source has a silent reference or a silent estimate in w: one silent stem voids the window for all
+ *   sources, as museval does.  museval tests the sum over the channels against 0 where this tests every sample: the two differ only
+ *   for exactly anti-phase channels.
+ *   Frames: frames[s][w] = valid[w] ? (den == 0 ? +inf : 10 log10(num / den)) : NaN.
+ *   Median: med[s] = the median of frames[s][w] over the valid windows: sorted ascending with +inf last; of K values the middle one
+ *   when K is odd, 0.5 * (a + b) of the two middle ones when K is even, NaN when K = 0 (W = 0 included).  A NaN in a valid window
+ *   (a NaN sample) is left out of the median as an invalid window is.
+ *   Order: no atomics; the order of every sum is a function of (C, win, hop) alone -- a lane of the window's workgroup adds quads
+ *   tid, tid + 256, .. of channel 0, then of channel 1, ..; the lanes on the fixed DPP tree, the four waves in wave order -- and the
+ *   16-byte and the one-sample load forms visit the same samples in the same order, so alignment, strides, grid and stream do not
+ *   change a bit of the result (as fqss_nsdr).  The 16-byte form is taken when est, ref are 16-byte aligned and ld_e, ld_r, hop are
+ *   multiples of 4.
+ *   ws: at least fqss_frame_sdr_ws_doubles(S, C, L, win, hop) = 3 * S * W doubles (0 for arguments that are refused), uninitialised.
+ *   Refused (FQSS_EINVAL, the cause in fqss_last_error, nothing launched): S < 1, S > 65535, C < 1, win < 1 or hop < 1; ld < L;
+ *   W > FQSS_FSDR_MAX_WINDOWS (the sort keys of one source, padded to a power of two, lie in the LDS of one workgroup: 8192 x 8 bytes
+ *   = 64 KB); a workspace shorter than fqss_frame_sdr_ws_doubles. */
+#define FQSS_FSDR_MAX_WINDOWS 8192
+int64_t fqss_frame_sdr_ws_doubles(int S, int C, int64_t L, int64_t win, int64_t hop);
+int fqss_frame_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* frames, double* med, int S, int C,
+                   int64_t L, int64_t win, int64_t hop, int64_t ld_e, int64_t ld_r, fqss_stream_t stream);
+
 
 #ifdef __cplusplus
 }
