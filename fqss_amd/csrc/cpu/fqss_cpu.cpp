@@ -2,7 +2,7 @@
 // batch 2, 1 s ... plumbing, no GPU"; reference train.py:31: device = "cpu" if use_cpu).  Plain C++ (g++, OpenMP), host pointers, the
 // `stream` argument is ignored, every call is synchronous.  It serves the entry points the UN-FUSED ConvTasNet QAT step uses (the
 // per-layer kernels that the G1 layer fixtures pin: KDTrainStep(coded=False, batched_quantizers=False) with the module-path teacher)
-// and, of the evaluation side, the SDR (fqss_sdr), the STOI (fqss_stoi) and the batched chunked path (fqss_splitter2_rows, fqss_chunk_gather_mc,
+// and, of the evaluation side, the SDR (fqss_sdr), BSS-eval's SDR / SIR / SAR (fqss_bss_eval), the STOI (fqss_stoi) and the batched chunked path (fqss_splitter2_rows, fqss_chunk_gather_mc,
 // fqss_sisnr_chunks, fqss_infer_ola_chunks);
 // anything else is absent from this library and fqss_amd/_lib.py raises.  Arithmetic: the same op sequences as the HIP kernels
 // (fp32, one IEEE operation per operator: built with -ffp-contract=off; IEEE division; round-half-even), reductions in fp64.
@@ -1273,6 +1273,116 @@ int fqss_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles,
         double coh = 0.0;
         for (int i = 0; i < F; ++i) coh += b[i] * x[i];
         db[p] = (ok && std::isfinite(coh)) ? 10.0 * log10(coh / (1.0 - coh)) : (double)NAN;
+    }
+    return FQSS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ BSS-eval SDR / SIR / SAR
+// include/fqss.h, fqss_bss_eval: the definition in straight fp64 loops (signals centred and normalised first, direct lag sums, the
+// recursion of fqss_sdr above for E_tgt, a plain unblocked Cholesky and forward substitutions for E_all); the workspace has the HIP
+// library's size rule and is not used
+int64_t fqss_bss_eval_ws_doubles(int S, int64_t L, int filter_length) {
+    if (S < 1 || S > 3 || L < 1 || filter_length < 1 || filter_length > 512) return 0;
+    const int64_t T = filter_length, n = S * T;
+    return ((L + 511) / 512) * (2 * S * S * T + 4 * S) + 2 * S * S * T + 16 + (n + S) * n;
+}
+
+static double bss_ratio_db(double num, double den) { return (den <= 0.0 && num > 0.0) ? (double)INFINITY : 10.0 * log10(num / den); }
+
+int fqss_bss_eval(const float* est, const float* ref, const int* tgt, double* ws, int64_t ws_doubles, double* out, int S, int64_t L,
+                  int64_t ld_e, int64_t ld_r, int filter_length, int zero_mean, double load_diag, fqss_stream_t) {
+    REQUIRE(est && ref && ws && out, "null pointer");
+    REQUIRE(S >= 1 && S <= 3 && L >= 1 && ld_e >= L && ld_r >= L, "bad shape (1 <= S <= 3, L >= 1, ld >= L)");
+    REQUIRE(filter_length >= 1 && filter_length <= 512, "filter_length outside 1..512");
+    REQUIRE(ws_doubles >= fqss_bss_eval_ws_doubles(S, L, filter_length), "workspace shorter than fqss_bss_eval_ws_doubles");
+    const int T = filter_length, n = S * T;
+    const double load = load_diag >= 0.0 ? load_diag : 0.0;      // (a negative or NaN load_diag: none)
+    std::vector<std::vector<double>> x(2 * S, std::vector<double>(L));      // targets, then estimates
+    std::vector<double> Ee(S, 0.0);
+    for (int m = 0; m < 2 * S; ++m) {
+        const float* src = m < S ? ref + m * ld_r : est + (m - S) * ld_e;
+        double s = 0.0, ss = 0.0;
+        for (int64_t i = 0; i < L; ++i) s += (x[m][i] = src[i]);
+        const double mean = zero_mean ? s / (double)L : 0.0;
+        for (int64_t i = 0; i < L; ++i) {
+            x[m][i] -= mean;
+            ss += x[m][i] * x[m][i];
+        }
+        const double nrm = fmax(sqrt(ss), 1e-6);
+        for (int64_t i = 0; i < L; ++i) x[m][i] /= nrm;
+        if (m >= S) Ee[m - S] = ss / (nrm * nrm);
+    }
+    // c[i][m][a] = sum_t ref_i[t] x_m[t + a]
+    std::vector<double> c((size_t)S * 2 * S * T, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int q = 0; q < S * 2 * S * T; ++q) {
+        const int i = q / (2 * S * T), m = (q / T) % (2 * S), a = q % T;
+        double v = 0.0;
+        for (int64_t t = 0; t + a < L; ++t) v += x[i][t] * x[m][t + a];
+        c[q] = v;
+    }
+    auto A = [&](int i, int k, int lag) { return lag >= 0 ? c[((size_t)i * 2 * S + k) * T + lag] : c[((size_t)k * 2 * S + i) * T - lag]; };
+    auto B = [&](int i, int j, int a) { return c[((size_t)i * 2 * S + S + j) * T + a]; };
+    // the lower triangle of G, factored in place; a non-positive pivot makes every result NaN
+    bool spd = true;
+    std::vector<double> G(S > 1 ? (size_t)n * n : 0);
+    if (S > 1) {
+        for (int r = 0; r < n; ++r)
+            for (int cc = 0; cc <= r; ++cc) G[(size_t)r * n + cc] = A(r / T, cc / T, r % T - cc % T) + (r == cc ? load : 0.0);
+        for (int j = 0; j < n; ++j) {
+            double p = G[(size_t)j * n + j];
+            for (int k = 0; k < j; ++k) p -= G[(size_t)j * n + k] * G[(size_t)j * n + k];
+            spd = spd && p > 0.0;
+            const double d = sqrt(p);
+            G[(size_t)j * n + j] = d;
+#pragma omp parallel for schedule(static)
+            for (int r = j + 1; r < n; ++r) {
+                double v = G[(size_t)r * n + j];
+                for (int k = 0; k < j; ++k) v -= G[(size_t)r * n + k] * G[(size_t)j * n + k];
+                G[(size_t)r * n + j] = v / d;
+            }
+        }
+    }
+    for (int j = 0; j < S; ++j) {
+        int q = tgt ? tgt[j] : j;
+        q = q < 0 ? 0 : (q >= S ? S - 1 : q);
+        // E_tgt: Levinson-Durbin on r = A_qq, b = B_qj
+        std::vector<double> a(T, 0.0), an(T, 0.0), sol(T, 0.0);
+        double E = A(q, q, 0) + load;
+        bool ok = E > 0.0;
+        a[0] = 1.0;
+        sol[0] = B(q, j, 0) / E;
+        for (int m = 1; m < T; ++m) {
+            double acc = 0.0, qq = 0.0;
+            for (int i = 0; i < m; ++i) {
+                acc += a[i] * A(q, q, m - i);
+                qq += sol[i] * A(q, q, m - i);
+            }
+            const double k = -acc / E;
+            E = E * (1.0 - k * k);
+            ok = ok && E > 0.0;
+            const double lam = (B(q, j, m) - qq) / E;
+            for (int i = 0; i <= m; ++i) an[i] = a[i] + k * a[m - i];
+            a.swap(an);
+            for (int i = 0; i <= m; ++i) sol[i] += lam * a[m - i];
+        }
+        double e_tgt = 0.0, e_all = 0.0;
+        for (int i = 0; i < T; ++i) e_tgt += B(q, j, i) * sol[i];
+        if (S > 1) {      // E_all = |L^-1 d_j|^2
+            std::vector<double> y(n);
+            for (int r = 0; r < n; ++r) {
+                double v = B(r / T, j, r % T);
+                for (int k = 0; k < r; ++k) v -= G[(size_t)r * n + k] * y[k];
+                y[r] = v / G[(size_t)r * n + r];
+                e_all += y[r] * y[r];
+            }
+        } else {
+            e_all = e_tgt;
+        }
+        ok = ok && spd && std::isfinite(e_tgt) && std::isfinite(e_all);
+        out[j] = ok ? bss_ratio_db(e_tgt, Ee[j] - e_tgt) : (double)NAN;
+        out[S + j] = ok ? bss_ratio_db(e_tgt, e_all - e_tgt) : (double)NAN;
+        out[2 * S + j] = ok ? bss_ratio_db(e_all, Ee[j] - e_all) : (double)NAN;
     }
     return FQSS_OK;
 }

@@ -164,6 +164,27 @@ int main() {
         CHECK(fqss_sdr(pe.data(), pr.data(), wsd.data(), 4096, dbv.data(), P, Ls, Ls - 1, ldp, 8, 0, -1.0, nullptr) == FQSS_EINVAL);
         CHECK(fqss_sdr_ws_doubles(P, 0, 8) == 0);
     }
+    // BSS-eval SDR / SIR / SAR: pitched rows, a permuted pairing, one source, refused arguments
+    {
+        const int S = 3, lde = 310, ldr = 305, tg[3] = {1, 2, 0};
+        const int64_t Ls = 300;
+        auto be = rnd((size_t)S * lde), br = rnd((size_t)S * ldr);
+        for (int j = 0; j < S; ++j)
+            for (int64_t i = 0; i < Ls; ++i) be[j * lde + i] = br[tg[j] * ldr + i] + 0.1f * br[j * ldr + i] + 0.05f * be[j * lde + i];
+        for (int T : {1, 7, 64}) {
+            std::vector<double> wsb((size_t)fqss_bss_eval_ws_doubles(S, Ls, T)), o(3 * S, 0.0);
+            CHECK(!wsb.empty());
+            CHECK(fqss_bss_eval(be.data(), br.data(), tg, wsb.data(), (int64_t)wsb.size(), o.data(), S, Ls, lde, ldr, T, T == 7, T == 7 ? 1e-3 : -1.0, nullptr) == 0);
+            for (int v = 0; v < 3 * S; ++v) CHECK(std::isfinite(o[v]) && o[v] > 5.0);
+            CHECK(fqss_bss_eval(be.data(), br.data(), nullptr, wsb.data(), (int64_t)wsb.size(), o.data(), 1, Ls, lde, ldr, T, 0, -1.0, nullptr) == 0);
+            CHECK(std::isfinite(o[0]) && std::isinf(o[1]) && o[0] == o[2]);
+            CHECK(fqss_bss_eval(be.data(), br.data(), tg, wsb.data(), (int64_t)wsb.size() - 1, o.data(), S, Ls, lde, ldr, T, 0, -1.0, nullptr) == FQSS_EINVAL);
+        }
+        std::vector<double> wsb(4096), o(12);
+        CHECK(fqss_bss_eval(be.data(), br.data(), tg, wsb.data(), 4096, o.data(), 4, Ls, lde, ldr, 4, 0, -1.0, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_bss_eval(be.data(), br.data(), tg, wsb.data(), 4096, o.data(), S, Ls, lde, ldr, 513, 0, -1.0, nullptr) == FQSS_EINVAL);
+        CHECK(fqss_bss_eval_ws_doubles(4, Ls, 8) == 0 && fqss_bss_eval_ws_doubles(S, Ls, 513) == 0);
+    }
     // batched chunked inference: a group that runs past the last (short) chunk, per-row splitter, per-chunk maps, gather-form overlap-add
     {
         const int64_t Lc = 310, seg = 100, hop = 75, Nc = 5;      // chunk 4 holds 10 samples

@@ -1,7 +1,8 @@
 // eval_dev.h -- per-sample device functions that more than one kernel of the evaluation side computes through, so that the kernels that
 // must agree bit for bit carry ONE operation sequence (contraction is off: every operator is one IEEE operation):
 //   the weighted overlap-add of infer.hip (k_infer_ola, k_infer_ola_chunks),
-//   the normalize=False splitter of codec.hip (k_splitter2_raw) and of track_eval.hip (k_splitter2_raw_rows).
+//   the normalize=False splitter of codec.hip (k_splitter2_raw) and of track_eval.hip (k_splitter2_raw_rows),
+//   the Levinson-Durbin recursion of sdr.hip (k_sdr_finish) and of bss_eval.hip (k_bss_tgt).
 #pragma once
 #include "fqss_dev.h"
 
@@ -66,6 +67,67 @@ __device__ __forceinline__ void split2_raw(float v, float thr, float delta, floa
     const float r = ((2.0f * (v - q0)) * thr) / delta - thr;      // process.py:35 op order
     msb = q0;
     lsb = split_clip(floorf(r / delta)) * delta;
+}
+
+// Levinson-Durbin on normalised lag sums r_s, b_s [F] in LDS (csrc/sdr.hip k_sdr_finish; csrc/bss_eval.hip k_bss_tgt): coh = b . R^-1 b
+// with R the symmetric Toeplitz matrix of r, valid in thread 0; ok: every prediction error was positive.  A 256-thread workgroup, all of
+// it in the call; a_s [2][kLevMaxF] holds (1, 0, ...) and zeros on entry and the caller has synchronised; red: 8 doubles.
+// a^(n) is the prediction polynomial of order n (a[0] = 1) with error E_n = E_(n-1) (1 - k^2); its reverse y solves R_(n+1) y = E_n e_n,
+// so the solution grows by x += (b[n] - sum_i x[i] r[n - i]) / E_n * y.  Thread j holds elements j and j + 256 of a and x in registers; a
+// is mirrored in LDS (two buffers, written for step n + 1 while step n's is read) for the reversed reads.  Per step: two dot products
+// (DPP tree inside a wave, the four wave sums through LDS, added in wave order), two updates, two barriers.
+constexpr int kLevMaxF = 512;
+__device__ __forceinline__ double levinson_coh(const double* r_s, const double* b_s, double (*a_s)[kLevMaxF], double* red, int F, bool& ok) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    double E = r_s[0];
+    ok = E > 0.0;
+    double a[2] = {tid == 0 ? 1.0 : 0.0, 0.0}, x[2] = {tid == 0 ? b_s[0] / E : 0.0, 0.0};
+    for (int m = 1; m < F; ++m) {
+        const double* ac = a_s[(m - 1) & 1];
+        double* an = a_s[m & 1];
+        double acc = 0.0, q = 0.0;
+        for (int s = 0; s < 2; ++s) {
+            const int i = tid + 256 * s;
+            if (i < m) {
+                const double rv = r_s[m - i];
+                acc = fma(a[s], rv, acc);
+                q = fma(x[s], rv, q);
+            }
+        }
+        acc = wave_sum63(acc);
+        q = wave_sum63(q);
+        if (lane == 63) {
+            red[2 * w] = acc;
+            red[2 * w + 1] = q;
+        }
+        __syncthreads();
+        acc = ((red[0] + red[2]) + red[4]) + red[6];
+        q = ((red[1] + red[3]) + red[5]) + red[7];
+        const double k = -acc / E;
+        E = E * (1.0 - k * k);
+        ok = ok && E > 0.0;
+        const double lam = (b_s[m] - q) / E;
+        for (int s = 0; s < 2; ++s) {
+            const int i = tid + 256 * s;
+            if (i <= m) {
+                const double arev = ac[m - i];
+                const double ai = fma(k, arev, a[s]);         // a^(m)[i]
+                x[s] = fma(lam, fma(k, a[s], arev), x[s]);    // + lam a^(m)[m - i]
+                a[s] = ai;
+                an[i] = ai;
+            }
+        }
+        __syncthreads();
+    }
+    double coh = 0.0;
+    for (int s = 0; s < 2; ++s) {
+        const int i = tid + 256 * s;
+        if (i < F) coh = fma(b_s[i], x[s], coh);
+    }
+    coh = wave_sum63(coh);
+    if (lane == 63) red[w] = coh;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 #endif  // __HIPCC__

@@ -7,12 +7,12 @@
 // Two kernels, all sums in fp64 (products of two fp32 values are exact there), no floating-point atomics -- the same bits every run:
 //   k_sdr_corr    grid (time tiles, pairs): the tile's share of r, b and of the four moments, stored to ws[pair][tile][2F + 4]
 //   k_sdr_finish  one workgroup per pair: tile partials summed in tile order, normalisation, Levinson-Durbin, the ratio in dB
-#include "fqss_dev.h"
+#include "eval_dev.h"
 
 namespace fqss {
 
 constexpr int kSdrTile = 1024;      // time samples per workgroup of k_sdr_corr (tests/test_gpu_sdr.py names it: TILE)
-constexpr int kSdrMaxF = 512;       // filter_length <= 512: two adjacent lags per thread of a 256-thread workgroup
+constexpr int kSdrMaxF = kLevMaxF;      // filter_length <= 512: two adjacent lags per thread of a 256-thread workgroup
 constexpr int kSdrMom = 4;          // sum t^2, sum p^2, sum t, sum p behind the 2F lag sums of a tile
 
 __host__ __device__ static inline int64_t sdr_stride(int F) { return 2 * (int64_t)F + kSdrMom; }
@@ -84,15 +84,12 @@ __device__ __forceinline__ double sdr_span_sum(const float* __restrict__ x, int6
     return s;
 }
 
-// Levinson-Durbin on the normalised lag sums.  a^(n) is the prediction polynomial of order n (a[0] = 1) with error E_n = E_(n-1) (1 - k^2);
-// its reverse y solves R_(n+1) y = E_n e_n, so the solution grows by x += (b[n] - sum_i x[i] r[n - i]) / E_n * y.  Thread j holds elements j and
-// j + 256 of a and x in registers; a is mirrored in LDS (two buffers, written for step n + 1 while step n's is read) for the reversed reads.
-// Per step: two dot products (DPP tree inside a wave, the four wave sums through LDS, added in wave order), two updates, two barriers.
+// Tile partials summed in tile order, normalisation, then the Levinson-Durbin recursion (levinson_coh, eval_dev.h) and the ratio.
 __global__ __launch_bounds__(256) void k_sdr_finish(const float* __restrict__ est, const float* __restrict__ ref, const double* __restrict__ ws,
                                                     double* __restrict__ db, int F, int64_t L, int64_t ld_e, int64_t ld_r, int64_t ntiles,
                                                     int zero_mean, double load_diag) {
     __shared__ double r_s[kSdrMaxF], b_s[kSdrMaxF], a_s[2][kSdrMaxF], red[8], mom[kSdrMom];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t p = blockIdx.x, stride = sdr_stride(F);
     const double* part = ws + p * ntiles * stride;
     const float *e = est + p * ld_e, *r = ref + p * ld_r;
@@ -142,56 +139,9 @@ __global__ __launch_bounds__(256) void k_sdr_finish(const float* __restrict__ es
         b_s[k] = bv;
     }
     __syncthreads();
-    double E = r_s[0];
-    bool ok = E > 0.0;
-    double a[2] = {tid == 0 ? 1.0 : 0.0, 0.0}, x[2] = {tid == 0 ? b_s[0] / E : 0.0, 0.0};
-    for (int m = 1; m < F; ++m) {
-        const double* ac = a_s[(m - 1) & 1];
-        double* an = a_s[m & 1];
-        double acc = 0.0, q = 0.0;
-        for (int s = 0; s < 2; ++s) {
-            const int i = tid + 256 * s;
-            if (i < m) {
-                const double rv = r_s[m - i];
-                acc = fma(a[s], rv, acc);
-                q = fma(x[s], rv, q);
-            }
-        }
-        acc = wave_sum63(acc);
-        q = wave_sum63(q);
-        if (lane == 63) {
-            red[2 * w] = acc;
-            red[2 * w + 1] = q;
-        }
-        __syncthreads();
-        acc = ((red[0] + red[2]) + red[4]) + red[6];
-        q = ((red[1] + red[3]) + red[5]) + red[7];
-        const double k = -acc / E;
-        E = E * (1.0 - k * k);
-        ok = ok && E > 0.0;
-        const double lam = (b_s[m] - q) / E;
-        for (int s = 0; s < 2; ++s) {
-            const int i = tid + 256 * s;
-            if (i <= m) {
-                const double arev = ac[m - i];
-                const double ai = fma(k, arev, a[s]);         // a^(m)[i]
-                x[s] = fma(lam, fma(k, a[s], arev), x[s]);    // + lam a^(m)[m - i]
-                a[s] = ai;
-                an[i] = ai;
-            }
-        }
-        __syncthreads();
-    }
-    double coh = 0.0;
-    for (int s = 0; s < 2; ++s) {
-        const int i = tid + 256 * s;
-        if (i < F) coh = fma(b_s[i], x[s], coh);
-    }
-    coh = wave_sum63(coh);
-    if (lane == 63) red[w] = coh;
-    __syncthreads();
+    bool ok;
+    const double coh = levinson_coh(r_s, b_s, a_s, red, F, ok);
     if (tid == 0) {
-        coh = ((red[0] + red[1]) + red[2]) + red[3];
         db[p] = (ok && isfinite(coh)) ? 10.0 * log10(coh / (1.0 - coh)) : (double)NAN;
     }
 }

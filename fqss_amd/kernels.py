@@ -2956,6 +2956,25 @@ def sdr(est, ref, filter_length=512, zero_mean=False, load_diag=None):
     return db
 
 
+def bss_eval(est, ref, tgt=None, filter_length=512, zero_mean=False, load_diag=None):
+    """est, ref [S, L] (1 <= S <= 3; rows may be pitched views), tgt: int [S] (estimate j is scored against target tgt[j]) or None for
+    the identity -> fp64 [3, S] on the device: BSS-eval's SDR, SIR and SAR in dB (mir_eval / fast_bss_eval's bss_eval_sources restated,
+    see fqss_bss_eval in include/fqss.h).  SIR is +inf at S = 1; NaN for a silent or duplicated target."""
+    _need_gpu(est, ref)
+    est, S, L, ld_e = as_rowmat(est)
+    ref, S2, L2, ld_r = as_rowmat(ref)
+    assert (S, L) == (S2, L2), "bss_eval: shape mismatch"
+    if tgt is not None:
+        tgt = torch.as_tensor(tgt).to(device=est.device, dtype=torch.int32).contiguous()
+        assert tgt.shape == (S,), "bss_eval: tgt is [S]"
+    n_ws = _lib.query("fqss_bss_eval_ws_doubles", S, L, int(filter_length))
+    ws = torch.empty(max(n_ws, 1), device=est.device, dtype=torch.float64)
+    out = torch.empty(3, S, device=est.device, dtype=torch.float64)
+    _lib.call("fqss_bss_eval", _p(est), _p(ref), _p(tgt), _p(ws), n_ws, _p(out), S, L, ld_e, ld_r, int(filter_length),
+              1 if zero_mean else 0, -1.0 if load_diag is None else float(load_diag), _stream())
+    return out
+
+
 STOI_RATES = (8000, 10000, 16000)
 _stoi_taps = {}
 

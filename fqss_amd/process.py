@@ -190,6 +190,21 @@ def stoi(est, ref, sample_rate, extended=False):
     return K.stoi(est.reshape(-1, est.shape[-1]), ref.reshape(-1, ref.shape[-1]), sample_rate, extended=extended)
 
 
+def bss_eval(est, ref, filter_length=512, zero_mean=False, load_diag=None):
+    """BSS-eval v3 (mir_eval / fast_bss_eval's bss_eval_sources, third party: the published definition restated, see fqss_bss_eval in
+    include/fqss.h) of S <= 3 estimates against S targets [S, ...]: every estimate is paired with the target of its best SI-SNR (first
+    maximum), as metric_evaluation pairs them, and the distortion left after projecting it on the `filter_length` lagged copies of that
+    target is split into interference (what the lagged copies of ALL targets explain) and artefacts (the rest).  Returns the means over
+    the estimates (SDR, SIR, SAR) in dB as one fp64 tensor [3] on the device; nothing is read back."""
+    S = ref.shape[0]
+    est, ref = est.reshape(S, -1), ref.reshape(S, -1)
+    db = K.sisnr_matrix(est, ref)
+    cols = torch.arange(S, device=db.device).expand(S, S)
+    first = torch.where(db == db.max(dim=1, keepdim=True).values, cols, S).min(dim=1).values
+    first = torch.where(first < S, first, 0)                            # (a row of NaN: index 0, as metric_evaluation)
+    return K.bss_eval(est, ref, tgt=first, filter_length=filter_length, zero_mean=zero_mean, load_diag=load_diag).mean(dim=1)
+
+
 def metric_evaluation(sep_waveform, clean_waveforms, sample_rate=16000, with_sdr=True, with_stoi=False, stoi_extended=False):
     """(SI-SNR, SDR, STOI) averaged over the sources (process.py:127-154): every estimate is paired with the target of its best SI-SNR
     (first maximum) and the metrics are taken on that pair.  The pairing stays on the device (first-maximum index + gather) and all

@@ -5,6 +5,8 @@ restated).  `dataset_cfg.name: librimix` walks `testing_cfg.test_dir` as val.py:
 s1..s3; whole utterances, resampled on the device); `synthetic` evaluates seeded two-speaker mixtures.  STOI (pystoi: third party,
 absent) is printed as nan unless `testing_cfg.stoi: true` asks for fqss_stoi, the restated definition, at the utterance's rate;
 `testing_cfg.stoi_extended: true` beside it puts the extended measure (ESTOI, fqss_stoi_x) into the same slot.
+`testing_cfg.bss_eval: true` (librimix) appends `,SIR=..,SAR=..` -- BSS-eval's interference and artefact ratios, fqss_bss_eval, the
+definition of mir_eval / fast_bss_eval restated -- to the result and progress lines; without the key the lines are what they were.
 `dataset_cfg.name: musdbhq` with `testing_cfg.NSDR: true` is the reference's `val_musdbhq_NSDR` (val.py:95-131) over folders of WAV
 stems (`val_musdbhq_nsdr` below: the `musdb` package is not needed for it); without NSDR the branch needs `museval` (absent): refused,
 unless `testing_cfg.frame_sdr: true` asks for museval's SDR restated -- the median over one-second windows, fqss_frame_sdr
@@ -20,7 +22,7 @@ import yaml
 
 from . import kernels as K
 from .data import synth_batch
-from .process import metric_evaluation, model_infer
+from .process import bss_eval, metric_evaluation, model_infer
 from .quantization.qat.models.load_model import create_pretrained_model, enable_observer
 
 
@@ -91,6 +93,7 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
 
     with_stoi, extended = bool(testing_cfg.get("stoi", False)), bool(testing_cfg.get("stoi_extended", False))
     rate = int(int(dataset_cfg.get("sample_rate", 16000)) * ratio)       # the utterance's rate after resampling (val.py:83 passes fs too)
+    with_bss, bss = bool(testing_cfg.get("bss_eval", False)), None      # BSS-eval (SDR, SIR, SAR) summed on the device
     sisdr = sisdr_imp = sdr = stoi = 0.0
     for i, (mix, clean) in enumerate(Prefetcher(_Utterances(), [[k] for k in range(n)], device, depth=1)):
         mix_wav, clean_wavs = mix[0], clean[0]
@@ -104,9 +107,13 @@ def val_librimix(model, model_cfg, dataset_cfg, testing_cfg, device):
         sisdr_imp += s - base
         sdr += d
         stoi += st
+        if with_bss:      # one more launch sequence per utterance; read back only where a line is printed
+            b = bss_eval(wavs, clean_wavs)
+            bss = b if bss is None else bss + b
         if (i % 500 == 0 and i > 0) or i == 1:
-            print("SI-SDR={:0.3f},SI-SDR-imp={:0.3f},SDR={:0.3f}".format(sisdr / (i + 1), sisdr_imp / (i + 1), sdr / (i + 1)))
-    return sisdr / n, sisdr_imp / n, sdr / n, stoi / n
+            print("SI-SDR={:0.3f},SI-SDR-imp={:0.3f},SDR={:0.3f}".format(sisdr / (i + 1), sisdr_imp / (i + 1), sdr / (i + 1))
+                  + (",SIR={:0.3f},SAR={:0.3f}".format(*(bss[1:] / (i + 1)).tolist()) if with_bss else ""))
+    return sisdr / n, sisdr_imp / n, sdr / n, stoi / n, (bss[1:] / n).tolist() if with_bss else None
 
 
 def _read_stereo_wav(path, rate, channels, device):
@@ -221,8 +228,9 @@ def val(argv=None):
         "No support for splitter/combiner with non QAT model."
     dataset_cfg, testing_cfg = conf["dataset_cfg"], conf.get("testing_cfg", {})
     if dataset_cfg["name"] == "librimix":
-        sisnr, imp, sdr, stoi = val_librimix(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
+        sisnr, imp, sdr, stoi, bss = val_librimix(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "synthetic":
+        bss = None
         sisnr, imp, sdr, stoi = val_synthetic(model, model_cfg, dataset_cfg, testing_cfg, "cuda")
     elif dataset_cfg["name"] == "musdbhq":
         if not testing_cfg.get("NSDR", False):
@@ -240,7 +248,8 @@ def val(argv=None):
         return res
     else:
         assert False, "Dataset {} is not supported!".format(dataset_cfg["name"])
-    print("SI-SDR={:0.2f},SI-SDR-imp={:0.2f},SDR={:0.2f},STOI={:0.3f}".format(sisnr, imp, sdr, stoi))
+    print("SI-SDR={:0.2f},SI-SDR-imp={:0.2f},SDR={:0.2f},STOI={:0.3f}".format(sisnr, imp, sdr, stoi)
+          + (",SIR={:0.2f},SAR={:0.2f}".format(*bss) if bss is not None else ""))
     return sisnr, imp
 
 

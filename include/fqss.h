@@ -1267,6 +1267,30 @@ int64_t fqss_sdr_ws_doubles(int P, int64_t L, int filter_length);
 int fqss_sdr(const float* est, const float* ref, double* ws, int64_t ws_doubles, double* db, int P, int64_t L, int64_t ld_e, int64_t ld_r,
              int filter_length, int zero_mean, double load_diag, fqss_stream_t stream);
 
+/* BSS-eval SDR / SIR / SAR of the evaluation side (csrc/bss_eval.hip): the numbers of mir_eval.bss_eval_sources /
+ * fast_bss_eval.bss_eval_sources (BSS-eval v3), both third party and absent.  The definition below is restated from their published
+ * form; the kernels are pinned to THIS statement and to an independent fp64 checker (tests/helpers_bss.py), parity with either
+ * package is not pinned by anything.  est [S][L], ref [S][L] fp32 (row strides ld_e, ld_r >= L); tgt [S] int on the device or NULL for
+ * the identity: estimate j is scored against target tgt[j] (each value in 0..S-1; a value outside is clamped into it).
+ * 1 <= S <= 3, 1 <= T = filter_length <= 512, L >= 1.  Everything below in fp64.
+ *  1. Every signal has its mean subtracted when zero_mean and is divided by max(its 2-norm, 1e-6), as in fqss_sdr.
+ *  2. Correlations, terms beyond the ends absent: A_ik[tau] = sum_t ref_i[t] ref_k[t + tau] for |tau| < T;
+ *     B_ij[a] = sum_t ref_i[t] est_j[t + a] for 0 <= a < T; E_j = sum_t est_j[t]^2.
+ *  3. G of order n = S T, G[(i, a)][(k, b)] = A_ik[a - b], plus load_diag on the diagonal unless it is negative or NaN;
+ *     d_j[(i, a)] = B_ij[a].
+ *  4. With q = tgt[j]: E_all = d_j^T G^-1 d_j (the energy of est_j's projection on the T lagged copies of all targets);
+ *     E_tgt = d_j[q]^T G_qq^-1 d_j[q] (on those of its own target: the coh of fqss_sdr, by the same recursion); at S = 1 E_all := E_tgt.
+ *  5. out [3][S]: SDR_j = 10 log10(E_tgt / (E_j - E_tgt)), SIR_j = 10 log10(E_tgt / (E_all - E_tgt)),
+ *     SAR_j = 10 log10(E_all / (E_j - E_all)).  A denominator <= 0 with a positive numerator gives +inf (SIR at S = 1).  The three
+ *     values of estimate j are NaN when its own Toeplitz solve meets a non-positive prediction error; all of out is NaN when the
+ *     Cholesky factorisation of G meets a non-positive pivot (a silent or duplicated target).
+ * ws: at least fqss_bss_eval_ws_doubles(S, L, filter_length) doubles (the tile partials of the correlations, the reduced
+ * correlations and the (n + S) x n system; 0 for arguments that are refused), uninitialised.  Stream-ordered launches, nothing is read
+ * back; no floating-point atomics: out is the same bit for bit from run to run and on any stream. */
+int64_t fqss_bss_eval_ws_doubles(int S, int64_t L, int filter_length);
+int fqss_bss_eval(const float* est, const float* ref, const int* tgt, double* ws, int64_t ws_doubles, double* out, int S, int64_t L,
+                  int64_t ld_e, int64_t ld_r, int filter_length, int zero_mean, double load_diag, fqss_stream_t stream);
+
 /* Short-time objective intelligibility of the evaluation side (csrc/stoi.hip; process.metric_evaluation, process.py:129-152:
  * torchmetrics' ShortTimeObjectiveIntelligibility(fs)(preds = estimate, target = clean) = pystoi.stoi(clean, estimate, fs,
  * extended=False) of Taal et al. 2011 -- third party and absent).  The steps below were restated from memory of the published
